@@ -7,22 +7,29 @@ pool of 8x4096 scenarios.  One "step" = one env.step() of all worlds of a rank. 
 (up to --roll env steps per launch, agent records on chip, every step writes its full observation / reward / flag
 tensors to HBM slice t of a trajectory buffer).
 
-Timing (repeats, median): after --warmup untimed steps the block of EXACTLY --steps steps is timed
-`repeats` times, each time bracketed by barrier + torch.cuda.synchronize() on both sides and max-reduced over ranks (the
-clock of a rank stops when its own closing synchronize returns, the closing barrier follows: the collective's latency is
-the bench's, not the K steps'); `ms_per_step` / `value` are the MEDIAN block (min / max beside it).  Short blocks are
-repeated until the timed blocks cover at least 2 s whatever --steps is (the driver's 20-step block is 0.2 ms: ~9000
-blocks).  ONE clock: `value`, `ms_per_step` and `roofline.achieved` / `frac` all come from the wall-clock median block;
-HIP events ride in every SECOND block only (recording one costs the host 4 us) and give `roofline.launch_ms_hip_events` /
-`frac_hip_events`; the wall clock is the median of the blocks without them.
+Timing: after --warmup untimed steps, a plain run times ONE block of exactly --steps steps, bracketed by barrier +
+torch.cuda.synchronize() on both sides (the clock of a rank stops when its own closing synchronize returns; several ranks:
+max-reduced over ranks); `ms_per_step` is that block's wall-clock time / --steps and `value` = worlds x --steps / that time.
+--dump-outputs DIR then writes what the last timed step handed its caller (observations, rewards, flags, game-over; cfg4: also
+agent 0's actions; several ranks: rank 0's worlds) as DIR/<name>.npy in float32 / float64: inputs are seeded, so two builds can
+be compared output for output.
+
+--full (repeats, median) adds everything else the line used to carry: the block of EXACTLY --steps steps is timed
+`repeats` times and `ms_per_step` / `value` are the MEDIAN block (min / max beside it).  Short blocks are repeated until the
+timed blocks cover at least 2 s whatever --steps is (the driver's 20-step block is 0.2 ms: ~9000 blocks; the number of blocks,
+hence the last step dumped, then follows the clock unless --repeats fixes it).  ONE clock: `value`, `ms_per_step` and
+`roofline.achieved` / `frac` all come from the wall-clock median block; HIP events ride in every SECOND block only (recording
+one costs the host 4 us) and give `roofline.launch_ms_hip_events` / `frac_hip_events`; the wall clock is the median of the
+blocks without them.  Also under --full: the measured device-to-device copy ceiling, the replayed PMC counters, the cfg4 / cfg5
+per-part timings, the statistics collective's price (several ranks) and the CPU baseline (--no-cpu-baseline drops it).
 
 Multi-GPU: `python bench.py --gpus N` with no RANK in the environment starts N one-GPU ranks itself
 (torch.distributed.run, before anything touches the GPU in this process); under a launcher (RANK set) it is one rank.
 Worlds are independent, each rank owns its own 4096 worlds (weak scaling); the only collective is the RCCL all-gather
 of per-world episode statistics (24-byte records packed by one kernel, cagym_pack_episode_stats) on a side stream.  The
-counters are cumulative, so it is issued once every G timed blocks, G chosen from its measured duration so that it costs
-at most 1 % of the timed time; the main stream never waits for the side stream inside a block (the bracketing
-synchronize at the block's end is the only join).
+counters are cumulative, so a plain run issues it once after the timed block, and --full once every G timed blocks, G chosen
+from its measured duration so that it costs at most 1 % of the timed time; the main stream never waits for the side stream
+inside a block (the bracketing synchronize at the block's end is the only join).
 
 Other rows of SURVEY 8(d): --config cfg2 (4096 x 4 NonCooperative), cfg4 (8192 x 10: GA3C-CADRL agent 0 + 9 RVO among
 rectangles, LaserScan), cfg5 (2048 x 20 information-gain env part + planner primitives).
@@ -54,6 +61,33 @@ def profile_replay(name):
     return json.load(open(q)) if os.path.exists(q) else None
 
 
+def step_outputs(env):
+    """What env.step() hands its caller: the observation dict, reward, game-over and the info flags (world-major tensors)."""
+    out = dict(env._obs())
+    out.update(reward=env.reward, flags=env.flags, game_over=env.game_over)
+    return out
+
+
+def dump_outputs(path, outputs, limit=64 * 10**6):
+    """--dump-outputs: every tensor (leading axis = world) as path/<name>.npy, float64 kept, anything else as float32.  Above
+    `limit` bytes a fixed seeded sample of worlds, the same rows of every tensor, is written, their indices in world_index.npy."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy() for k, v in outputs.items()}
+    arrs = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrs.items()}
+    n = {a.shape[0] for a in arrs.values()}
+    assert len(n) == 1, "outputs disagree on the number of worlds"
+    n = n.pop()
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit:
+        keep = int(limit // (total / n + 8))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["world_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -64,7 +98,12 @@ def parse_args(argv=None):
     ap.add_argument("--agents", type=int, default=None)
     ap.add_argument("--policy", default=None, choices=["rvo", "noncoop"])
     ap.add_argument("--roll", type=int, default=512, help="max env steps per launch")
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks (0 = at least 5, more while the blocks are short)")
+    ap.add_argument("--full", action="store_true",
+                    help="time the block repeatedly (median) and add the line's secondary figures: roofline, copy ceiling, replayed counters, "
+                         "cfg4 / cfg5 per-part timings, CPU baseline; a plain run times one block of --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--repeats", type=int, default=0, help="--full: timed blocks (0 = at least 5, more while the blocks are short)")
     ap.add_argument("--per-step-launch", action="store_true", help="one cagym_step_autoreset launch per env step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--halves", type=int, default=1, help="cfg4: split the rank's worlds into this many independent groups, each with its own handle and HIP stream, so that one group's GA3C forward (matrix cores) overlaps another group's env step (vector units); 1 = one group (measured, round 4: 0.147 ms with 1, 0.190 with 2 - the forward is one latency-bound workgroup per CU whatever the number of worlds; round 3: 0.302 / 0.383 / 0.500 with 1 / 2 / 4: not kept as default)")
@@ -78,7 +117,12 @@ def parse_args(argv=None):
     ap.add_argument("--pool-factor", type=int, default=8, help="scenario pool size = factor x worlds")
     ap.add_argument("--scenarios", default="host", choices=["host", "device"],
                     help="host: numpy rejection sampler + upload; device: cagym_generate_scenarios (same rule)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.repeats and not args.full:
+        ap.error("--repeats needs --full (a plain run times one block of --steps steps)")
+    return args
 
 
 def self_launch(args):
@@ -227,6 +271,8 @@ def main():
         launch_mode = "cagym_step_autoreset per step" if args.per_step_launch else "cagym_rollout"
         kernel_name = env.kernel_name(rollout=not args.per_step_launch, auto_reset=True)
 
+        last_launch = {"steps": 0}
+
         def run(n_steps):
             done = 0
             launches = 0
@@ -238,10 +284,16 @@ def main():
                         launches += 1
                 else:
                     env.rollout(k, auto_reset=True, out=traj)
+                    last_launch["steps"] = k
                     launches += 1
                 done += k
             gather_stats(env)  # at most once per block; joined by the bracketing synchronize, never by the main stream
             return launches
+
+        def last_outputs():
+            if args.per_step_launch:
+                return step_outputs(env)
+            return {k: v[last_launch["steps"] - 1] for k, v in traj.items()}  # the last step's slice of the trajectory buffer
     elif args.config == "cfg4":
         # agent 0 GA3C-CADRL (state kernel + fused forward kernel per step) + 9 RVO agents among 2-10 rectangles,
         # LaserScan on every agent (scanned inside the step launch), game over when agent 0 is done, auto-reset
@@ -335,6 +387,10 @@ def main():
             gather_stats(env)
             return n_steps
 
+        def last_outputs():
+            outs = [dict(step_outputs(e_h), actions=x_h) for e_h, _g, x_h, _s in groups]
+            return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+
         def cfg4_extra():
             def loop(fn, reps=50):
                 fn()
@@ -394,6 +450,9 @@ def main():
                 env.step(ext, auto_reset=True)
             gather_stats(env)
             return n_steps
+
+        def last_outputs():
+            return step_outputs(env)
 
         def cfg5_extra():
             """The WHOLE cfg5 step as the reference runs it (env.py:342-379 _take_action_dmcts + experiments/src/dmcts.py:50-95):
@@ -511,7 +570,9 @@ def main():
 
     run(args.warmup)
     barrier()
-    if world_size > 1:
+    if not args.full:
+        stats_state["probing"] = True  # no collective inside the timed block: issued once after it, below
+    elif world_size > 1:
         # duration of the statistics collective (pack kernel + all-gather, bracketed by synchronize), median of 5, on its own
         tc = []
         for _ in range(5):
@@ -523,7 +584,7 @@ def main():
         stats_state["collective_ms"] = 1e3 * sorted(tc)[2]
         stats_state["probing"] = True  # no collective inside the probe blocks below
     blocks = [timed_block()]
-    if world_size > 1:
+    if args.full and world_size > 1:
         # one block in `every` carries the collective: at most 1 % of the timed time, priced on the median of five probe
         # blocks (the first block of a run is slower than the rest); same value on every rank
         while len(blocks) < 5:
@@ -545,9 +606,9 @@ def main():
             blocks.append(timed_block())
         return n
 
-    if args.repeats > 0:
+    if args.full and args.repeats > 0:
         more_blocks(max(0, args.repeats - len(blocks)))  # (a multi-rank run has timed its 5 probe blocks already)
-    else:  # at least 5 blocks, and short blocks are repeated until the timed blocks cover 2 s whatever --steps is
+    elif args.full:  # at least 5 blocks, and short blocks are repeated until the timed blocks cover 2 s whatever --steps is
         while len(blocks) < 50000:
             covered = sum(b[0] for b in blocks if b[1] is None)  # the wall clock is taken from the blocks without HIP events
             med = sorted(b[0] for b in blocks)[len(blocks) // 2]
@@ -562,41 +623,14 @@ def main():
     dev_sorted = sorted(b[1] for b in blocks if b[1] is not None)
     dev_ms = dev_sorted[len(dev_sorted) // 2] if dev_sorted else 1e3 * elapsed  # (--repeats 1: no block with events)
     launches = blocks[0][2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs())  # before anything below steps the env again (cfg4 / cfg5 extras)
 
     st = stats_mod.summarize(gathered if gathered is not None else env.packed_episode_stats())
     if rank == 0:
         total_worlds = N * world_size if scaling == "weak" else total
         value = total_worlds * args.steps / elapsed
         steps_per_launch = args.steps / launches
-        launch_ms_dev = dev_ms / launches            # HIP events around the block, median
-        launch_ms = 1e3 * elapsed / launches         # the wall clock `value` is computed from: ONE clock for the whole line
-        achieved = balg * N * M * steps_per_launch / (launch_ms * 1e-3) / 1e9
-        achieved_dev = balg * N * M * steps_per_launch / (launch_ms_dev * 1e-3) / 1e9
-        # HBM bytes per launch from the PMC counters are NOT collected in this run (they need rocprofv3 --pmc passes);
-        # the figure below replays profiles/ (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate passes) for the
-        # headline shape only and is labelled as such; null for any other shape.
-        traffic = None
-        replay = None  # counters of the headline shape, collected by the rocprofv3 --pmc passes of tools/final_profile_r3.sh
-        rp = next((q for q in (os.path.join(ROOT, "profiles", r, "headline_pmc.json") for r in ("r4", "r3")) if os.path.exists(q)), None)
-        if (N, M, policy, args.per_step_launch) == (4096, 10, "rvo", False) and rp:
-            replay = json.load(open(rp))
-        rp_name = os.path.relpath(rp, ROOT) if rp else None
-        traffic_per_agent_step = (replay["hbm_bytes_per_agent_step"] + replay.get("hbm_bytes_per_agent_per_launch", 0.0) / steps_per_launch) if replay else None
-        short_launch = steps_per_launch <= 32  # the driver's command: one 20-step launch per block
-        if replay:
-            traffic = traffic_per_agent_step * N * M * steps_per_launch / (launch_ms * 1e-3) / 1e9  # GB/s, comparable to `achieved`
-        # measured device-to-device copy ceiling next to the vendor HBM figure: read + write of 1 GiB
-        src = torch.empty(1 << 30, dtype=torch.uint8, device=device)
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        for _ in range(5):
-            dst.copy_(src)
-        c1.record()
-        torch.cuda.synchronize(device)
-        copy_gbs = 5 * 2 * (1 << 30) / (c0.elapsed_time(c1) * 1e-3) / 1e9
-        del src, dst
         line = {
             "metric": "env-steps/sec (whole node), %d worlds x %d agents" % (total_worlds if scaling == "strong" else N, M),
             "value": value, "unit": "env-steps/s", "n_gpus": world_size, "steps": args.steps, "warmup": args.warmup,
@@ -606,50 +640,83 @@ def main():
                        "worlds_per_gpu": N, "agents": M, "steps_per_launch": steps_per_launch,
                        "launch_mode": launch_mode,
                        "parallelism": "worlds sharded x%d, no data-path collective" % world_size},
-            "repeats": len(blocks), "timing": "wall clock: median of the %d timed blocks of %d steps without HIP events; launch_ms_hip_events: median of the %d blocks in between that carry them" % (len(walls), args.steps, len(dev_sorted)),
-            "ms_per_step_min": 1e3 * walls[0] / args.steps, "ms_per_step_max": 1e3 * walls[-1] / args.steps,
-            "timed_region_s": sum(walls),
-            "rccl_ranks": world_size if (world_size > 1 and backend == "nccl") else 0,
-            "stats_collective": None if world_size == 1 else {
-                "ms": stats_state["collective_ms"], "every_blocks": stats_state["every"],
-                "share_of_timed_time": stats_state["collective_ms"] * 1e-3 / (stats_state["every"] * max(elapsed, 1e-9)),
-                "what": "cagym_pack_episode_stats (one kernel) + all-gather of 24-byte records on a side stream, issued in one of every_blocks timed blocks; joined only by the block's closing synchronize"},
-            "collective_backend": backend if world_size > 1 else None,
+            "timing": "wall clock: one timed block of %d steps after %d warmup steps" % (args.steps, args.warmup),
             "agent_steps_per_s": value * M,
-            "roofline": {"bound": "hbm", "bound_note": "the HBM roofline is the one BASELINE.json's metric asks for; the counters (valu_busy below) show the kernel is bound by VALU issue, and its HBM traffic is below the algorithmic bytes",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": None if traffic is None else
-                         "replayed from %s (rocprofv3 --pmc passes on %s-step launches of this shape: FETCH_SIZE x2 + WRITE_SIZE per agent-step, plus the per-launch load / store of the agent records spread over this run's %d steps per launch), not measured in this run" % (rp_name, replay.get("steps_per_launch", "512"), int(steps_per_launch)),
-                         # what actually bounds the kernel (the HBM fraction above is the metric BASELINE.json asks for): VALU issue
-                         # (a 20-step launch ends with its slowest workgroup: its own counters, where the profile has them)
-                         "valu_busy": None if not replay else replay.get("valu_busy_20_step_launches", replay["valu_busy"]) if short_launch else replay["valu_busy"],
-                         "valu_insts_per_agent_step": None if not replay else replay.get("valu_insts_per_agent_step_20_step_launches", replay["valu_insts_per_agent_step"]) if short_launch else replay["valu_insts_per_agent_step"],
-                         "valu_source": None if not replay else "replayed from %s (SQ_ACTIVE_INST_VALU, SQ_INSTS_VALU, GRBM_GUI_ACTIVE of the %s-step launches), not measured in this run" % (rp_name, "20" if short_launch and "valu_busy_20_step_launches" in replay else replay.get("steps_per_launch", "512")),
-                         "kernel": kernel_name,
-                         "clock": "wall-clock median block (the clock of `value` and `ms_per_step`: frac = alg_bytes_per_agent_step x agents x worlds / ms_per_step / peak)",
-                         "launch_ms": launch_ms, "launch_ms_min": 1e3 * walls[0] / launches, "launch_ms_max": 1e3 * walls[-1] / launches,
-                         "launch_ms_hip_events": launch_ms_dev, "achieved_hip_events": achieved_dev, "frac_hip_events": achieved_dev / HBM_PEAK_GBS,
-                         "alg_bytes_per_agent_step": balg,
-                         "measured_d2d_copy_GBs": copy_gbs,
-                         "alg_bytes_per_launch": balg * N * M * steps_per_launch,
-                         "traffic_bytes_per_launch": None if traffic is None else traffic_per_agent_step * N * M * steps_per_launch},
             "episodes": st,
         }
-        for name, fn in extra.items():
-            line[name] = fn()
-        if args.config == "cfg4":  # the timed step holds three launches: the roofline object prices the env kernel alone
-            c4 = profile_replay("cfg4_pmc.json")
-            if c4:
-                line["roofline"].update({"valu_busy": c4.get("valu_busy"), "valu_insts_per_agent_step": c4.get("valu_insts_per_agent_step"),
-                                         "waves_per_simd": c4.get("waves_per_simd"),
-                                         "valu_source": "replayed from profiles/r4/cfg4_pmc.json (rocprofv3 --pmc SQ pass of the env kernel on this workload), not measured in this run"})
-            line["roofline"].update({"achieved": line["cfg4"]["env_kernel_hbm_frac"] * HBM_PEAK_GBS, "frac": line["cfg4"]["env_kernel_hbm_frac"],
-                                     "launch_ms": line["cfg4"]["env_kernel_ms_per_step"], "launch_ms_min": None, "launch_ms_max": None,
-                                     "note": ("env part alone: cagym_step_begin + cagym_step_finish back to back on one stream (both launches incl. laser scan), timed in its own loop"
-                                              if args.cfg4_step != "fused" else "env kernel alone (cagym_step_autoreset incl. laser scan), timed in its own loop")})
-        if not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(M, pol, config=args.config)
+        if args.full:
+            launch_ms_dev = dev_ms / launches            # HIP events around the block, median
+            launch_ms = 1e3 * elapsed / launches         # the wall clock `value` is computed from: ONE clock for the whole line
+            achieved = balg * N * M * steps_per_launch / (launch_ms * 1e-3) / 1e9
+            achieved_dev = balg * N * M * steps_per_launch / (launch_ms_dev * 1e-3) / 1e9
+            # HBM bytes per launch from the PMC counters are NOT collected in this run (they need rocprofv3 --pmc passes);
+            # the figure below replays profiles/ (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate passes) for the
+            # headline shape only and is labelled as such; null for any other shape.
+            traffic = None
+            replay = None  # counters of the headline shape, collected by the rocprofv3 --pmc passes of tools/final_profile_r3.sh
+            rp = next((q for q in (os.path.join(ROOT, "profiles", r, "headline_pmc.json") for r in ("r4", "r3")) if os.path.exists(q)), None)
+            if (N, M, policy, args.per_step_launch) == (4096, 10, "rvo", False) and rp:
+                replay = json.load(open(rp))
+            rp_name = os.path.relpath(rp, ROOT) if rp else None
+            traffic_per_agent_step = (replay["hbm_bytes_per_agent_step"] + replay.get("hbm_bytes_per_agent_per_launch", 0.0) / steps_per_launch) if replay else None
+            short_launch = steps_per_launch <= 32  # the driver's command: one 20-step launch per block
+            if replay:
+                traffic = traffic_per_agent_step * N * M * steps_per_launch / (launch_ms * 1e-3) / 1e9  # GB/s, comparable to `achieved`
+            # measured device-to-device copy ceiling next to the vendor HBM figure: read + write of 1 GiB
+            src = torch.empty(1 << 30, dtype=torch.uint8, device=device)
+            dst = torch.empty_like(src)
+            dst.copy_(src)
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            for _ in range(5):
+                dst.copy_(src)
+            c1.record()
+            torch.cuda.synchronize(device)
+            copy_gbs = 5 * 2 * (1 << 30) / (c0.elapsed_time(c1) * 1e-3) / 1e9
+            del src, dst
+            line.update({
+                "repeats": len(blocks), "timing": "wall clock: median of the %d timed blocks of %d steps without HIP events; launch_ms_hip_events: median of the %d blocks in between that carry them" % (len(walls), args.steps, len(dev_sorted)),
+                "ms_per_step_min": 1e3 * walls[0] / args.steps, "ms_per_step_max": 1e3 * walls[-1] / args.steps,
+                "timed_region_s": sum(walls),
+                "rccl_ranks": world_size if (world_size > 1 and backend == "nccl") else 0,
+                "stats_collective": None if world_size == 1 else {
+                    "ms": stats_state["collective_ms"], "every_blocks": stats_state["every"],
+                    "share_of_timed_time": stats_state["collective_ms"] * 1e-3 / (stats_state["every"] * max(elapsed, 1e-9)),
+                    "what": "cagym_pack_episode_stats (one kernel) + all-gather of 24-byte records on a side stream, issued in one of every_blocks timed blocks; joined only by the block's closing synchronize"},
+                "collective_backend": backend if world_size > 1 else None,
+                "roofline": {"bound": "hbm", "bound_note": "the HBM roofline is the one BASELINE.json's metric asks for; the counters (valu_busy below) show the kernel is bound by VALU issue, and its HBM traffic is below the algorithmic bytes",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "traffic_source": None if traffic is None else
+                             "replayed from %s (rocprofv3 --pmc passes on %s-step launches of this shape: FETCH_SIZE x2 + WRITE_SIZE per agent-step, plus the per-launch load / store of the agent records spread over this run's %d steps per launch), not measured in this run" % (rp_name, replay.get("steps_per_launch", "512"), int(steps_per_launch)),
+                             # what actually bounds the kernel (the HBM fraction above is the metric BASELINE.json asks for): VALU issue
+                             # (a 20-step launch ends with its slowest workgroup: its own counters, where the profile has them)
+                             "valu_busy": None if not replay else replay.get("valu_busy_20_step_launches", replay["valu_busy"]) if short_launch else replay["valu_busy"],
+                             "valu_insts_per_agent_step": None if not replay else replay.get("valu_insts_per_agent_step_20_step_launches", replay["valu_insts_per_agent_step"]) if short_launch else replay["valu_insts_per_agent_step"],
+                             "valu_source": None if not replay else "replayed from %s (SQ_ACTIVE_INST_VALU, SQ_INSTS_VALU, GRBM_GUI_ACTIVE of the %s-step launches), not measured in this run" % (rp_name, "20" if short_launch and "valu_busy_20_step_launches" in replay else replay.get("steps_per_launch", "512")),
+                             "kernel": kernel_name,
+                             "clock": "wall-clock median block (the clock of `value` and `ms_per_step`: frac = alg_bytes_per_agent_step x agents x worlds / ms_per_step / peak)",
+                             "launch_ms": launch_ms, "launch_ms_min": 1e3 * walls[0] / launches, "launch_ms_max": 1e3 * walls[-1] / launches,
+                             "launch_ms_hip_events": launch_ms_dev, "achieved_hip_events": achieved_dev, "frac_hip_events": achieved_dev / HBM_PEAK_GBS,
+                             "alg_bytes_per_agent_step": balg,
+                             "measured_d2d_copy_GBs": copy_gbs,
+                             "alg_bytes_per_launch": balg * N * M * steps_per_launch,
+                             "traffic_bytes_per_launch": None if traffic is None else traffic_per_agent_step * N * M * steps_per_launch},
+            })
+            for name, fn in extra.items():
+                line[name] = fn()
+            if args.config == "cfg4":  # the timed step holds three launches: the roofline object prices the env kernel alone
+                c4 = profile_replay("cfg4_pmc.json")
+                if c4:
+                    line["roofline"].update({"valu_busy": c4.get("valu_busy"), "valu_insts_per_agent_step": c4.get("valu_insts_per_agent_step"),
+                                             "waves_per_simd": c4.get("waves_per_simd"),
+                                             "valu_source": "replayed from profiles/r4/cfg4_pmc.json (rocprofv3 --pmc SQ pass of the env kernel on this workload), not measured in this run"})
+                line["roofline"].update({"achieved": line["cfg4"]["env_kernel_hbm_frac"] * HBM_PEAK_GBS, "frac": line["cfg4"]["env_kernel_hbm_frac"],
+                                         "launch_ms": line["cfg4"]["env_kernel_ms_per_step"], "launch_ms_min": None, "launch_ms_max": None,
+                                         "note": ("env part alone: cagym_step_begin + cagym_step_finish back to back on one stream (both launches incl. laser scan), timed in its own loop"
+                                                  if args.cfg4_step != "fused" else "env kernel alone (cagym_step_autoreset incl. laser scan), timed in its own loop")})
+            if not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(M, pol, config=args.config)
         print(json.dumps(line), flush=True)
     if world_size > 1:
         dist.barrier()

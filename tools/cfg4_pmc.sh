@@ -3,7 +3,7 @@
 O=${1:-gpurun_out/cfg4_pmc}
 mkdir -p $O
 export TMPDIR=/tmp
-CMD="python3 bench.py --config cfg4 --steps 200 --warmup 50 --repeats 3 --no-cpu-baseline"
+CMD="python3 bench.py --full --config cfg4 --steps 200 --warmup 50 --repeats 3 --no-cpu-baseline"
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS -d $O/p1 -o run -- $CMD > /dev/null 2>&1
 python tools/pmc_summary.py $O/p1 k_step3 > $O/p1.txt
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d $O/p2 -o run -- $CMD > $O/p2.log 2>&1 && python tools/pmc_summary.py $O/p2 k_step3 > $O/p2.txt

@@ -3,7 +3,7 @@
 O=${1:-gpurun_out/cfg5_prof}
 mkdir -p $O
 export TMPDIR=/tmp
-CMD="python3 bench.py --config cfg5 --steps 50 --warmup 10 --repeats 2 --no-cpu-baseline"
+CMD="python3 bench.py --full --config cfg5 --steps 50 --warmup 10 --repeats 2 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $CMD > $O/bench_under_rocprof.json 2>/dev/null || exit 1
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAIT_INST_ANY -d $O/pmc_sq -o run -- $CMD > /dev/null 2>&1 || exit 1
 rocprofv3 --kernel-trace --output-format csv --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCP_TCC_READ_REQ_sum -d $O/pmc_tcc -o run -- $CMD > /dev/null 2>&1 || exit 1

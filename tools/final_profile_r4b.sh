@@ -10,11 +10,11 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -s > $O/gputests_full.log 2>&1 || { tail -30 $O/gputests_full.log; exit 1; }
 grep -v "^$" $O/gputests_full.log | grep "passed\|failed\|max |p\|laserscan:" > $O/gputests.log; cat $O/gputests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 echo headline done
-python bench.py --config cfg4 --steps 200 --warmup 50 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg4 -o run -- python3 bench.py --config cfg4 --steps 200 --warmup 50 --repeats 5 --no-cpu-baseline > $O/bench_cfg4_under_rocprof.json 2>/dev/null
+python bench.py --full --config cfg4 --steps 200 --warmup 50 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg4 -o run -- python3 bench.py --full --config cfg4 --steps 200 --warmup 50 --repeats 5 --no-cpu-baseline > $O/bench_cfg4_under_rocprof.json 2>/dev/null
 cp $(find $O/stats_cfg4 -name "*kernel_stats.csv" | head -1) $O/bench_cfg4_kernel_stats.csv
 echo cfg4 done
 python tools/ga3c_phases.py 2>&1 | grep -v amdgpu.ids > $O/ga3c_forward_phases_h16.txt
