@@ -469,6 +469,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->obst_rvo = new_obst_rvo;
     e->D.ko = new_ko;
     e->scenarios_set = true;
+    e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
     return CAGYM_OK;
 }
 
@@ -520,6 +521,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     }
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     e->scenarios_set = true;
+    e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
     return CAGYM_OK;
 }
 

@@ -39,8 +39,12 @@ enum { CAGYM_POL_STATIC = 0,   /* policies/StaticPolicy.py:9-12            a = (
        CAGYM_POL_LEARNING = 3, /* policies/LearningPolicy.py:11-16         a = (v_pref*u0, 4*(2*u1-1))     */
        CAGYM_POL_CARRL = 4,    /* policies/CARRLPolicy.py:5-15             11-row table, index in ext[.,0] */
        CAGYM_POL_RVO = 5,      /* policies/RVOPolicy.py:53-117             ORCA half-planes (other agents and, :56-57, the
-                                  world's rectangles) + 2-D LP; needs 2*max_obstacles + max_agents - 1 <= 32 (64 for
-                                  max_agents > 10) half-planes per ego and non-degenerate rectangles               */
+                                  world's rectangles) + 2-D LP; needs non-degenerate rectangles, and among them
+                                  cagym_set_scenarios caps the handle's max_obstacles per kernel specialisation:
+                                  max_agents 4: 6, 10: 11, 20: 15, other <= 12: 9, 13..32: 16 (2*max_obstacles +
+                                  max_agents - 1 half-plane slots of an LP group: 16 for max_agents 4, 32 for 10, 64
+                                  otherwise; 2*max_obstacles <= 32; the obstacle-candidate lists in the LP scratch,
+                                  13 B per (ego, candidate); the roll-out's LDS within 160 KB)                      */
        CAGYM_POL_GA3C = 6,     /* policies/GA3CCADRLPolicy.py:34-43        action supplied by cagym_ga3c_* */
        CAGYM_POL_IGMCTS = 7 }; /* policies/ig_mcts.py:79-109               (v, omega) supplied by planner  */
 

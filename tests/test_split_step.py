@@ -120,3 +120,24 @@ def test_split_step_without_rvo_agents_and_call_order():
     split.env.reset()  # a reset voids a pending begin
     with pytest.raises(RuntimeError, match="without a cagym_step_begin"):
         split.env.step_finish()
+    # a new scenario pool voids it too: the pending begin solved the old pool's worlds (k_step_post3 would read velocities
+    # that nobody wrote for the new one)
+    S = split.env.S
+    rvo_pool = scen.random_worlds_fast(S, M, seed=4)
+    split.env.set_scenarios(rvo_pool, scen.POLICY_RVO, scen.DYN_UNICYCLE, coop=np.full((S, M), 0.5))
+    split.env.reset()
+    split.env.step_begin()  # an RVO pool: the PRE half is launched
+    split.env.set_scenarios(rvo_pool, scen.POLICY_RVO, scen.DYN_UNICYCLE, coop=np.full((S, M), 0.5))
+    with pytest.raises(RuntimeError, match="without a cagym_step_begin"):
+        split.env.step_finish()
+    split.env.reset()
+    split.env.step_begin()
+    assert split.env.generate_scenarios(seed=9) == 0
+    with pytest.raises(RuntimeError, match="without a cagym_step_begin"):
+        split.env.step_finish()
+    # a refused pool changes nothing, a pending begin included
+    split.env.reset()
+    split.env.step_begin()
+    with pytest.raises(RuntimeError, match="n_agents out of range"):
+        split.env.set_scenarios(rvo_pool, scen.POLICY_RVO, scen.DYN_UNICYCLE, n_agents=np.full(S, M + 1, dtype=np.int32))
+    split.env.step_finish()
