@@ -3,7 +3,8 @@
 for MANY worlds at once: batched env + belief update + team MI reward + Dec-MCTS trees, all on the GPU.
 Every world runs the same scenario with its own random streams; prints the cumulative team reward statistics.
 
-usage: python examples/dmcts_experiment.py [--worlds 256] [--steps 30] [--Ntree 30] [--Ncycles 5] [--cp 1.0]"""
+usage: python examples/dmcts_experiment.py [--worlds 256] [--steps 30] [--Ntree 30] [--Ncycles 5] [--cp 1.0]
+                                         [--parallelize-agents]  (the reference's agent-parallel planning mode)"""
 import argparse
 import importlib
 import os
@@ -25,6 +26,7 @@ ap.add_argument("--Ntree", type=int, default=30)
 ap.add_argument("--Ncycles", type=int, default=5)
 ap.add_argument("--Nsims", type=int, default=10)
 ap.add_argument("--cp", type=float, default=1.0)
+ap.add_argument("--parallelize-agents", action="store_true", help="ig_mcts.set_param(..., parallelize_agents=True)")
 args = ap.parse_args()
 
 N, M = args.worlds, 10
@@ -41,7 +43,7 @@ env.set_scenarios(np.tile(a6[None], (N, 1, 1)), np.tile(pol[None], (N, 1)), scen
 env.reset()
 ig = igm.InfoGain(env)                                            # detect_fov 60 deg, range 5 m, xdt 5 (dmcts.py:74-78)
 planner = dm.DeviceDecMCTSPlanner(ig, 3, radius=0.5, Ntree=args.Ntree, Nsims=args.Nsims, horizon=4, c_p=args.cp,
-                                  gamma=0.95, Ncycles=args.Ncycles, seed=0)
+                                  gamma=0.95, Ncycles=args.Ncycles, seed=0, parallelize_agents=args.parallelize_agents)
 world = torch.arange(N, dtype=torch.int32, device=env.device)
 targets = torch.tensor(a6[3:5, 0:2], device=env.device)
 cum = torch.zeros(N, dtype=torch.float64, device=env.device)

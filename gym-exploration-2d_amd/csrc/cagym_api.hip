@@ -1032,8 +1032,11 @@ inline size_t dm_align(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t cagym_dmcts_workspace_bytes(int n_worlds, const cagym_dmcts_params* p) {
     if (!p || n_worlds < 1 || p->n_robots < 1 || p->Ntree < 1 || p->Ncycles < 1) return 0;
     const size_t trees = (size_t)n_worlds * p->n_robots;
-    return dm_align(trees * sizeof(DmPublished)) + dm_align(trees * 2 * sizeof(int32_t)) + dm_align(trees * (size_t)dm_node_cap(*p) * sizeof(DmNode)) +
-           dm_align(trees * (size_t)dm_mask_cap(*p) * sizeof(DmMasks)) + trees * (size_t)dm_node_cap(*p) * sizeof(double);  // (last: the trees' compact value arrays)
+    const size_t bytes = dm_align(trees * sizeof(DmPublished)) + dm_align(trees * 2 * sizeof(int32_t)) + dm_align(trees * (size_t)dm_node_cap(*p) * sizeof(DmNode)) +
+                         dm_align(trees * (size_t)dm_mask_cap(*p) * sizeof(DmMasks)) + trees * (size_t)dm_node_cap(*p) * sizeof(double);  // (last: the trees' compact value arrays)
+    if (p->parallel_agents != 1) return bytes;
+    // agent-parallel mode: behind the above, the second publication buffer and the robots' distributions between the launches
+    return dm_align(bytes) + dm_align(trees * sizeof(DmPublished)) + trees * sizeof(DmDist);
 }
 
 int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* poses, void* workspace,
@@ -1048,6 +1051,7 @@ int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* 
         p.comm_n < 1 || p.comm_n > DM_MAXCOMM || p.Ntree < 1 || p.Ncycles < 1 || p.xdt < 1 || p.xdt > 1000 ||
         (size_t)p.Ntree * p.Ncycles > 100000)
         return fail(e, CAGYM_E_INVALID, "Dec-MCTS parameters out of range (n_robots<=8, horizon<=8, Nsims<=32, comm_n<=8)");
+    if (p.parallel_agents > 1) return fail(e, CAGYM_E_INVALID, "Dec-MCTS parallel_agents must be 0 or 1");
     const int N = e->cfg.n_worlds;
     if (workspace_bytes < cagym_dmcts_workspace_bytes(N, params)) return fail(e, CAGYM_E_INVALID, "workspace too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1058,13 +1062,31 @@ int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* 
     DmNode* nodes = reinterpret_cast<DmNode*>(base + dm_align(trees * sizeof(DmPublished)) + dm_align(trees * 2 * sizeof(int32_t)));
     DmMasks* masks = reinterpret_cast<DmMasks*>(reinterpret_cast<unsigned char*>(nodes) + dm_align(trees * (size_t)dm_node_cap(p) * sizeof(DmNode)));
     double* mu = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(masks) + dm_align(trees * (size_t)dm_mask_cap(p) * sizeof(DmMasks)));
-    if (p.reset_comms) HIPCHK(e, hipMemsetAsync(pub, 0, trees * sizeof(DmPublished), st));
+    // agent-parallel mode: the second publication buffer and the distributions (cagym_dmcts_workspace_bytes)
+    DmPublished* pub2 = reinterpret_cast<DmPublished*>(reinterpret_cast<unsigned char*>(mu) + dm_align(trees * (size_t)dm_node_cap(p) * sizeof(double)));
+    DmDist* dist = reinterpret_cast<DmDist*>(reinterpret_cast<unsigned char*>(pub2) + dm_align(trees * sizeof(DmPublished)));
+    if (p.reset_comms) {
+        HIPCHK(e, hipMemsetAsync(pub, 0, trees * sizeof(DmPublished), st));
+        if (p.parallel_agents) HIPCHK(e, hipMemsetAsync(pub2, 0, trees * sizeof(DmPublished), st));
+    }
     DmParams P;
     P.R = p.n_robots; P.Ntree = p.Ntree; P.Nsims = p.Nsims; P.horizon = p.horizon; P.Ncycles = p.Ncycles; P.comm_n = p.comm_n;
     P.node_cap = dm_node_cap(p); P.mask_cap = dm_mask_cap(p); P.xdt = p.xdt; P.call_base = p.call_base;
     P.c_p = p.c_p; P.gamma = p.gamma; P.radius = p.radius; P.dt = p.dt; P.fov = p.fov_rad; P.range = p.range; P.seed = p.seed;
-    hipLaunchKernelGGL(k_dmcts_plan, dim3((unsigned)N), dim3(DM_THREADS), 0, st, e->G, P, poses, nodes, masks, mu, nn, pub, actions, paths, stats);
-    HIPCHK(e, hipGetLastError());
+    if (!p.parallel_agents) {
+        hipLaunchKernelGGL(k_dmcts_plan, dim3((unsigned)N), dim3(DM_THREADS), 0, st, e->G, P, poses, nodes, masks, mu, nn, pub, actions, paths, stats);
+        HIPCHK(e, hipGetLastError());
+        return CAGYM_OK;
+    }
+    // one launch per cycle, each reading the publications of the one before from one buffer and writing the other.  The last
+    // cycle writes `pub`, which both modes read at the next call; with an odd number of cycles the first reads a copy of it.
+    DmPublished* buf[2] = {pub, pub2};
+    if (p.Ncycles & 1) HIPCHK(e, hipMemcpyAsync(pub2, pub, trees * sizeof(DmPublished), hipMemcpyDeviceToDevice, st));
+    for (int c = 0; c < p.Ncycles; c++) {
+        hipLaunchKernelGGL(k_dmcts_plan_cycle, dim3((unsigned)trees), dim3(DM_THREADS), 0, st, e->G, P, c, poses, nodes, masks, mu, nn,
+                           buf[(p.Ncycles - c) & 1], buf[(p.Ncycles - c - 1) & 1], dist, actions, paths, stats);
+        HIPCHK(e, hipGetLastError());
+    }
     return CAGYM_OK;
 }
 

@@ -7,6 +7,10 @@
 // (DecMCTSPlanner, host tree over the same device primitives): generator keys, summation orders and tie rules are
 // the same, and the two make identical decisions (tests/test_dmcts.py).
 //
+// Two kernels share the grow (dm_grow) and everything around it: k_dmcts_plan, the sequential mode (one workgroup per world,
+// robots in index order), and k_dmcts_plan_cycle, the reference's agent-parallel mode (ig_mcts.set_param(..., parallelize_agents=True):
+// one workgroup per world and robot, one launch per cycle; tests/test_dmcts_parallel.py).
+//
 // Tree bookkeeping is a few scalar operations per grow and runs on lane 0; what costs time -- the visibility set of a newly
 // selected node, the Nsims x (horizon - stage) roll-out steps, the MI rewards, the top-n scan -- is spread over the workgroup
 // with the functions of cagym_ig.h (so the numbers are those of cagym_ig_rollouts bit for bit).
@@ -343,326 +347,402 @@ __device__ inline double dm_reward_wave(const double* belief, const unsigned lon
     return __shfl(r, 0, 64);
 }
 
+// What a kernel keeps in LDS during a planning step.  dist_*: the robots' action distributions (my_act_dist); the one-world kernel
+// holds all R rows, the per-cycle kernel the row of its own robot.
+struct DmLds {
+    unsigned long long vis[IG_BEL], excl[IG_BEL], bobs[IG_BEL];
+    unsigned long long wvis[DM_WAVES][IG_BEL], wobs[DM_WAVES][IG_BEL], wbobs[DM_WAVES][IG_BEL];  // a wave's own masks
+    uint16_t wlist[DM_WAVES][IG_BEL * IG_BEL / 4];  // cone cells of the wave's current visibility query (a 60-degree cone of 5 m holds < 100)
+    uint8_t wtail[DM_WAVES][DM_MAXH], wbtail[DM_WAVES][DM_MAXH];
+    double wbest[DM_WAVES];
+    int wbest_sim[DM_WAVES];
+    double red[DM_THREADS];
+    int redi[DM_THREADS];
+    double cpose[27];
+    int cfeas[9];
+    double rew[DM_MAXSIMS];
+    uint8_t btail[DM_MAXH];
+    int sh_sel, sh_pick, sh_n, sh_depth;
+    int sh_path[DM_MAXH + 2], sh_better[DM_MAXH + 2];
+    int picks[DM_MAXCOMM];
+    int dist_idx[DM_MAXR][DM_MAXCOMM];
+    double dist_q[DM_MAXR][DM_MAXCOMM];
+    int dist_n[DM_MAXR];
+};
+
+// A robot's action distribution between the launches of the agent-parallel mode (k_dmcts_plan_cycle): the LDS row dist_*[dr].
+struct DmDist {
+    int32_t n, idx[DM_MAXCOMM];
+    double q[DM_MAXCOMM];
+};
+
+// ---- Tree.__init__ (DecMCTS.py:92-138): root + expansion of the root; my_act_dist = the root state alone (LDS row dr) -----
+__device__ __forceinline__ void dm_init_tree(const uint32_t* d2, const DmParams& P, const double* pose, DmNode* T, DmMasks* MK, double* MU,
+                                             int* nn, DmLds& S, int dr, int tid) {
+    for (int j = tid; j < IG_BEL; j += DM_THREADS) { MK[0].observed[j] = 0ull; MK[0].best_obs[j] = 0ull; }
+    if (tid == 0) {
+        T[0].mu = 0.0; T[0].Nv = 0.0; T[0].best = 0.0;
+        T[0].pose[0] = pose[0]; T[0].pose[1] = pose[1]; T[0].pose[2] = pose[2];
+        T[0].parent = -1; T[0].child0 = -1; T[0].mask = 0; T[0].nchild = 0; T[0].stage = 0; T[0].has_roll = 0; T[0].seq_len = 0;
+        for (int a = 0; a < DM_MAXH; a++) { T[0].acts[a] = DM_NOACT; T[0].seq[a] = DM_NOACT; }
+        MU[0] = 0.0;
+        nn[0] = 1; nn[1] = 1;
+        S.dist_n[dr] = 1; S.dist_idx[dr][0] = 0; S.dist_q[dr][0] = 1.0;
+    }
+    __syncthreads();
+    dm_expand(d2, T, MU, nn, 0, P, S.cpose, S.cfeas, tid);
+}
+
+// ---- one Tree.grow of robot r in world w (DecMCTS.py:273-360) with generator key `call`.  pub: the world's R published
+//      distributions this grow samples the other robots' plans from; the robot's own distribution is the LDS row dr -----
+__device__ __forceinline__ void dm_grow(const uint32_t* d2, const double* belief, const DmParams& P, const IgCone& cone, DmNode* T,
+                                        DmMasks* MK, double* MU, int* nn, const DmPublished* pub, int w, int r, int dr,
+                                        unsigned int call, DmLds& S, int tid) {
+    const int R = P.R, H = P.horizon;
+    const int wave = tid >> 6, lane = tid & 63;
+    DMSTAMP_BEGIN();
+    DMSTAMP_COUNT();
+    // ---- _get_system_state (DecMCTS.py:182-194): one sampled plan per robot this one listens to -------
+    for (int j = tid; j < IG_BEL; j += DM_THREADS) S.excl[j] = 0ull;
+    __syncthreads();
+    for (int other = 0; other < R - 1; other++) {  // Q15 listening graph (see dmcts.py)
+        if (other == r || pub[other].n <= 0) continue;  // uniform
+        if (tid == 0) {
+            const int n = pub[other].n;
+            double tot = 0.0;
+            for (int k = 0; k < n; k++) tot += pub[other].q[k];
+            const double thr = dm_u01(P.seed ^ 0x5DEECE66Dull, (unsigned int)w, (call << 4) | (unsigned int)other) * tot;
+            int pick = n - 1;
+            double run = 0.0;
+            for (int k = 0; k < n; k++) {
+                run += pub[other].q[k];
+                if (run > thr) { pick = k; break; }
+            }
+            S.sh_pick = pick;
+        }
+        __syncthreads();
+        for (int j = tid; j < IG_BEL; j += DM_THREADS) S.excl[j] |= pub[other].obs[S.sh_pick][j];
+        __syncthreads();
+    }
+    DMSTAMP(0);
+    // ---- selection (DecMCTS.py:14-18, 140-153, 288-289) --------------------------------------------------
+    // (the children of a node are scored side by side on the lanes of wave 0 - a logarithm, a division and a square root
+    //  each; lane 0 alone walked up to 4 levels x 9 children - and the first maximum in child order is taken, as `if u > best`)
+    if (wave == 0) {
+        int node = 0, depth = 0;
+        for (;;) {
+            if (lane == 0) S.sh_path[depth] = node;  // the walk from the root: back-propagation climbs it without reloading parents
+            const int nc = T[node].nchild;  // uniform
+            if (nc <= 0) break;
+            depth++;
+            const double n_p = T[node].Nv;
+            const int c0 = T[node].child0;
+            double u = -INFINITY;
+            int bi = lane;
+            if (lane < nc) {
+                const DmNode& ch = T[c0 + lane];
+                if (ch.Nv == 0.0) u = INFINITY;
+                else u = n_p > 0.0 ? ch.mu + 2 * P.c_p * sqrt(2 * log(n_p) / ch.Nv) : ch.mu;
+            }
+            for (int off = 8; off > 0; off >>= 1) {  // nc <= 9: lanes 0..15
+                const double u2 = __shfl_down(u, off, 64);
+                const int i2 = __shfl_down(bi, off, 64);
+                if (u2 > u || (u2 == u && i2 < bi)) { u = u2; bi = i2; }
+            }
+            node = c0 + __shfl(bi, 0, 64);
+        }
+        if (lane == 0) { S.sh_sel = node; S.sh_depth = depth; }
+    }
+    __syncthreads();
+    const int s = S.sh_sel;
+    DMSTAMP(1);
+    dm_materialise(d2, T, MK, nn + 1, s, P, S.vis, tid, cone);
+    DMSTAMP(2);
+    dm_expand(d2, T, MU, nn, s, P, S.cpose, S.cfeas, tid);
+    DMSTAMP(3);
+    // ---- simulation (DecMCTS.py:233-271, 296-327): Nsims random roll-outs from the selected node, one wave each ----
+    const int steps = H - T[s].stage;
+    const unsigned long long rseed = P.seed * 1000003ull + (unsigned long long)call;
+    const DmMasks& sm = MK[T[s].mask];
+    {
+        double my_best = -INFINITY;
+        int my_best_sim = 0x7fffffff;
+        for (int sim = wave; sim < P.Nsims; sim += DM_WAVES) {
+            unsigned long long* obs = S.wobs[wave];
+            if (lane < IG_BEL) obs[lane] = sm.observed[lane];
+            dm_wave_sync();
+            double x = T[s].pose[0], y = T[s].pose[1], th = T[s].pose[2];
+            for (int t = 0; t < steps; t++) {
+                const uint32_t k = ig_rand_primitive(rseed, (uint32_t)w, (uint32_t)sim, (uint32_t)t);
+                double v, wv;
+                dm_prim((int)k, v, wv);
+                const bool ok = dm_next_pose_wave(d2, x, y, th, v, wv, P.xdt, P.dt, P.radius, lane);  // uniform across the wave
+                DMSTAMP(8);
+                if (ok) {
+                    dm_visible_wave(d2, x, y, th, P.fov, P.range, S.wvis[wave], S.wlist[wave], lane, cone);
+                    if (lane < IG_BEL) obs[lane] |= S.wvis[wave][lane];
+                    dm_wave_sync();
+                }
+                if (lane == 0) S.wtail[wave][t] = ok ? (uint8_t)k : (uint8_t)DM_INFEAS;
+                DMSTAMP(9);
+            }
+            if (lane < IG_BEL) S.wvis[wave][lane] = obs[lane] & ~S.excl[lane];  // mcts_reward (ig_mcts.py:234-241)
+            dm_wave_sync();
+            const double rr = dm_reward_wave(belief, S.wvis[wave], lane);
+            DMSTAMP(10);
+            if (lane == 0) S.rew[sim] = rr;
+            if (rr > my_best) {  // uniform across the wave; `if rew > best_reward` keeps the first maximum
+                my_best = rr;
+                my_best_sim = sim;
+                if (lane < IG_BEL) S.wbobs[wave][lane] = obs[lane];
+                if (lane < DM_MAXH) S.wbtail[wave][lane] = lane < steps ? S.wtail[wave][lane] : (uint8_t)DM_NOACT;
+            }
+            dm_wave_sync();
+        }
+        if (lane == 0) { S.wbest[wave] = my_best; S.wbest_sim[wave] = my_best_sim; }
+    }
+    DMSTAMP(4);
+    __syncthreads();
+    DMSTAMP(5);
+    // the first maximum in roll-out order: highest reward, lowest roll-out index among equals
+    int bw = 0;
+    for (int q = 1; q < DM_WAVES; q++)
+        if (S.wbest[q] > S.wbest[bw] || (S.wbest[q] == S.wbest[bw] && S.wbest_sim[q] < S.wbest_sim[bw])) bw = q;
+    const double best = S.wbest[bw];
+    for (int j = tid; j < IG_BEL; j += DM_THREADS) S.bobs[j] = S.wbobs[bw][j];
+    if (tid < DM_MAXH) S.btail[tid] = S.wbtail[bw][tid];
+    __syncthreads();
+    // ---- back-propagation (DecMCTS.py:329-356) ----------------------------------------------------------------
+    for (int j = tid; j < IG_BEL; j += DM_THREADS) MK[T[s].mask].best_obs[j] = S.bobs[j];
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int sim = 0; sim < P.Nsims; sim++) acc += S.rew[sim];
+        const double avg = acc / P.Nsims;
+        const int st = T[s].stage;
+        T[s].mu = avg; T[s].best = best; T[s].Nv = 1.0; T[s].has_roll = 1;
+        MU[s] = avg;
+        T[s].seq_len = (uint8_t)H;
+        for (int a = 0; a < DM_MAXH; a++) T[s].seq[a] = a < st ? T[s].acts[a] : (a < H ? S.btail[a - st] : (uint8_t)DM_NOACT);
+        S.red[0] = avg;
+    }
+    __syncthreads();
+    const double avg = S.red[0];
+    // the selected node's ancestors (the walk T[a].parent, recorded at selection).  Each one's update reads and writes only its
+    // own statistics, so they are independent: thread d takes ancestor d (round 4; lane 0 climbed them one after the other with
+    // two barriers and a dependent round trip to the node pool per level)
+    if (tid < S.sh_depth) {
+        const int a = S.sh_path[tid];
+        const bool better = best > T[a].best;
+        S.sh_better[tid] = better ? T[a].mask : -1;
+        const double mu_new = (P.gamma * T[a].mu * T[a].Nv + avg) / (T[a].Nv + 1);
+        T[a].mu = mu_new;
+        MU[a] = mu_new;
+        T[a].Nv = P.gamma * T[a].Nv + 1;
+        if (better) {
+            T[a].best = best;
+            T[a].has_roll = 1;
+            T[a].seq_len = T[s].seq_len;
+            for (int q = 0; q < DM_MAXH; q++) T[a].seq[q] = T[s].seq[q];
+        }
+    }
+    __syncthreads();
+    for (int d = 0; d < S.sh_depth; d++) {
+        const int m = S.sh_better[d];  // uniform
+        if (m >= 0)
+            for (int j = tid; j < IG_BEL; j += DM_THREADS) MK[m].best_obs[j] = S.bobs[j];
+    }
+    DMSTAMP(6);
+    // ---- _update_distribution (DecMCTS.py:162-180): top comm_n nodes by mu (first created first on ties),
+    //      those with a roll-out, q = mu^2 -------------------------------------------------------------------------
+    const int total = nn[0];
+    int mypick[DM_MAXCOMM];  // the rounds' winners (uniform: every thread derives them from the waves' candidates)
+    // Thread t owns the nodes 1 + t + k DM_THREADS.  Its best one is found ONCE (round 4: from the tree's compact value array -
+    // 8-byte stride, coalesced - instead of the 80-byte nodes); a round's winner is taken out of the race by its owner alone,
+    // which looks for its next best - every other thread's candidate stands.  (Before: every thread rescanned all its nodes
+    // against the list of winners in each of the comm_n rounds: 11 - 12 % of a grow once a tree holds ~1000 nodes.)
+    double bm = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = 1 + tid; i < total; i += DM_THREADS) {  // ascending i: the first maximum wins
+        const double m = MU[i];
+        if (m > bm) { bm = m; bi = i; }
+    }
+#pragma unroll
+    for (int round = 0; round < DM_MAXCOMM; round++) {  // (unrolled to its compile-time bound: mypick stays in registers)
+        if (round >= P.comm_n) break;
+        // arg-max over (mu desc, index asc): inside the wave by lane shuffles, across the waves through LDS - one barrier per round
+        double rm = bm;
+        int ri = bi;
+        for (int off = 32; off > 0; off >>= 1) {
+            const double m2 = __shfl_down(rm, off, 64);
+            const int i2 = __shfl_down(ri, off, 64);
+            if (m2 > rm || (m2 == rm && i2 < ri)) { rm = m2; ri = i2; }
+        }
+        double* wr = S.red + (round & 1) * DM_WAVES;
+        int* wi = S.redi + (round & 1) * DM_WAVES;
+        if (lane == 0) { wr[wave] = rm; wi[wave] = ri; }
+        __syncthreads();
+        double gm = wr[0];
+        int gi = wi[0];
+        for (int q = 1; q < DM_WAVES; q++)
+            if (wr[q] > gm || (wr[q] == gm && wi[q] < gi)) { gm = wr[q]; gi = wi[q]; }
+        mypick[round] = gi;
+        if (tid == 0) S.picks[round] = gi;
+        if (gi == bi && gi != 0x7fffffff) {  // my node won: my next best among the ones not picked yet
+            bm = -INFINITY;
+            bi = 0x7fffffff;
+            for (int i = 1 + tid; i < total; i += DM_THREADS) {
+                bool taken = false;
+#pragma unroll
+                for (int q = 0; q < DM_MAXCOMM; q++)
+                    if (q <= round) taken |= mypick[q] == i;
+                const double m = MU[i];
+                if (!taken && m > bm) { bm = m; bi = i; }
+            }
+        }
+    }
+    __syncthreads();
+    // those of the winners that have a roll-out, in rank order, with q = mu^2 / sum: lane q of wave 0 fetches winner q's fields
+    // (one round trip for all of them; lane 0 alone made up to fifteen dependent ones), the sum runs over the kept entries in order
+    if (wave == 0) {
+        const int pk = lane < P.comm_n ? S.picks[lane] : 0x7fffffff;
+        const bool ok = pk != 0x7fffffff && T[pk].has_roll;
+        const double mu = ok ? T[pk].mu : 0.0;
+        const unsigned long long km = __ballot(ok);
+        const int cnt = __popcll(km), pos = __popcll(km & ((1ull << lane) - 1ull));
+        const double sq = mu * mu;
+        double tot = 0.0;
+        for (int k = 0; k < DM_MAXCOMM; k++) {
+            const double v = __shfl(sq, k, 64);
+            if ((km >> k) & 1ull) tot += v;
+        }
+        if (ok) {  // (an empty list leaves the distribution as it was)
+            S.dist_idx[dr][pos] = pk;
+            S.dist_q[dr][pos] = tot == 0.0 ? 1.0 / cnt : sq / tot;
+        }
+        if (lane == 0) {
+            S.sh_n = cnt;
+            if (cnt > 0) S.dist_n[dr] = cnt;
+        }
+    }
+    __syncthreads();
+    DMSTAMP(7);
+    DMSTAMP_FLUSH();
+}
+
+// ---- send_comms: publish the robot's distribution (LDS row dr) into `out` (ig_mcts.py:107) ---------------------------------
+__device__ __forceinline__ void dm_publish(const DmNode* T, const DmMasks* MK, const DmLds& S, int dr, DmPublished& out, int tid) {
+    const int n = S.dist_n[dr];
+    for (int q = 0; q < n; q++) {
+        const DmNode& src = T[S.dist_idx[dr][q]];
+        // the root entry of a tree without roll-outs has no best roll-out: it stands for "stay", nothing observed
+        const DmMasks& srm = MK[src.mask];  // (distribution entries have a roll-out or are the root: their masks exist)
+        for (int j = tid; j < IG_BEL; j += DM_THREADS) out.obs[q][j] = src.has_roll ? srm.best_obs[j] : srm.observed[j];
+    }
+    if (tid == 0) {
+        out.n = n;
+        for (int q = 0; q < n; q++) out.q[q] = S.dist_q[dr][q];
+        const DmNode& b = T[S.dist_idx[dr][0]];
+        out.seq_len = b.has_roll ? b.seq_len : 0;
+        for (int a = 0; a < DM_MAXH; a++) out.seq0[a] = b.has_roll ? b.seq[a] : (uint8_t)DM_NOACT;
+    }
+    __syncthreads();
+}
+
+// ---- action = first action of the best path (ig_mcts.py:109) and the tree's statistics, for tree t = w R + r ---------------
+__device__ __forceinline__ void dm_output(const DmPublished& p, const DmNode* T, const int32_t* nn, size_t t, double* out_actions,
+                                          uint8_t* out_paths, double* out_stats) {
+    double v = 0.0, wv = 0.0;
+    if (p.seq_len > 0 && p.seq0[0] < 9) dm_prim(p.seq0[0], v, wv);
+    out_actions[t * 2] = v;
+    out_actions[t * 2 + 1] = wv;
+    for (int a = 0; a < DM_MAXH; a++) out_paths[t * DM_MAXH + a] = a < p.seq_len ? p.seq0[a] : (uint8_t)DM_NOACT;
+    out_stats[t * 3] = T[0].mu;
+    out_stats[t * 3 + 1] = T[0].Nv;
+    out_stats[t * 3 + 2] = (double)nn[0];
+}
+
 // Lanes per world (round 4).  A world's planning step is ONE serial chain of R x Ncycles x Ntree grows, each a chain of dependent
 // gathers through the L2-resident distance field (sphere traces): the kernel is latency-bound (VALU busy 44 %), a CU holds 16
 // waves at 128 VGPRs, and cfg5 gives a CU 8 worlds.  With 4 waves per world only 4 worlds ran at a time - two rounds of
 // workgroups - and the 10 roll-outs of a grow took 3 rounds of waves, the third half empty; with 2 waves per world all 8 run
 // at once and the roll-outs take exactly 5 rounds: one round of workgroups of ~1.5x the duration instead of two.
+// Sequential mode (parallelize_agents=False): one workgroup per world, robots in index order within a cycle.
 __global__ void __launch_bounds__(DM_THREADS, DM_WAVES_PER_SIMD) k_dmcts_plan(IgDev G, DmParams P, const double* poses, DmNode* nodes, DmMasks* masks, double* mu_all,
                                                          int32_t* n_nodes_all, DmPublished* pub_all, double* out_actions,
                                                          uint8_t* out_paths, double* out_stats) {
-    __shared__ unsigned long long vis[IG_BEL], excl[IG_BEL], bobs[IG_BEL];
-    __shared__ unsigned long long wvis[DM_WAVES][IG_BEL], wobs[DM_WAVES][IG_BEL], wbobs[DM_WAVES][IG_BEL];  // a wave's own masks
-    __shared__ uint16_t wlist[DM_WAVES][IG_BEL * IG_BEL / 4];  // cone cells of the wave's current visibility query (a 60-degree cone of 5 m holds < 100)
-    __shared__ uint8_t wtail[DM_WAVES][DM_MAXH], wbtail[DM_WAVES][DM_MAXH];
-    __shared__ double wbest[DM_WAVES];
-    __shared__ int wbest_sim[DM_WAVES];
-    __shared__ double red[DM_THREADS];
-    __shared__ int redi[DM_THREADS];
-    __shared__ double cpose[27];
-    __shared__ int cfeas[9];
-    __shared__ double rew[DM_MAXSIMS];
-    __shared__ uint8_t btail[DM_MAXH];
-    __shared__ int sh_sel, sh_pick, sh_n, sh_depth;
-    __shared__ int sh_path[DM_MAXH + 2], sh_better[DM_MAXH + 2];
-    __shared__ int picks[DM_MAXCOMM];
-    __shared__ int dist_idx[DM_MAXR][DM_MAXCOMM];
-    __shared__ double dist_q[DM_MAXR][DM_MAXCOMM];
-    __shared__ int dist_n[DM_MAXR];
-    const int w = blockIdx.x, tid = threadIdx.x, R = P.R, H = P.horizon;
-    const int wave = tid >> 6, lane = tid & 63;
+    __shared__ DmLds S;
+    const int w = blockIdx.x, tid = threadIdx.x, R = P.R;
     const uint32_t* d2 = G.d2 + (size_t)ig_scenario(G, w) * CAGYM_MAPD * CAGYM_MAPD;
     const double* belief = G.mi + (size_t)w * IG_BEL * IG_BEL;  // the MI cache of the world's belief (IgDev::mi)
     DmPublished* pub = pub_all + (size_t)w * R;
     const IgCone cone = ig_cone(P.fov);  // the cone test's two tangents, once for every visibility query of the planning step
 
-    // ---- Tree.__init__ (DecMCTS.py:92-138): root + expansion of the root; my_act_dist = the root state alone -----
     for (int r = 0; r < R; r++) {
-        DmNode* T = nodes + ((size_t)w * R + r) * P.node_cap;
-        DmMasks* MK = masks + ((size_t)w * R + r) * P.mask_cap;
-        double* MU = mu_all + ((size_t)w * R + r) * P.node_cap;  // the nodes' values once more, 8 bytes apart (the top-n scan's input)
-        int* nn = n_nodes_all + ((size_t)w * R + r) * 2;  // [0] nodes, [1] mask-pool entries
-        for (int j = tid; j < IG_BEL; j += DM_THREADS) { MK[0].observed[j] = 0ull; MK[0].best_obs[j] = 0ull; }
-        if (tid == 0) {
-            T[0].mu = 0.0; T[0].Nv = 0.0; T[0].best = 0.0;
-            T[0].pose[0] = poses[((size_t)w * R + r) * 3]; T[0].pose[1] = poses[((size_t)w * R + r) * 3 + 1];
-            T[0].pose[2] = poses[((size_t)w * R + r) * 3 + 2];
-            T[0].parent = -1; T[0].child0 = -1; T[0].mask = 0; T[0].nchild = 0; T[0].stage = 0; T[0].has_roll = 0; T[0].seq_len = 0;
-            for (int a = 0; a < DM_MAXH; a++) { T[0].acts[a] = DM_NOACT; T[0].seq[a] = DM_NOACT; }
-            MU[0] = 0.0;
-            nn[0] = 1; nn[1] = 1;
-            dist_n[r] = 1; dist_idx[r][0] = 0; dist_q[r][0] = 1.0;
-        }
-        __syncthreads();
-        dm_expand(d2, T, MU, nn, 0, P, cpose, cfeas, tid);
+        const size_t t = (size_t)w * R + r;
+        // MU: the nodes' values once more, 8 bytes apart (the top-n scan's input); nn: [0] nodes, [1] mask-pool entries
+        dm_init_tree(d2, P, poses + t * 3, nodes + t * P.node_cap, masks + t * P.mask_cap, mu_all + t * P.node_cap, n_nodes_all + t * 2, S, r, tid);
     }
 
     for (int cycle = 0; cycle < P.Ncycles; cycle++) {
         for (int r = 0; r < R; r++) {
-            DmNode* T = nodes + ((size_t)w * R + r) * P.node_cap;
-            DmMasks* MK = masks + ((size_t)w * R + r) * P.mask_cap;
-            double* MU = mu_all + ((size_t)w * R + r) * P.node_cap;
-            int* nn = n_nodes_all + ((size_t)w * R + r) * 2;
+            const size_t t = (size_t)w * R + r;
+            DmNode* T = nodes + t * P.node_cap;
+            DmMasks* MK = masks + t * P.mask_cap;
+            double* MU = mu_all + t * P.node_cap;
+            int* nn = n_nodes_all + t * 2;
             for (int g = 0; g < P.Ntree; g++) {
                 const unsigned int call = P.call_base + (unsigned int)((cycle * R + r) * P.Ntree + g) + 1u;
-                DMSTAMP_BEGIN();
-                DMSTAMP_COUNT();
-                // ---- _get_system_state (DecMCTS.py:182-194): one sampled plan per robot this one listens to -------
-                for (int j = tid; j < IG_BEL; j += DM_THREADS) excl[j] = 0ull;
-                __syncthreads();
-                for (int other = 0; other < R - 1; other++) {  // Q15 listening graph (see dmcts.py)
-                    if (other == r || pub[other].n <= 0) continue;  // uniform
-                    if (tid == 0) {
-                        const int n = pub[other].n;
-                        double tot = 0.0;
-                        for (int k = 0; k < n; k++) tot += pub[other].q[k];
-                        const double thr = dm_u01(P.seed ^ 0x5DEECE66Dull, (unsigned int)w, (call << 4) | (unsigned int)other) * tot;
-                        int pick = n - 1;
-                        double run = 0.0;
-                        for (int k = 0; k < n; k++) {
-                            run += pub[other].q[k];
-                            if (run > thr) { pick = k; break; }
-                        }
-                        sh_pick = pick;
-                    }
-                    __syncthreads();
-                    for (int j = tid; j < IG_BEL; j += DM_THREADS) excl[j] |= pub[other].obs[sh_pick][j];
-                    __syncthreads();
-                }
-                DMSTAMP(0);
-                // ---- selection (DecMCTS.py:14-18, 140-153, 288-289) --------------------------------------------------
-                // (the children of a node are scored side by side on the lanes of wave 0 - a logarithm, a division and a square root
-                //  each; lane 0 alone walked up to 4 levels x 9 children - and the first maximum in child order is taken, as `if u > best`)
-                if (wave == 0) {
-                    int node = 0, depth = 0;
-                    for (;;) {
-                        if (lane == 0) sh_path[depth] = node;  // the walk from the root: back-propagation climbs it without reloading parents
-                        const int nc = T[node].nchild;  // uniform
-                        if (nc <= 0) break;
-                        depth++;
-                        const double n_p = T[node].Nv;
-                        const int c0 = T[node].child0;
-                        double u = -INFINITY;
-                        int bi = lane;
-                        if (lane < nc) {
-                            const DmNode& ch = T[c0 + lane];
-                            if (ch.Nv == 0.0) u = INFINITY;
-                            else u = n_p > 0.0 ? ch.mu + 2 * P.c_p * sqrt(2 * log(n_p) / ch.Nv) : ch.mu;
-                        }
-                        for (int off = 8; off > 0; off >>= 1) {  // nc <= 9: lanes 0..15
-                            const double u2 = __shfl_down(u, off, 64);
-                            const int i2 = __shfl_down(bi, off, 64);
-                            if (u2 > u || (u2 == u && i2 < bi)) { u = u2; bi = i2; }
-                        }
-                        node = c0 + __shfl(bi, 0, 64);
-                    }
-                    if (lane == 0) { sh_sel = node; sh_depth = depth; }
-                }
-                __syncthreads();
-                const int s = sh_sel;
-                DMSTAMP(1);
-                dm_materialise(d2, T, MK, nn + 1, s, P, vis, tid, cone);
-                DMSTAMP(2);
-                dm_expand(d2, T, MU, nn, s, P, cpose, cfeas, tid);
-                DMSTAMP(3);
-                // ---- simulation (DecMCTS.py:233-271, 296-327): Nsims random roll-outs from the selected node, one wave each ----
-                const int steps = H - T[s].stage;
-                const unsigned long long rseed = P.seed * 1000003ull + (unsigned long long)call;
-                const DmMasks& sm = MK[T[s].mask];
-                {
-                    double my_best = -INFINITY;
-                    int my_best_sim = 0x7fffffff;
-                    for (int sim = wave; sim < P.Nsims; sim += DM_WAVES) {
-                        unsigned long long* obs = wobs[wave];
-                        if (lane < IG_BEL) obs[lane] = sm.observed[lane];
-                        dm_wave_sync();
-                        double x = T[s].pose[0], y = T[s].pose[1], th = T[s].pose[2];
-                        for (int t = 0; t < steps; t++) {
-                            const uint32_t k = ig_rand_primitive(rseed, (uint32_t)w, (uint32_t)sim, (uint32_t)t);
-                            double v, wv;
-                            dm_prim((int)k, v, wv);
-                            const bool ok = dm_next_pose_wave(d2, x, y, th, v, wv, P.xdt, P.dt, P.radius, lane);  // uniform across the wave
-                            DMSTAMP(8);
-                            if (ok) {
-                                dm_visible_wave(d2, x, y, th, P.fov, P.range, wvis[wave], wlist[wave], lane, cone);
-                                if (lane < IG_BEL) obs[lane] |= wvis[wave][lane];
-                                dm_wave_sync();
-                            }
-                            if (lane == 0) wtail[wave][t] = ok ? (uint8_t)k : (uint8_t)DM_INFEAS;
-                            DMSTAMP(9);
-                        }
-                        if (lane < IG_BEL) wvis[wave][lane] = obs[lane] & ~excl[lane];  // mcts_reward (ig_mcts.py:234-241)
-                        dm_wave_sync();
-                        const double rr = dm_reward_wave(belief, wvis[wave], lane);
-                        DMSTAMP(10);
-                        if (lane == 0) rew[sim] = rr;
-                        if (rr > my_best) {  // uniform across the wave; `if rew > best_reward` keeps the first maximum
-                            my_best = rr;
-                            my_best_sim = sim;
-                            if (lane < IG_BEL) wbobs[wave][lane] = obs[lane];
-                            if (lane < DM_MAXH) wbtail[wave][lane] = lane < steps ? wtail[wave][lane] : (uint8_t)DM_NOACT;
-                        }
-                        dm_wave_sync();
-                    }
-                    if (lane == 0) { wbest[wave] = my_best; wbest_sim[wave] = my_best_sim; }
-                }
-                DMSTAMP(4);
-                __syncthreads();
-                DMSTAMP(5);
-                // the first maximum in roll-out order: highest reward, lowest roll-out index among equals
-                int bw = 0;
-                for (int q = 1; q < DM_WAVES; q++)
-                    if (wbest[q] > wbest[bw] || (wbest[q] == wbest[bw] && wbest_sim[q] < wbest_sim[bw])) bw = q;
-                const double best = wbest[bw];
-                for (int j = tid; j < IG_BEL; j += DM_THREADS) bobs[j] = wbobs[bw][j];
-                if (tid < DM_MAXH) btail[tid] = wbtail[bw][tid];
-                __syncthreads();
-                // ---- back-propagation (DecMCTS.py:329-356) ----------------------------------------------------------------
-                for (int j = tid; j < IG_BEL; j += DM_THREADS) MK[T[s].mask].best_obs[j] = bobs[j];
-                if (tid == 0) {
-                    double acc = 0.0;
-                    for (int sim = 0; sim < P.Nsims; sim++) acc += rew[sim];
-                    const double avg = acc / P.Nsims;
-                    const int st = T[s].stage;
-                    T[s].mu = avg; T[s].best = best; T[s].Nv = 1.0; T[s].has_roll = 1;
-                    MU[s] = avg;
-                    T[s].seq_len = (uint8_t)H;
-                    for (int a = 0; a < DM_MAXH; a++) T[s].seq[a] = a < st ? T[s].acts[a] : (a < H ? btail[a - st] : (uint8_t)DM_NOACT);
-                    red[0] = avg;
-                }
-                __syncthreads();
-                const double avg = red[0];
-                // the selected node's ancestors (the walk T[a].parent, recorded at selection).  Each one's update reads and writes only its
-                // own statistics, so they are independent: thread d takes ancestor d (round 4; lane 0 climbed them one after the other with
-                // two barriers and a dependent round trip to the node pool per level)
-                if (tid < sh_depth) {
-                    const int a = sh_path[tid];
-                    const bool better = best > T[a].best;
-                    sh_better[tid] = better ? T[a].mask : -1;
-                    const double mu_new = (P.gamma * T[a].mu * T[a].Nv + avg) / (T[a].Nv + 1);
-                    T[a].mu = mu_new;
-                    MU[a] = mu_new;
-                    T[a].Nv = P.gamma * T[a].Nv + 1;
-                    if (better) {
-                        T[a].best = best;
-                        T[a].has_roll = 1;
-                        T[a].seq_len = T[s].seq_len;
-                        for (int q = 0; q < DM_MAXH; q++) T[a].seq[q] = T[s].seq[q];
-                    }
-                }
-                __syncthreads();
-                for (int d = 0; d < sh_depth; d++) {
-                    const int m = sh_better[d];  // uniform
-                    if (m >= 0)
-                        for (int j = tid; j < IG_BEL; j += DM_THREADS) MK[m].best_obs[j] = bobs[j];
-                }
-                DMSTAMP(6);
-                // ---- _update_distribution (DecMCTS.py:162-180): top comm_n nodes by mu (first created first on ties),
-                //      those with a roll-out, q = mu^2 -------------------------------------------------------------------------
-                const int total = nn[0];
-                int mypick[DM_MAXCOMM];  // the rounds' winners (uniform: every thread derives them from the waves' candidates)
-                // Thread t owns the nodes 1 + t + k DM_THREADS.  Its best one is found ONCE (round 4: from the tree's compact value array -
-                // 8-byte stride, coalesced - instead of the 80-byte nodes); a round's winner is taken out of the race by its owner alone,
-                // which looks for its next best - every other thread's candidate stands.  (Before: every thread rescanned all its nodes
-                // against the list of winners in each of the comm_n rounds: 11 - 12 % of a grow once a tree holds ~1000 nodes.)
-                double bm = -INFINITY;
-                int bi = 0x7fffffff;
-                for (int i = 1 + tid; i < total; i += DM_THREADS) {  // ascending i: the first maximum wins
-                    const double m = MU[i];
-                    if (m > bm) { bm = m; bi = i; }
-                }
-#pragma unroll
-                for (int round = 0; round < DM_MAXCOMM; round++) {  // (unrolled to its compile-time bound: mypick stays in registers)
-                    if (round >= P.comm_n) break;
-                    // arg-max over (mu desc, index asc): inside the wave by lane shuffles, across the waves through LDS - one barrier per round
-                    double rm = bm;
-                    int ri = bi;
-                    for (int off = 32; off > 0; off >>= 1) {
-                        const double m2 = __shfl_down(rm, off, 64);
-                        const int i2 = __shfl_down(ri, off, 64);
-                        if (m2 > rm || (m2 == rm && i2 < ri)) { rm = m2; ri = i2; }
-                    }
-                    double* wr = red + (round & 1) * DM_WAVES;
-                    int* wi = redi + (round & 1) * DM_WAVES;
-                    if (lane == 0) { wr[wave] = rm; wi[wave] = ri; }
-                    __syncthreads();
-                    double gm = wr[0];
-                    int gi = wi[0];
-                    for (int q = 1; q < DM_WAVES; q++)
-                        if (wr[q] > gm || (wr[q] == gm && wi[q] < gi)) { gm = wr[q]; gi = wi[q]; }
-                    mypick[round] = gi;
-                    if (tid == 0) picks[round] = gi;
-                    if (gi == bi && gi != 0x7fffffff) {  // my node won: my next best among the ones not picked yet
-                        bm = -INFINITY;
-                        bi = 0x7fffffff;
-                        for (int i = 1 + tid; i < total; i += DM_THREADS) {
-                            bool taken = false;
-#pragma unroll
-                            for (int q = 0; q < DM_MAXCOMM; q++)
-                                if (q <= round) taken |= mypick[q] == i;
-                            const double m = MU[i];
-                            if (!taken && m > bm) { bm = m; bi = i; }
-                        }
-                    }
-                }
-                __syncthreads();
-                // those of the winners that have a roll-out, in rank order, with q = mu^2 / sum: lane q of wave 0 fetches winner q's fields
-                // (one round trip for all of them; lane 0 alone made up to fifteen dependent ones), the sum runs over the kept entries in order
-                if (wave == 0) {
-                    const int pk = lane < P.comm_n ? picks[lane] : 0x7fffffff;
-                    const bool ok = pk != 0x7fffffff && T[pk].has_roll;
-                    const double mu = ok ? T[pk].mu : 0.0;
-                    const unsigned long long km = __ballot(ok);
-                    const int cnt = __popcll(km), pos = __popcll(km & ((1ull << lane) - 1ull));
-                    const double sq = mu * mu;
-                    double tot = 0.0;
-                    for (int k = 0; k < DM_MAXCOMM; k++) {
-                        const double v = __shfl(sq, k, 64);
-                        if ((km >> k) & 1ull) tot += v;
-                    }
-                    if (ok) {  // (an empty list leaves the distribution as it was)
-                        dist_idx[r][pos] = pk;
-                        dist_q[r][pos] = tot == 0.0 ? 1.0 / cnt : sq / tot;
-                    }
-                    if (lane == 0) {
-                        sh_n = cnt;
-                        if (cnt > 0) dist_n[r] = cnt;
-                    }
-                }
-                __syncthreads();
-                DMSTAMP(7);
-                DMSTAMP_FLUSH();
+                dm_grow(d2, belief, P, cone, T, MK, MU, nn, pub, w, r, r, call, S, tid);  // hears what the earlier robots just published
             }
-            // ---- send_comms: publish this robot's distribution (ig_mcts.py:107) ------------------------------------------
-            const int n = dist_n[r];
-            for (int q = 0; q < n; q++) {
-                const DmNode& src = T[dist_idx[r][q]];
-                // the root entry of a tree without roll-outs has no best roll-out: it stands for "stay", nothing observed
-                const DmMasks& srm = MK[src.mask];  // (distribution entries have a roll-out or are the root: their masks exist)
-                for (int j = tid; j < IG_BEL; j += DM_THREADS) pub[r].obs[q][j] = src.has_roll ? srm.best_obs[j] : srm.observed[j];
-            }
-            if (tid == 0) {
-                pub[r].n = n;
-                for (int q = 0; q < n; q++) pub[r].q[q] = dist_q[r][q];
-                const DmNode& b = T[dist_idx[r][0]];
-                pub[r].seq_len = b.has_roll ? b.seq_len : 0;
-                for (int a = 0; a < DM_MAXH; a++) pub[r].seq0[a] = b.has_roll ? b.seq[a] : (uint8_t)DM_NOACT;
-            }
-            __syncthreads();
+            dm_publish(T, MK, S, r, pub[r], tid);
         }
     }
-    // ---- action = first action of the best path (ig_mcts.py:109) --------------------------------------------------------
     if (tid < R) {
-        const int r = tid;
-        const DmPublished& p = pub[r];
-        double v = 0.0, wv = 0.0;
-        if (p.seq_len > 0 && p.seq0[0] < 9) dm_prim(p.seq0[0], v, wv);
-        out_actions[((size_t)w * R + r) * 2] = v;
-        out_actions[((size_t)w * R + r) * 2 + 1] = wv;
-        for (int a = 0; a < DM_MAXH; a++) out_paths[((size_t)w * R + r) * DM_MAXH + a] = a < p.seq_len ? p.seq0[a] : (uint8_t)DM_NOACT;
-        const DmNode* T = nodes + ((size_t)w * R + r) * P.node_cap;
-        out_stats[((size_t)w * R + r) * 3] = T[0].mu;
-        out_stats[((size_t)w * R + r) * 3 + 1] = T[0].Nv;
-        out_stats[((size_t)w * R + r) * 3 + 2] = (double)n_nodes_all[((size_t)w * R + r) * 2];
+        const size_t t = (size_t)w * R + tid;
+        dm_output(pub[tid], nodes + t * P.node_cap, n_nodes_all + t * 2, t, out_actions, out_paths, out_stats);
+    }
+}
+
+// Agent-parallel mode (parallelize_agents=True, collision_avoidance_env.py:342-379): the R robots of a cycle plan independently on
+// what was published before the cycle, so one workgroup per (world, robot) - block w R + r - and one launch per cycle.  The
+// launch of cycle c reads the publications of cycle c - 1 (the previous planning step's for c = 0) from pub_src and writes its
+// robot's to pub_dst: nothing is read that the launch writes, so the result does not depend on the order in which the
+// workgroups run, and no workgroup waits for another.  What the one-world kernel keeps in LDS across cycles lives in the
+// workspace: the trees (as there) and the robot's distribution (dist_all); the root is built by the launch of cycle 0.  The
+// launch of the last cycle writes the outputs.
+__global__ void __launch_bounds__(DM_THREADS, DM_WAVES_PER_SIMD) k_dmcts_plan_cycle(IgDev G, DmParams P, int cycle, const double* poses, DmNode* nodes,
+                                                               DmMasks* masks, double* mu_all, int32_t* n_nodes_all,
+                                                               const DmPublished* pub_src, DmPublished* pub_dst, DmDist* dist_all,
+                                                               double* out_actions, uint8_t* out_paths, double* out_stats) {
+    __shared__ DmLds S;
+    const int R = P.R, tid = threadIdx.x;
+    const int w = blockIdx.x / R, r = blockIdx.x - w * R;
+    const size_t t = blockIdx.x;  // = w R + r: the tree's index, as in k_dmcts_plan
+    const uint32_t* d2 = G.d2 + (size_t)ig_scenario(G, w) * CAGYM_MAPD * CAGYM_MAPD;
+    const double* belief = G.mi + (size_t)w * IG_BEL * IG_BEL;
+    const IgCone cone = ig_cone(P.fov);
+    DmNode* T = nodes + t * P.node_cap;
+    DmMasks* MK = masks + t * P.mask_cap;
+    double* MU = mu_all + t * P.node_cap;
+    int* nn = n_nodes_all + t * 2;
+    DmDist& dist = dist_all[t];
+
+    if (cycle == 0) {
+        dm_init_tree(d2, P, poses + t * 3, T, MK, MU, nn, S, 0, tid);
+    } else {
+        if (tid == 0) S.dist_n[0] = dist.n;
+        if (tid < DM_MAXCOMM) { S.dist_idx[0][tid] = dist.idx[tid]; S.dist_q[0][tid] = dist.q[tid]; }
+        __syncthreads();
+    }
+    for (int g = 0; g < P.Ntree; g++) {
+        const unsigned int call = P.call_base + (unsigned int)((cycle * R + r) * P.Ntree + g) + 1u;  // the keys of k_dmcts_plan
+        dm_grow(d2, belief, P, cone, T, MK, MU, nn, pub_src + (size_t)w * R, w, r, 0, call, S, tid);
+    }
+    dm_publish(T, MK, S, 0, pub_dst[t], tid);
+    if (cycle + 1 < P.Ncycles) {
+        if (tid == 0) dist.n = S.dist_n[0];
+        if (tid < DM_MAXCOMM) { dist.idx[tid] = S.dist_idx[0][tid]; dist.q[tid] = S.dist_q[0][tid]; }
+    } else if (tid == 0) {
+        dm_output(pub_dst[t], T, nn, t, out_actions, out_paths, out_stats);
     }
 }

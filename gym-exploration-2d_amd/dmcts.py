@@ -17,11 +17,18 @@ Reference behaviour restated (paths under gym_collision_avoidance/envs/policies/
                                distributions, grow Ntree times, publish; action = first action of the best path
   ig_mcts.py:234-241           mcts_reward = MI(own observed cells minus cells observed in the sampled plans of
                                the other robots) on the current belief
+  ig_mcts.py:53-77             set_param(..., parallelize_agents): the planning mode
+  collision_avoidance_env.py:342-379
+                               _take_action_dmcts: per cycle, robots in index order (sequential: robot k hears
+                               what robots j < k published in this cycle) or each robot in its own process on a
+                               copy of env.agents taken when the cycle starts (agent-parallel: every robot hears
+                               what was published before the cycle, i.e. in the previous cycle or planning step)
 Random numbers are counter-based (splitmix64 finaliser) for both the plan sampling and the roll-outs; the reference
 uses the global np.random stream, so only statistical agreement with it is possible.  This host
 planner is also the executable specification of the device tree (csrc/cagym_dmcts.h, cagym_dmcts_plan): same
 generator keys, same summation orders, same tie rules -- the two make identical decisions (tests/test_dmcts.py).
 """
+import ctypes
 import math
 
 import numpy as np
@@ -117,11 +124,15 @@ class DecMCTSPlanner(object):
         rollouts(pose0, observed0, exclude, world, n_steps, radius, nsims, seed)
               -> (rewards[Q,nsims], actions[Q,nsims,H] uint8, observed[Q,nsims,60] uint64)
     (gym-exploration-2d_amd.ig.InfoGainBackend on the GPU; tests use an adapter over the CPU oracle.)
+    parallelize_agents: the reference's agent-parallel mode (ig_mcts.set_param): in every cycle each robot hears the
+    plans published before the cycle started instead of those the robots before it published in this cycle.  The loop
+    order, the generator keys and self.calls are those of the sequential mode.
     """
 
     def __init__(self, backend, n_worlds, n_robots, radius=0.5, Ntree=30, Nsims=10, horizon=4, c_p=1.0, gamma=0.95,
-                 Ncycles=5, comm_n=5, seed=0):
+                 Ncycles=5, comm_n=5, seed=0, parallelize_agents=False):
         self.be, self.N, self.R = backend, int(n_worlds), int(n_robots)
+        self.parallelize_agents = bool(parallelize_agents)
         self.radius, self.Ntree, self.Nsims, self.horizon = float(radius), int(Ntree), int(Nsims), int(horizon)
         self.c_p, self.gamma, self.Ncycles, self.comm_n = float(c_p), float(gamma), int(Ncycles), int(comm_n)
         self.seed = int(seed)
@@ -213,11 +224,15 @@ class DecMCTSPlanner(object):
             self.published = [[None] * self.N for _ in range(self.R)]
         published = self.published
         for cycle in range(self.Ncycles):
-            for r in range(self.R):  # robots in index order; a robot sees what the earlier ones just published
+            # agent-parallel: every robot of the cycle hears the plans as they stood when the cycle started (the
+            # reference plans each robot on a pickled copy of env.agents); a publication replaces the list entry, so
+            # copying the outer lists is the snapshot.  Sequential: the live lists.
+            heard = [list(p) for p in published] if self.parallelize_agents else published
+            for r in range(self.R):  # robots in index order; sequential: a robot sees what the earlier ones just published
                 for w in range(self.N):
                     for other in range(self.R - 1):
-                        if other != r and published[other][w] is not None:
-                            trees[r][w].comms[other] = published[other][w]
+                        if other != r and heard[other][w] is not None:
+                            trees[r][w].comms[other] = heard[other][w]
                 for _ in range(self.Ntree):
                     self._grow_all(r, trees[r])
                 for w in range(self.N):
@@ -234,13 +249,22 @@ class DecMCTSPlanner(object):
         return actions, paths
 
 
+class DmctsParams(ctypes.Structure):
+    """cagym_dmcts_params (include/cagym.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_robots", "Ntree", "Nsims", "horizon", "Ncycles", "comm_n", "xdt", "reset_comms")] + \
+               [("call_base", ctypes.c_uint32), ("parallel_agents", ctypes.c_uint32)] + \
+               [(n, ctypes.c_double) for n in ("c_p", "gamma", "radius", "dt", "fov_rad", "range")] + [("seed", ctypes.c_uint64)]
+
+
 class DeviceDecMCTSPlanner(object):
     """Same planner with the trees on the device (cagym_dmcts_plan, csrc/cagym_dmcts.h): one workgroup per world grows
     the trees of all its robots; nothing but the poses goes in and the chosen actions come out.  Makes the same
-    decisions as DecMCTSPlanner(InfoGainBackend(ig), ...) for the same seed."""
+    decisions as DecMCTSPlanner(InfoGainBackend(ig), ...) for the same seed and mode.  parallelize_agents=True: the
+    agent-parallel mode (one workgroup per world and robot, one launch per cycle; the workspace holds a second publication
+    buffer)."""
 
     def __init__(self, ig, n_robots, radius=0.5, Ntree=30, Nsims=10, horizon=4, c_p=1.0, gamma=0.95, Ncycles=5, comm_n=5,
-                 seed=0):
+                 seed=0, parallelize_agents=False):
         import ctypes as C
         import torch
         from . import _lib
@@ -248,12 +272,10 @@ class DeviceDecMCTSPlanner(object):
         self.ig, self.b, self.L = ig, ig.b, ig.L
         self.N, self.R = ig.b.N, int(n_robots)
 
-        class Params(C.Structure):
-            _fields_ = [(n, C.c_int32) for n in ("n_robots", "Ntree", "Nsims", "horizon", "Ncycles", "comm_n", "xdt",
-                                                 "reset_comms")] + [("call_base", C.c_uint32), ("pad", C.c_uint32)] + \
-                       [(n, C.c_double) for n in ("c_p", "gamma", "radius", "dt", "fov_rad", "range")] + [("seed", C.c_uint64)]
-        self.P = Params(self.R, int(Ntree), int(Nsims), int(horizon), int(Ncycles), int(comm_n), ig.xdt, 1, 0, 0,
-                        float(c_p), float(gamma), float(radius), ig.dt, ig.fov, ig.range, int(seed) & _M64)
+        Params = DmctsParams  # (include/cagym.h)
+        self.P = Params(self.R, int(Ntree), int(Nsims), int(horizon), int(Ncycles), int(comm_n), ig.xdt, 1, 0,
+                        int(bool(parallelize_agents)), float(c_p), float(gamma), float(radius), ig.dt, ig.fov, ig.range,
+                        int(seed) & _M64)
         self.L.cagym_dmcts_workspace_bytes.restype = C.c_size_t
         self.L.cagym_dmcts_workspace_bytes.argtypes = [C.c_int, C.POINTER(Params)]
         self.L.cagym_dmcts_plan.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -269,6 +291,21 @@ class DeviceDecMCTSPlanner(object):
     def reset(self):
         """Forget the communicated plans at the next plan() (new episode)."""
         self.P.reset_comms = 1
+
+    @property
+    def parallelize_agents(self):
+        return bool(self.P.parallel_agents)
+
+    @parallelize_agents.setter
+    def parallelize_agents(self, on):
+        """Switch the mode for the next plan(); the communicated plans are kept.  The sequential workspace is the first
+        part of the agent-parallel one, so a workspace that grows keeps its contents."""
+        self.P.parallel_agents = int(bool(on))
+        nbytes = self.L.cagym_dmcts_workspace_bytes(self.N, self._C.byref(self.P))
+        if nbytes > self.workspace.numel():
+            ws = self._torch.zeros(nbytes, dtype=self._torch.uint8, device=self.workspace.device)
+            ws[:self.workspace.numel()].copy_(self.workspace)
+            self.workspace = ws
 
     def plan(self, poses):
         """poses [N, R, 3] (torch or numpy).  Returns device tensors (actions [N,R,2], paths [N,R,8] uint8, where

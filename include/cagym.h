@@ -305,10 +305,18 @@ int cagym_get_scenarios(void* env, cagym_scenario_ptrs* out);
  * episode start); call_base = number of tree grows requested by earlier calls with this seed (keys the random
  * streams).  Outputs DEVICE: actions [N,R,2] = (v, omega) of the first step of each robot's best path,
  * paths [N,R,8] primitive indices of that path (254 = infeasible draw, 255 = none), stats [N,R,3] = root mu,
- * root N, node count (may be NULL).  Limits: n_robots <= 8, horizon <= 8, Nsims <= 32, comm_n <= 8. */
+ * root N, node count (may be NULL).  Limits: n_robots <= 8, horizon <= 8, Nsims <= 32, comm_n <= 8.
+ * parallel_agents selects the mode of ig_mcts.set_param(..., parallelize_agents) (collision_avoidance_env.py:342-379):
+ * 0 sequential (within a cycle, robot k hears what robots j < k published in that cycle; one workgroup per world),
+ * 1 agent-parallel (every robot of a cycle hears the publications as they stood when the cycle started; one workgroup
+ * per world and robot, one launch per cycle); any other value is refused (CAGYM_E_INVALID).  Generator keys, call_base
+ * and everything else are the same in both modes.  Mode 1 needs the larger workspace cagym_dmcts_workspace_bytes()
+ * reports for it (a second publication buffer); mode 0's size is unchanged.  The published plans are kept in the same
+ * place in both modes, so the mode may change between calls on one workspace without reset_comms; reset_comms clears
+ * the publications of the mode of the call. */
 typedef struct cagym_dmcts_params {
     int32_t n_robots, Ntree, Nsims, horizon, Ncycles, comm_n, xdt, reset_comms;
-    uint32_t call_base, pad;
+    uint32_t call_base, parallel_agents;
     double c_p, gamma, radius, dt, fov_rad, range;
     uint64_t seed;
 } cagym_dmcts_params;

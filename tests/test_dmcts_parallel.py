@@ -1,0 +1,342 @@
+"""Dec-MCTS in the reference's agent-parallel mode (ig_mcts.set_param(..., parallelize_agents=True),
+collision_avoidance_env.py:342-379): every robot of a cycle hears the plans as they stood when the cycle started.
+CPU: the host planner's mode against its sequential mode and against the reference's own parallel loop
+(tests/golden/ig_dmcts_reference_parallel.npz); the C ABI.  GPU: the device planner (k_dmcts_plan_cycle) makes the host
+planner's decisions."""
+import ctypes
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from test_dmcts import OBST, OracleBackend, _ig_world
+
+dm = importlib.import_module("gym-exploration-2d_amd.dmcts")
+scen = importlib.import_module("gym-exploration-2d_amd.scenarios")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "ig_dmcts_reference_parallel.npz")
+
+
+def _poses(N, R, seed):
+    """R robots per world on a line through the free cross of IG_agent_crossing's map, with jitter."""
+    rng = np.random.default_rng(seed)
+    x = np.linspace(-12.0, 12.0, R) if R > 1 else np.zeros(1)
+    base = np.stack([x, np.zeros(R), np.zeros(R)], 1)
+    return np.stack([base + np.concatenate([rng.uniform(-0.8, 0.8, (R, 2)), rng.uniform(-3, 3, (R, 1))], 1) for _ in range(N)])
+
+
+def _host(N, R, parallel, **kw):
+    orc.build()
+    edf = _ig_world()
+    return dm.DecMCTSPlanner(OracleBackend([edf] * N, [np.ones((60, 60))] * N), N, R, parallelize_agents=parallel, **kw)
+
+
+def _same_tree(a, b):
+    return len(a.nodes) == len(b.nodes) and a.root.mu == b.root.mu and a.root.N == b.root.N and \
+        all(x.mu == y.mu and x.N == y.N for x, y in zip(a.nodes, b.nodes))
+
+
+def test_single_robot_modes_agree():
+    kw = dict(radius=0.5, Ntree=6, Nsims=3, horizon=4, Ncycles=3, seed=4)
+    seq, par = _host(2, 1, False, **kw), _host(2, 1, True, **kw)
+    poses = _poses(2, 1, 1)
+    for _ in range(2):
+        a_s, p_s = seq.plan(poses)
+        a_p, p_p = par.plan(poses)
+        assert np.array_equal(a_s, a_p) and p_s == p_p
+        assert all(_same_tree(seq.trees[0][w], par.trees[0][w]) for w in range(2))
+        poses = poses + np.array([0.3, 0.1, 0.2])
+    assert seq.calls == par.calls
+
+
+def test_one_cycle_robot0_agrees():
+    """Ncycles = 1: robot 0 hears only what was published before the planning step in both modes; robot 1 hears robot 0's
+    fresh plan in the sequential mode only."""
+    kw = dict(radius=0.5, Ntree=8, Nsims=3, horizon=4, Ncycles=1, seed=6)
+    seq, par = _host(3, 3, False, **kw), _host(3, 3, True, **kw)
+    poses = _poses(3, 3, 2)
+    a_s, p_s = seq.plan(poses)
+    a_p, p_p = par.plan(poses)
+    assert np.array_equal(a_s[:, 0], a_p[:, 0]) and [p[0] for p in p_s] == [p[0] for p in p_p]
+    assert all(_same_tree(seq.trees[0][w], par.trees[0][w]) for w in range(3))
+    assert seq.calls == par.calls == 3 * 8
+
+
+def test_default_budget_modes_differ():
+    """At the experiment's budget (Ntree 30, Nsims 10, Ncycles 5) the flag changes what some robot hears and decides."""
+    seq, par = _host(2, 3, False), _host(2, 3, True)
+    poses = _poses(2, 3, 3)
+    _, p_s = seq.plan(poses)
+    _, p_p = par.plan(poses)
+    assert seq.calls == par.calls
+    assert p_s != p_p or any(not _same_tree(seq.trees[r][w], par.trees[r][w]) for r in range(3) for w in range(2))
+
+
+def _run_pipeline_parallel(seed, n_steps, edf):
+    """test_dmcts._run_pipeline with the agent-parallel planner: IG_agent_crossing on the CPU oracle env, belief update, team
+    MI reward, planning, motion (experiments/src/dmcts.py:50-95)."""
+    M = 10
+    a6 = np.zeros((M, 6))
+    a6[:, 4], a6[:, 5], a6[:, 0] = 1.0, 0.1, 1e3 + np.arange(M)
+    a6[0], a6[1], a6[2] = [-5, 0, 16, 0, 1, .5], [0, 0, 16, 0, 1, .5], [5, 0, 16, 0, 1, .5]
+    a6[3], a6[4] = [6, 12, 0, 0, 1, .2], [-6, -12, 0, 0, 1, .2]
+    pol = np.zeros(M, dtype=np.int32)
+    pol[:3] = scen.POLICY_IGMCTS
+    env = orc.OracleEnv(N=1, M=M, max_obstacles=4, game_over_mode=orc.GO_AGENT0)
+    env.set_scenario(a6[None], pol[None], scen.DYN_FIRSTORDER, heading0=np.zeros((1, M)), n_agents=[5],
+                     obstacles=np.array(OBST, dtype=np.float64)[None], n_obst=[4])
+    env.reset()
+    belief = np.ones((60, 60))
+    planner = dm.DecMCTSPlanner(OracleBackend([edf], [belief]), 1, 3, radius=0.5, Ntree=5, Nsims=3, horizon=4, c_p=1.0,
+                                gamma=0.95, Ncycles=2, seed=seed, parallelize_agents=True)
+    cum = [0.0]
+    for t in range(n_steps):
+        poses = np.concatenate([env.f("pos")[0, :3], env.f("heading")[0, :3, None]], axis=1)
+        obs = orc.update_belief(belief, edf, poses, np.zeros((3, 1, 2)), np.zeros(3, dtype=np.int32))
+        cum.append(cum[-1] + orc.mi_reward(belief, obs))
+        actions, _ = planner.plan(poses[None])
+        ext = np.zeros((1, M, 2))
+        ext[0, :3] = actions[0]
+        env.step(ext)
+    return np.array(cum)
+
+
+def test_statistics_match_reference_parallel_loop():
+    orc.build()
+    ref = np.load(FIXTURE)
+    rc = ref["cum_reward"]  # [seeds, steps + 1]
+    assert ref["team_reward"].shape == (rc.shape[0], rc.shape[1] - 1, 3)
+    # every robot's belief update saw the same cells (no target is detected in this scenario): one belief per world holds
+    assert np.abs(ref["team_reward"] - ref["team_reward"][..., :1]).max() < 1e-12
+    edf = _ig_world()
+    mine = np.array([_run_pipeline_parallel(s, rc.shape[1] - 1, edf) for s in range(8)])
+    assert np.abs(mine[:, 1] - rc[:, 1].mean()).max() < 1e-9 and np.ptp(rc[:, 1]) < 1e-9  # step 1: planner-independent
+    spread = 3 * np.sqrt(rc[:, -1].var() / len(rc) + mine[:, -1].var() / len(mine))
+    assert abs(mine[:, -1].mean() - rc[:, -1].mean()) < spread, (mine[:, -1], rc[:, -1])
+    assert (np.diff(mine, axis=1) > 0).all()
+
+
+def _c_compiler():
+    for c in ("cc", "gcc", "clang", os.environ.get("HIPCC", "hipcc")):  # (hipcc: the compiler the build itself needs)
+        if shutil.which(c):
+            return c
+    raise RuntimeError("no C compiler")
+
+
+def test_params_abi(tmp_path):
+    """cagym_dmcts_params keeps its size and layout; parallel_agents sits where the padding word was."""
+    src = tmp_path / "abi.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cagym.h"\n'
+                   'int main(void) { printf("%d %d %d %d %d\\n", (int)sizeof(cagym_dmcts_params), '
+                   '(int)offsetof(cagym_dmcts_params, call_base), (int)offsetof(cagym_dmcts_params, parallel_agents), '
+                   '(int)offsetof(cagym_dmcts_params, c_p), (int)offsetof(cagym_dmcts_params, seed)); return 0; }\n')
+    exe = tmp_path / "abi"
+    subprocess.run([_c_compiler(), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [96, 32, 36, 40, 88]
+    P = dm.DmctsParams
+    assert [ctypes.sizeof(P), P.call_base.offset, P.parallel_agents.offset, P.c_p.offset, P.seed.offset] == got
+
+
+def test_workspace_bytes_by_mode():
+    """Mode 0's workspace is what it always was; mode 1 adds a second publication buffer and the distributions."""
+    b = importlib.import_module("gym-exploration-2d_amd.build")
+    b.build()
+    L = importlib.import_module("gym-exploration-2d_amd._lib").load()
+    L.cagym_dmcts_workspace_bytes.restype = ctypes.c_size_t
+    L.cagym_dmcts_workspace_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(dm.DmctsParams)]
+    P = dm.DmctsParams(3, 30, 10, 4, 5, 5, 5, 1, 0, 0, 1.0, 0.95, 0.5, 0.1, 0.5, 5.0, 0)
+    N, trees = 16, 48
+    al = lambda x: (x + 255) // 256 * 256
+    node_cap, mask_cap, pub = 1 + 9 * (30 * 5 + 1), 1 + 30 * 5, 3920  # DmNode 80 B, DmMasks 960 B, DmPublished 3920 B
+    seq = al(trees * pub) + al(trees * 8) + al(trees * node_cap * 80) + al(trees * mask_cap * 960) + trees * node_cap * 8
+    assert L.cagym_dmcts_workspace_bytes(N, ctypes.byref(P)) == seq
+    P.parallel_agents = 1
+    assert L.cagym_dmcts_workspace_bytes(N, ctypes.byref(P)) == al(seq) + al(trees * pub) + trees * 104  # DmDist 104 B
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------
+def _gpu_env(N, M=4):
+    B = importlib.import_module("gym-exploration-2d_amd.batched_env").BatchedCollisionAvoidanceEnv
+    igm = importlib.import_module("gym-exploration-2d_amd.ig")
+    env = B(N, M, max_obstacles=4, game_over_mode="all")
+    env.set_scenarios(scen.random_worlds_fast(N, M, seed=2), scen.POLICY_STATIC, scen.DYN_FIRSTORDER,
+                      obstacles=np.tile(np.array(OBST, dtype=np.float64)[None], (N, 1, 1)), n_obst=[4] * N)
+    env.reset()
+    return env, igm.InfoGain(env), igm
+
+
+def _compare(host, dev, ph, ad, ah, N, R, tag):
+    import torch
+    torch.cuda.synchronize()
+    pd, st = dev.paths.cpu().numpy(), dev.stats.cpu().numpy()
+    for w in range(N):
+        for r in range(R):
+            seq = [254 if a < 0 else a for a in ph[w][r]]
+            assert list(pd[w, r, :len(seq)]) == seq and (pd[w, r, len(seq):] == 255).all(), (tag, w, r, seq, pd[w, r])
+            t = host.trees[r][w]
+            assert int(st[w, r, 2]) == len(t.nodes), (tag, w, r)
+            assert abs(st[w, r, 0] - t.root.mu) <= 1e-12 * max(1.0, abs(t.root.mu)) and abs(st[w, r, 1] - t.root.N) < 1e-12
+    assert np.array_equal(ad.cpu().numpy(), ah), tag
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("R", [1, 3, 8])
+@pytest.mark.parametrize("budget", [dict(Ntree=8, Nsims=5, Ncycles=3), dict(Ntree=30, Nsims=10, Ncycles=5)])
+def test_device_tree_decides_like_the_host_tree_parallel(budget, R):
+    """k_dmcts_plan_cycle against DecMCTSPlanner(parallelize_agents=True) on the same device primitives: identical best paths,
+    actions, root statistics and node counts over two consecutive planning steps."""
+    N = 4
+    env, ig, igm = _gpu_env(N)
+    poses = _poses(N, R, 5)
+    kw = dict(radius=0.5, horizon=4, c_p=1.0, gamma=0.95, seed=21, parallelize_agents=True, **budget)
+    host = dm.DecMCTSPlanner(igm.InfoGainBackend(ig), N, R, **kw)
+    dev = dm.DeviceDecMCTSPlanner(ig, R, **kw)
+    for step in range(2):
+        ah, ph = host.plan(poses)
+        ad, _ = dev.plan(poses)
+        _compare(host, dev, ph, ad, ah, N, R, step)
+        poses = poses + np.array([0.3, 0.1, 0.2])
+    assert host.calls == dev.calls
+    env.close()
+
+
+@pytest.mark.gpu
+def test_device_parallel_runs_are_bitwise_equal():
+    import torch
+    N, R = 8, 3
+    env, ig, _ = _gpu_env(N)
+    poses = _poses(N, R, 7)
+    out = []
+    for _ in range(2):
+        dev = dm.DeviceDecMCTSPlanner(ig, R, Ntree=12, Nsims=6, Ncycles=3, seed=9, parallelize_agents=True)
+        rec = []
+        for step in range(2):
+            a, p = dev.plan(poses + 0.2 * step)
+            torch.cuda.synchronize()
+            rec += [a.cpu().numpy().tobytes(), p.cpu().numpy().tobytes(), dev.stats.cpu().numpy().tobytes()]
+        out.append(rec)
+    assert out[0] == out[1]
+    env.close()
+
+
+@pytest.mark.gpu
+def test_parallel_agents_value_refused():
+    """parallel_agents = 2 is refused with CAGYM_E_INVALID; the handle and the planner stay usable."""
+    import torch
+    N, R = 4, 3
+    env, ig, _ = _gpu_env(N)
+    dev = dm.DeviceDecMCTSPlanner(ig, R, Ntree=4, Nsims=3, Ncycles=2, seed=1, parallelize_agents=True)
+    p = torch.as_tensor(_poses(N, R, 1), device=env.device).contiguous()
+    dev.P.parallel_agents = 2
+    with torch.cuda.device(env.device):
+        rc = dev.L.cagym_dmcts_plan(dev.b.h, ctypes.byref(dev.P), p.data_ptr(), dev.workspace.data_ptr(), dev.workspace.numel(),
+                                    dev.actions.data_ptr(), dev.paths.data_ptr(), dev.stats.data_ptr(), dev.b._stream())
+    assert rc == -1  # CAGYM_E_INVALID
+    assert b"parallel_agents" in dev.L.cagym_last_error(dev.b.h)
+    dev.P.parallel_agents = 1
+    a, _ = dev.plan(p)
+    torch.cuda.synchronize()
+    fresh = dm.DeviceDecMCTSPlanner(ig, R, Ntree=4, Nsims=3, Ncycles=2, seed=1, parallelize_agents=True)
+    b, _ = fresh.plan(p)
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and torch.equal(dev.stats, fresh.stats)
+    env.step()  # the environment handle still steps
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Ncycles", [2, 3])
+def test_alternating_modes_reproduce_fresh_planners(Ncycles):
+    """One planner switched between the modes with reset() in between gives what fresh planners of each mode give (from the
+    same call counter).  An odd number of cycles starts the parallel mode from a copy of the publications, an even one not."""
+    import torch
+    N, R = 6, 3
+    env, ig, _ = _gpu_env(N)
+    kw = dict(Ntree=6, Nsims=4, seed=13, Ncycles=Ncycles)
+    poses = _poses(N, R, 11)
+    one = dm.DeviceDecMCTSPlanner(ig, R, **kw)
+    for k, par in enumerate([False, True, False, True]):
+        one.parallelize_agents = par
+        if k:
+            one.reset()
+        fresh = dm.DeviceDecMCTSPlanner(ig, R, parallelize_agents=par, **kw)
+        fresh.calls = one.calls
+        for step in range(2):
+            a1, p1 = one.plan(poses + 0.25 * step)
+            a2, p2 = fresh.plan(poses + 0.25 * step)
+            torch.cuda.synchronize()
+            assert torch.equal(a1, a2) and torch.equal(p1, p2) and torch.equal(one.stats, fresh.stats), (k, step)
+    env.close()
+
+
+@pytest.mark.gpu
+def test_mode_change_keeps_publications():
+    """Without reset(), a planning step in one mode hears what the previous step published in the other mode, as the host
+    planner does."""
+    N, R = 4, 3
+    env, ig, igm = _gpu_env(N)
+    kw = dict(radius=0.5, horizon=4, c_p=1.0, gamma=0.95, seed=5, Ntree=6, Nsims=4, Ncycles=3)
+    host = dm.DecMCTSPlanner(igm.InfoGainBackend(ig), N, R, **kw)
+    dev = dm.DeviceDecMCTSPlanner(ig, R, **kw)
+    poses = _poses(N, R, 13)
+    for step, par in enumerate([False, True, False, True]):
+        host.parallelize_agents = par
+        dev.parallelize_agents = par
+        ah, ph = host.plan(poses)
+        ad, _ = dev.plan(poses)
+        _compare(host, dev, ph, ad, ah, N, R, step)
+        poses = poses + np.array([0.3, 0.1, 0.2])
+    env.close()
+
+
+@pytest.mark.gpu
+def test_cfg5_pipeline_parallel_matches_the_reference_statistics():
+    """test_dmcts.test_cfg5_pipeline_on_device_matches_the_reference_statistics in the agent-parallel mode, against the
+    reference's own parallel loop."""
+    import torch
+    B = importlib.import_module("gym-exploration-2d_amd.batched_env").BatchedCollisionAvoidanceEnv
+    igm = importlib.import_module("gym-exploration-2d_amd.ig")
+    rc = np.load(FIXTURE)["cum_reward"]
+    N, M, T = 24, 10, rc.shape[1] - 1
+    a6 = np.zeros((M, 6))
+    a6[:, 4], a6[:, 5], a6[:, 0] = 1.0, 0.1, 1e3 + np.arange(M)
+    a6[0], a6[1], a6[2] = [-5, 0, 16, 0, 1, .5], [0, 0, 16, 0, 1, .5], [5, 0, 16, 0, 1, .5]
+    a6[3], a6[4] = [6, 12, 0, 0, 1, .2], [-6, -12, 0, 0, 1, .2]
+    pol = np.zeros(M, dtype=np.int32)
+    pol[:3] = scen.POLICY_IGMCTS
+    env = B(N, M, max_obstacles=4, game_over_mode="agent0")
+    env.set_scenarios(np.tile(a6[None], (N, 1, 1)), np.tile(pol[None], (N, 1)), scen.DYN_FIRSTORDER,
+                      heading0=np.zeros((N, M)), n_agents=[5] * N,
+                      obstacles=np.tile(np.array(OBST, dtype=np.float64)[None], (N, 1, 1)), n_obst=[4] * N)
+    env.reset()
+    ig = igm.InfoGain(env)
+    planner = dm.DeviceDecMCTSPlanner(ig, 3, radius=0.5, Ntree=5, Nsims=3, horizon=4, c_p=1.0, gamma=0.95, Ncycles=2, seed=3,
+                                      parallelize_agents=True)
+    world = torch.arange(N, dtype=torch.int32, device=env.device)
+    det = torch.zeros((N, 3, 1, 2), dtype=torch.float64, device=env.device)
+    nd = torch.zeros((N, 3), dtype=torch.int32, device=env.device)
+    cum = torch.zeros(N, dtype=torch.float64, device=env.device)
+    first = None
+    ext = torch.zeros((N, M, 2), dtype=torch.float32, device=env.device)
+    for t in range(T):
+        st = env.state()
+        poses = torch.stack([st["pos_x"][:, :3], st["pos_y"][:, :3], st["heading"][:, :3]], dim=2)
+        obs = ig.update_belief(poses, det, nd)
+        cum = cum + ig.mi_reward(obs, world)
+        if t == 0:
+            first = cum.clone()
+        actions, _ = planner.plan(poses)
+        ext[:, :3] = actions.float()
+        env.step(ext)
+    torch.cuda.synchronize()
+    cum, first = cum.cpu().numpy(), first.cpu().numpy()
+    assert np.abs(first - rc[:, 1].mean()).max() < 1e-9
+    spread = 3 * np.sqrt(rc[:, -1].var() / len(rc) + cum.var() / N)
+    assert abs(cum.mean() - rc[:, -1].mean()) < spread, (cum, rc[:, -1])
+    assert cum.std() > 0.05
+    env.close()
