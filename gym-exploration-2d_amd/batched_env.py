@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import scenarios as sc
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> hipStream_t as an int
 
@@ -59,6 +60,13 @@ class BatchedCollisionAvoidanceEnv(object):
         self._out = self._outputs(self.obs_oas, self.obs_ego, self.obs_laser, self.reward, self.flags, self.game_over)
         self._state = None
         self._side = None  # side stream of step_overlapped (created on first use)
+        # policies the env drives itself inside step() (attach_ga3c / attach_ig_mcts) and what the pool holds
+        self._ga3c = None
+        self._igm = None
+        self._act = None          # [N, M, 2] f32 action table of an internal step (the caller's buffer is only read)
+        self._pool_policies = set()
+        self._n_ig = None         # IG robots per scenario (-1: the scenarios differ; None: a generated pool)
+        self.team_reward = None   # [N] f64: the team's MI reward of the last step with ig_mcts attached (policy.team_reward)
 
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
@@ -106,6 +114,14 @@ class BatchedCollisionAvoidanceEnv(object):
             rc = self.L.cagym_set_scenarios(self.h, p(a6), p(h0), p(pol), p(dyn), p(na), p(co), p(ob), p(no),
                                             self._stream())
         _lib.check(self.L, self.h, rc, "cagym_set_scenarios")
+        live = np.arange(M)[None, :] < (na if na is not None else np.full(S, M))[:, None]
+        self._pool_policies = set(np.unique(pol[live]).tolist())
+        counts = ((pol == sc.POLICY_IGMCTS) & live).sum(axis=1)
+        self._n_ig = int(counts[0]) if (counts == counts[0]).all() else -1
+        if self._igm is not None and self._n_ig != self._igm.R:  # the attached planner was sized for another team
+            self.detach_ig_mcts()
+        if self._igm is not None:  # new rasters: their distance fields and fresh beliefs (cagym_ig_init)
+            _lib.check(self.L, self.h, self.L.cagym_ig_init(self.h, self._stream()), "cagym_ig_init")
 
     def sense_occupancy_grid(self, out=None):
         """'local_grid' observation of every agent (OccupancyGridSensor.sense): uint8 [N, M, 60, 60], 1 = occupied.
@@ -135,6 +151,9 @@ class BatchedCollisionAvoidanceEnv(object):
         with torch.cuda.device(self.device):
             rc = self.L.cagym_generate_scenarios(self.h, C.byref(P), C.byref(nf) if check else None, self._stream())
         _lib.check(self.L, self.h, rc, "cagym_generate_scenarios")
+        self._pool_policies = {int(ego_policy), int(other_policies[0]), int(other_policies[1])}
+        self._n_ig = None
+        self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
         return int(nf.value) if check else None
 
     def scenarios(self):
@@ -161,14 +180,92 @@ class BatchedCollisionAvoidanceEnv(object):
             rc = self.L.cagym_reset(self.h, None if m is None else m.data_ptr(), int(bool(advance_episode)),
                                     C.byref(self._out), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_reset")
+        if self._igm is not None:  # a new episode: prior beliefs (of the masked worlds) and no communicated plans (of any world)
+            self._igm.ig.reset_belief(m)
+            self._igm.planner.reset()
         return self._obs()
+
+    # ---- policies driven inside step(): GA3C-CADRL (collision_avoidance_env.py:287-340) and ig_mcts (:342-379) ------------------
+    def attach_ga3c(self, checkpoint="iros18", max_observed=None):
+        """From now on step() and rollout() compute the action of every active GA3C agent themselves
+        (GA3CCADRLPolicy.find_next_action): one cagym_ga3c_act_merge launch writes the whole action table - the network's action
+        for the GA3C agents, the caller's rows for every other slot - into a buffer of the env, and the step reads that.  The env
+        keeps the policy (and its weight blob, which the handle caches by address) for as long as it is attached."""
+        from .ga3c import GA3CCADRLPolicy
+        self._ga3c = GA3CCADRLPolicy(self, checkpoint=checkpoint, max_observed=max_observed)
+        self._alloc_act()
+        return self._ga3c
+
+    def attach_ig_mcts(self, detect_fov=60.0, detect_range=5.0, xdt=5, Ntree=30, Nsims=10, mcts_cp=1.0, mcts_horizon=4,
+                       mcts_gamma=0.95, Ncycles=5, parallelize_agents=False, radius=0.5, seed=0):
+        """From now on step() plans the (v, omega) of every IG robot itself (ig_mcts.set_param + find_next_action, the Dec-MCTS
+        cycles of collision_avoidance_env.py:342-379): robot poses and detections (cagym_ig_robot_inputs), belief update, the
+        team's MI reward into self.team_reward, Dec-MCTS plan (seeded counter-based streams), the robots' rows of the action
+        table (cagym_ig_robot_actions), then the step.  One belief per world, shared by its robots.  Every scenario of the pool
+        must hold the same number of IG robots.  Not available under auto-reset or in rollout()."""
+        from .ig import InfoGain
+        from .dmcts import DeviceDecMCTSPlanner
+        R = self._n_ig if self._n_ig is not None else 0
+        self._igm = None
+        ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
+        N, K, dev = self.N, self.K, self.device
+        g = type("IgState", (), {})()
+        g.ig, g.R, g.range = ig, R, float(detect_range)
+        g.poses = torch.zeros((N, max(R, 1), 3), dtype=torch.float64, device=dev)
+        g.det = torch.zeros((N, max(R, 1), K, 2), dtype=torch.float64, device=dev)
+        g.n_det = torch.zeros((N, max(R, 1)), dtype=torch.int32, device=dev)
+        g.world = torch.arange(N, dtype=torch.int32, device=dev)
+        ig.robot_inputs(R, g.range, self.obs_oas, g.poses, g.det, g.n_det)  # refuses a pool without R robots in every scenario
+        g.planner = DeviceDecMCTSPlanner(ig, R, radius=radius, Ntree=Ntree, Nsims=Nsims, horizon=mcts_horizon, c_p=mcts_cp,
+                                         gamma=mcts_gamma, Ncycles=Ncycles, seed=seed, parallelize_agents=parallelize_agents)
+        self._igm = g
+        self._alloc_act()
+        return g.planner
+
+    def detach_ig_mcts(self):
+        self._igm = None
+        self.team_reward = None
+
+    def _alloc_act(self):
+        if self._act is None:
+            self._act = torch.zeros((self.N, self.M, 2), dtype=torch.float32, device=self.device)
+
+    def _drives_ga3c(self):
+        return self._ga3c is not None and sc.POLICY_GA3C in self._pool_policies
+
+    def _internal_actions(self, a):
+        """The action table the step reads: the caller's `a` (or None) when nothing is attached, else the env's own buffer."""
+        ga3c = self._drives_ga3c()
+        if not ga3c and self._igm is None:
+            return a
+        table = self._act
+        if ga3c:
+            self._ga3c.act_merge(a, table)
+        elif a is None:
+            table.zero_()
+        else:
+            table.copy_(a)
+        if self._igm is not None:
+            g = self._igm
+            g.ig.robot_inputs(g.R, g.range, self.obs_oas, g.poses, g.det, g.n_det)
+            observed = g.ig.update_belief(g.poses, g.det, g.n_det)
+            self.team_reward = g.ig.mi_reward(observed, g.world)  # before the move, as the reference computes it
+            planned, _ = g.planner.plan(g.poses)
+            g.ig.robot_actions(g.R, planned, table)
+        return table
 
     def step(self, actions=None, auto_reset=False):
         """One env.step() of every world.  auto_reset=True: finished worlds restart inside the same launch
-        (VecEnv semantics: the returned observation is the first one of the new episode)."""
+        (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
+        (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
+        itself is only read."""
+        if auto_reset and self._igm is not None:
+            raise RuntimeError("step(auto_reset=True) with ig_mcts attached: the planner's per-world restart (beliefs, "
+                               "communicated plans) is not implemented; step without auto-reset and reset() yourself")
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
+        a = self._internal_actions(a)
         fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
         rc = fn(self.h, None if a is None else a.data_ptr(), C.byref(self._out), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_step")
@@ -179,12 +276,20 @@ class BatchedCollisionAvoidanceEnv(object):
         """First half of step(): the internal RVO policies' half-planes and linear programs on the current state (they do not
         depend on the external actions: env.py:287-340 gathers every agent's action before any agent moves).  `stream`: a
         torch.cuda.Stream to run it on BESIDE the producer of the external actions (default: the current stream); the caller
-        orders step_finish behind it (step_overlapped does)."""
+        orders step_finish behind it (step_overlapped does).  Refused while a policy is attached (see step_finish)."""
+        self._refuse_split()
         raw = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         _lib.check(self.L, self.h, self.L.cagym_step_begin(self.h, raw), "cagym_step_begin")
 
+    def _refuse_split(self):
+        if self._drives_ga3c() or self._igm is not None:
+            raise RuntimeError("the split step (step_begin / step_finish / step_overlapped) takes every action from the caller: "
+                               "use step() while a policy is attached (attach_ga3c / attach_ig_mcts)")
+
     def step_finish(self, actions=None, auto_reset=False):
-        """Second half of step(): everything else, with every agent's action in hand.  Same results as step(), bit for bit."""
+        """Second half of step(): everything else, with every agent's action in hand.  Same results as step(), bit for bit.
+        Takes every action from the caller: refused while attach_ga3c / attach_ig_mcts drive agents inside step()."""
+        self._refuse_split()
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
@@ -198,6 +303,7 @@ class BatchedCollisionAvoidanceEnv(object):
         Worth it when the policy leaves the GPU idle (a host-side or remote policy).  NOT for cagym_ga3c_act on the same GPU:
         measured on MI355X (profiles/r4/cfg4_overlap_trace_*.txt) the two kernels do run side by side, but sharing the CUs halves
         each one's occupancy and both take twice as long - 0.251 ms per cfg4 step against 0.194 ms for the fused launch."""
+        self._refuse_split()
         main = torch.cuda.current_stream(self.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -220,9 +326,22 @@ class BatchedCollisionAvoidanceEnv(object):
         return buf
 
     def rollout(self, n_steps, auto_reset=True, out=None):
-        """n_steps env steps in one launch (all agents internally driven); returns [T, ...] buffers."""
+        """n_steps env steps in one launch (all agents internally driven); returns [T, ...] buffers.  With GA3C attached and
+        GA3C agents in the pool: T x (cagym_ga3c_act_merge, step), each step writing slice t of the buffers - no host
+        synchronisation, so the chain can be captured in a graph."""
+        if self._igm is not None:
+            raise RuntimeError("rollout() with ig_mcts attached is not implemented (the planner needs per-world restarts)")
         if out is None:
             out = self.alloc_rollout(n_steps)
+        if self._drives_ga3c():
+            fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
+            keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
+            for t in range(int(n_steps)):
+                self._ga3c.act_merge(None, self._act)
+                o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in keys])
+                rc = fn(self.h, self._act.data_ptr(), C.byref(o), self._stream())
+                _lib.check(self.L, self.h, rc, "cagym_step")
+            return out
         o = self._outputs(out.get("other_agents_states"), out.get("ego"), out.get("laserscan"), out.get("reward"),
                           out.get("flags"), out.get("game_over"))
         # (no torch.cuda.device context here and in step(): the library switches to the handle's device itself - DEVGUARD)

@@ -49,7 +49,10 @@ struct Env {
     size_t pre_lds_min = 0;  // CAGYM_PRE_LDS (bytes, read at creation): the PRE half asks for at least this much LDS per workgroup - a cap on how
                              // many of its workgroups share a CU with the caller's policy kernel (tools/cfg4_overlap.py)
     bool begun = false;  // cagym_step_begin was enqueued and no cagym_step_finish has consumed its velocities yet
+    int n_ig = 0;        // IG robots (active CAGYM_POL_IGMCTS slots) of every scenario of the pool; N_IG_UNEQUAL when the scenarios
+                         // differ, N_IG_RANDOM when cagym_generate_scenarios may have drawn some (cagym_ig_robot_inputs / _actions)
 };
+enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
 int fail(Env* e, int code, const std::string& msg) {
     g_last_error = msg;
@@ -374,9 +377,13 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     for (size_t k = 0; k < SM; k++)
         if (policy_id[k] == CAGYM_POL_RVO) new_any_rvo = 1;
     std::vector<int32_t> na(S), no(S, 0);
+    int new_n_ig = 0;
     for (size_t s = 0; s < S; s++) {
         na[s] = n_agents ? n_agents[s] : (int32_t)M;
         if (na[s] < 0 || na[s] > (int32_t)M) return fail(e, CAGYM_E_INVALID, "n_agents out of range");
+        int c = 0;
+        for (int k = 0; k < na[s]; k++) c += policy_id[s * M + k] == CAGYM_POL_IGMCTS;
+        new_n_ig = s == 0 ? c : (c == new_n_ig ? new_n_ig : N_IG_UNEQUAL);
         if (n_obst && e->cfg.max_obstacles > 0) {
             no[s] = n_obst[s];
             if (no[s] < 0 || no[s] > e->cfg.max_obstacles) return fail(e, CAGYM_E_INVALID, "n_obst out of range");
@@ -466,6 +473,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     // a new pool restarts the episode numbering
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));
     e->any_rvo = new_any_rvo;
+    e->n_ig = new_n_ig;
     e->obst_rvo = new_obst_rvo;
     e->D.ko = new_ko;
     e->scenarios_set = true;
@@ -508,6 +516,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     HIPCHK(e, hipGetLastError());
     D.sc_heading0 = nullptr;  // toward the goal (agent.py:29-31)
     e->any_rvo = (P.ego_policy == CAGYM_POL_RVO || P.policy_a == CAGYM_POL_RVO || P.policy_b == CAGYM_POL_RVO) ? 1 : 0;
+    e->n_ig = (P.ego_policy == CAGYM_POL_IGMCTS || P.policy_a == CAGYM_POL_IGMCTS || P.policy_b == CAGYM_POL_IGMCTS) ? N_IG_RANDOM : 0;
     e->obst_rvo = 0;  // the generator draws free-space worlds
     e->D.ko = 0;
     if (e->cfg.max_obstacles > 0) {  // free space: empty rasters
@@ -805,9 +814,11 @@ int cagym_ga3c_act(void* env, const float* weights, int max_observed, void* work
         if (int rc = ga3c_pack(e, weights, st, false)) return rc;
         const unsigned grid = (unsigned)((e->cfg.n_worlds + 31) / 32);
         if (e->cfg.max_agents <= 16)
-            hipLaunchKernelGGL(k_ga3c_act_h16<16>, dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions);
+            hipLaunchKernelGGL((k_ga3c_act_h16<16, false>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions,
+                               (const float*)nullptr);
         else
-            hipLaunchKernelGGL(k_ga3c_act_h16<32>, dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions);
+            hipLaunchKernelGGL((k_ga3c_act_h16<32, false>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions,
+                               (const float*)nullptr);
         HIPCHK(e, hipGetLastError());
         return CAGYM_OK;
     }
@@ -834,6 +845,35 @@ int cagym_ga3c_act(void* env, const float* weights, int max_observed, void* work
                        ext_actions, (int32_t*)nullptr, (float*)nullptr, ctr);
     if (int rc = launched("k_ga3c_forward")) return rc;
     return CAGYM_OK;
+}
+
+int cagym_ga3c_act_merge(void* env, const float* weights, int max_observed, void* work, const float* ext_in, float* actions, void* stream) {
+    Env* e = reinterpret_cast<Env*>(env);
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    if (!weights || !work || !actions || max_observed < 1 || max_observed > 10)
+        return fail(e, CAGYM_E_INVALID, "bad arguments (max_observed in 1..10)");
+    const size_t total = (size_t)e->cfg.n_worlds * e->cfg.max_agents;
+    if (ext_in && ext_in < actions + 2 * total && actions < ext_in + 2 * total) return fail(e, CAGYM_E_INVALID, "ext_in aliases actions");
+    if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(ext_in)) & 7)
+        return fail(e, CAGYM_E_INVALID, "actions / ext_in must be 8-byte aligned");
+    DEVGUARD(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int which = ga3c_kernel_choice();
+    if (which == GA_KERNEL_BAD) return fail(e, CAGYM_E_INVALID, "CAGYM_GA3C: unknown forward kernel (h16, mfma32 or valu)");
+    if (which == GA_KERNEL_H16) {  // cagym_ga3c_act's launch; its status lanes copy the other rows
+        if (int rc = ga3c_pack(e, weights, st, false)) return rc;
+        const unsigned grid = (unsigned)((e->cfg.n_worlds + 31) / 32);
+        if (e->cfg.max_agents <= 16)
+            hipLaunchKernelGGL((k_ga3c_act_h16<16, true>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, actions, ext_in);
+        else
+            hipLaunchKernelGGL((k_ga3c_act_h16<32, true>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, actions, ext_in);
+        HIPCHK(e, hipGetLastError());
+        return CAGYM_OK;
+    }
+    // CAGYM_GA3C=mfma32 / valu (A/B): the table first, then cagym_ga3c_act's chain over it
+    if (ext_in) HIPCHK(e, hipMemcpyAsync(actions, ext_in, total * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    else HIPCHK(e, hipMemsetAsync(actions, 0, total * 2 * sizeof(float), st));
+    return cagym_ga3c_act(env, weights, max_observed, work, actions, stream);
 }
 
 #ifdef CAGYM_STAMPS
@@ -1019,6 +1059,42 @@ int cagym_ig_rollouts(void* env, const double* pose0, const uint64_t* observed0,
                        reinterpret_cast<const unsigned long long*>(exclude), world, n_steps, radius, nsims, max_steps, xdt,
                        dt, fov_rad, range, (unsigned long long)seed, rewards, actions, final_pose,
                        reinterpret_cast<unsigned long long*>(observed_out));
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+static int ig_robots_check(Env* e, int n_robots, const char* what) {
+    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, std::string(what) + " before cagym_set_scenarios");
+    if (e->n_ig == N_IG_RANDOM)
+        return fail(e, CAGYM_E_STATE, std::string(what) + ": the generated pool's IG robot count is random (cagym_generate_scenarios)");
+    if (n_robots < 1 || e->n_ig != n_robots)
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": every scenario of the pool must hold exactly n_robots IG agents (" +
+                                            (e->n_ig == N_IG_UNEQUAL ? std::string("the counts differ") : std::to_string(e->n_ig) + " per scenario") + ")");
+    return CAGYM_OK;
+}
+
+int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const float* obs_oas, double* poses, double* detections,
+                          int32_t* n_det, void* stream) {
+    Env* e = reinterpret_cast<Env*>(env);
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    if (!obs_oas || !poses || !detections || !n_det) return fail(e, CAGYM_E_INVALID, "null argument");
+    if (int rc = ig_robots_check(e, n_robots, "cagym_ig_robot_inputs")) return rc;
+    DEVGUARD(e);
+    hipLaunchKernelGGL(k_ig_robot_inputs, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D,
+                       n_robots, (float)detect_range, obs_oas, poses, detections, n_det);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_robot_actions(void* env, int n_robots, const double* planner_actions, float* actions, void* stream) {
+    Env* e = reinterpret_cast<Env*>(env);
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    if (!planner_actions || !actions) return fail(e, CAGYM_E_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(actions) & 7) return fail(e, CAGYM_E_INVALID, "actions must be 8-byte aligned");
+    if (int rc = ig_robots_check(e, n_robots, "cagym_ig_robot_actions")) return rc;
+    DEVGUARD(e);
+    hipLaunchKernelGGL(k_ig_robot_actions, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D,
+                       n_robots, planner_actions, actions);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

@@ -518,8 +518,13 @@ __global__ void __launch_bounds__(512) k_ga3c_forward_h16(const unsigned char* _
 // workgroup, 256 workgroups; a handle whose every slot is a GA3C agent runs max_agents tiles per workgroup one after the other (what
 // the three-kernel chain did in as many rounds of workgroups).  Until round 4 (second session) the call was three launches -
 // selection with ticket words, state rows through HBM, forward - 5.1 + 5.9 us in front of the network (profiles/r4).
-template <int LPA>
-__global__ void __launch_bounds__(512) k_ga3c_act_h16(CagymDev D, const unsigned char* __restrict__ P, int max_observed, float* ext_actions) {
+//
+// MERGE (cagym_ga3c_act_merge): the launch writes the whole [N*M, 2] action table - the lanes that load a slot's status word copy
+// ext_in's row of every slot that is not an active GA3C agent (or write (0, 0) without ext_in), the forward pass writes the rest.
+// MERGE = false is cagym_ga3c_act's kernel as it was (other rows untouched).
+template <int LPA, bool MERGE>
+__global__ void __launch_bounds__(512) k_ga3c_act_h16(CagymDev D, const unsigned char* __restrict__ P, int max_observed, float* ext_actions,
+                                                      const float* __restrict__ ext_in) {
     GASTAMP_BEGIN();
     ga16_keep_f16_subnormals();
     __shared__ __attribute__((aligned(16))) unsigned char lds[GA16_LDS_BYTES];
@@ -534,6 +539,14 @@ __global__ void __launch_bounds__(512) k_ga3c_act_h16(CagymDev D, const unsigned
     uint32_t st[2];
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) st[pass] = pass * 512 + n < nslots ? D.status[first + pass * 512 + n] : 0u;
+    // MERGE: the caller's rows are requested beside the status words, AHEAD of the weights - the copy below then waits for them
+    // alone (vector loads return in order), not for the weight preload that overlaps the listing and the state rows
+    float2 row[2];
+    if constexpr (MERGE) {
+#pragma unroll
+        for (int pass = 0; pass < 2; pass++)
+            row[pass] = ext_in && pass * 512 + n < nslots ? reinterpret_cast<const float2*>(ext_in)[first + pass * 512 + n] : make_float2(0.f, 0.f);
+    }
     // the first tile's weights travel while the agents are listed and their state rows built (requested BEHIND the status words:
     // vector loads return in order)
     Ga16Pre W;
@@ -545,6 +558,13 @@ __global__ void __launch_bounds__(512) k_ga3c_act_h16(CagymDev D, const unsigned
         take[pass] = (st[pass] & CAGYM_FLAG_ACTIVE) && ST_POLICY(st[pass]) == CAGYM_POL_GA3C;
         m[pass] = __ballot(take[pass]);
         if (lane == 0) wcnt[pass][wave] = __popcll(m[pass]);
+    }
+    if constexpr (MERGE) {
+#pragma unroll
+        for (int pass = 0; pass < 2; pass++) {
+            const int s = pass * 512 + n;
+            if (s < nslots && !take[pass]) reinterpret_cast<float2*>(ext_actions)[first + s] = row[pass];
+        }
     }
     __syncthreads();
     int cnt = 0;
@@ -592,4 +612,5 @@ __global__ void __launch_bounds__(512) k_ga3c_act_h16(CagymDev D, const unsigned
         if (tile + 32 < cnt) ga16_preload(P, W);
     }
 }
+
 

@@ -451,3 +451,63 @@ __global__ void __launch_bounds__(128) k_ig_rollouts(IgDev G, const double* pose
         }
     }
 }
+
+// ---- the env's IG robots (cagym_ig_robot_inputs / cagym_ig_robot_actions): one wave per world ----------------------------------------
+// A world's robots are its active slots whose policy id is CAGYM_POL_IGMCTS, in slot order; lane j holds slot j (M <= 32).
+__device__ __forceinline__ bool ig_robot_slot(const CagymDev& D, int w, int lane, unsigned long long& robots) {
+    const uint32_t st = lane < D.M ? D.status[(size_t)w * D.M + lane] : 0u;
+    const bool robot = (st & CAGYM_FLAG_ACTIVE) && ST_POLICY(st) == CAGYM_POL_IGMCTS;
+    robots = __ballot(robot);
+    return robot;
+}
+
+// ig_mcts.update_belief's inputs (ig_mcts.py:117-152) for the R robots of every world: poses [N,R,3] = (x, y, heading) of the state,
+// and the detector emulation (find_targets_in_obs) on each robot's OtherAgentsStates rows oas [N,M,M-1,10]: a row is a target when
+// column 9 is 1.0 (a static agent) and sqrt(r0^2 + r1^2) <= range (fp32, as the table is; the FOV test is always true);
+// detections [N,R,M-1,2] = row[0:2] + pose[0:2] in fp64, in row order (farthest first), n_det [N,R].
+__global__ void __launch_bounds__(64) k_ig_robot_inputs(CagymDev D, int R, float range, const float* __restrict__ oas, double* poses,
+                                                         double* detections, int32_t* n_det) {
+    const int w = blockIdx.x, lane = threadIdx.x, M = D.M, K = M - 1;
+    unsigned long long robots;
+    ig_robot_slot(D, w, lane, robots);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int r = 0; r < R; r++) {
+        const int slot = robots ? __ffsll((long long)robots) - 1 : -1;  // wave-uniform
+        robots &= robots - 1ull;
+        double px = 0.0, py = 0.0, th = 0.0;
+        int cnt = 0;
+        if (slot >= 0) {
+            const size_t a = (size_t)w * M + slot;
+            px = D.px[a]; py = D.py[a]; th = D.heading[a];
+            bool tgt = false;
+            float r0 = 0.f, r1 = 0.f;
+            if (lane < K) {
+                const float* row = oas + (a * K + lane) * 10;
+                r0 = row[0];
+                r1 = row[1];
+                tgt = row[9] == 1.0f && sqrtf(r0 * r0 + r1 * r1) <= range;
+            }
+            const unsigned long long tm = __ballot(tgt);
+            if (tgt) {
+                double* d = detections + (((size_t)w * R + r) * K + __popcll(tm & below)) * 2;
+                d[0] = (double)r0 + px;
+                d[1] = (double)r1 + py;
+            }
+            cnt = __popcll(tm);
+        }
+        // (a world with fewer robots - which the host-side validation of the pool rules out - gets zero poses and no detections)
+        if (lane < 3) poses[((size_t)w * R + r) * 3 + lane] = lane == 0 ? px : lane == 1 ? py : th;
+        if (lane == 0) n_det[(size_t)w * R + r] = cnt;
+    }
+}
+
+// the planner's (v, omega) [N,R,2] into the robots' rows of the action table [N*M,2] (fp64 -> fp32 round to nearest)
+__global__ void __launch_bounds__(64) k_ig_robot_actions(CagymDev D, int R, const double* __restrict__ planned, float* actions) {
+    const int w = blockIdx.x, lane = threadIdx.x;
+    unsigned long long robots;
+    if (!ig_robot_slot(D, w, lane, robots)) return;
+    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
+    if (rank >= R) return;
+    const double* p = planned + ((size_t)w * R + rank) * 2;
+    reinterpret_cast<float2*>(actions)[(size_t)w * D.M + lane] = make_float2((float)p[0], (float)p[1]);
+}

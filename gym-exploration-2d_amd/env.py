@@ -57,7 +57,34 @@ class GA3CCADRLPolicy(_Policy):
 
 
 class ig_mcts(_Policy):
+    """Marker of policies/ig_mcts.py.  set_param records the planner parameters; the env plans every robot inside step()
+    (BatchedCollisionAvoidanceEnv.attach_ig_mcts) and writes the world's team reward to `team_reward` after each step."""
     policy_id, str = sc.POLICY_IGMCTS, "ig_mcts"
+    PLANNER_KEYS = ("detect_fov", "detect_range", "dt", "xdt", "Ntree", "Nsims", "mcts_cp", "mcts_horizon", "mcts_gamma",
+                    "Ncycles", "parallelize_agents")
+
+    def __init__(self):
+        self.params = None
+        self.ego_agent = None
+        self.team_reward = None
+
+    def set_param(self, ego_agent, occ_map, map_size, map_res, detect_fov, detect_range, dt=0.1, xdt=1,
+                  Ntree=100, Nsims=10, parallelize_sims=False, mcts_cp=1., mcts_horizon=10, mcts_gamma=1, Ncycles=5,
+                  parallelize_agents=False):
+        """ig_mcts.set_param (ig_mcts.py:53-77).  The device belief grid and distance field are fixed to the reference's map
+        (Config.MAP_WIDTH x MAP_HEIGHT at SUBMAP_RESOLUTION), so other values are refused; occ_map is the env's raster
+        (env.map) and is not copied.  parallelize_sims is ignored: every tree grow runs its Nsims roll-outs in parallel on the
+        device anyway.  The planner's random streams are seeded (CollisionAvoidanceEnv.planner_seed), not np.random."""
+        if tuple(np.asarray(map_size, dtype=np.float64).ravel()) != (float(Config.MAP_WIDTH), float(Config.MAP_HEIGHT)):
+            raise ValueError("ig_mcts.set_param: map_size must be (Config.MAP_WIDTH, Config.MAP_HEIGHT) = (%r, %r), got %r"
+                             % (Config.MAP_WIDTH, Config.MAP_HEIGHT, map_size))
+        if float(map_res) != float(Config.SUBMAP_RESOLUTION):
+            raise ValueError("ig_mcts.set_param: map_res must be Config.SUBMAP_RESOLUTION = %r, got %r"
+                             % (Config.SUBMAP_RESOLUTION, map_res))
+        self.ego_agent = ego_agent
+        self.params = {"detect_fov": float(detect_fov), "detect_range": float(detect_range), "dt": float(dt), "xdt": int(xdt),
+                       "Ntree": int(Ntree), "Nsims": int(Nsims), "mcts_cp": float(mcts_cp), "mcts_horizon": int(mcts_horizon),
+                       "mcts_gamma": float(mcts_gamma), "Ncycles": int(Ncycles), "parallelize_agents": bool(parallelize_agents)}
 
 
 class UnicycleDynamics(object):
@@ -97,6 +124,10 @@ class Config(object):
     HOMOGENEOUS_TESTING = False
     COLLISION_AV_W_STATIC_AGENT = False
     MAX_NUM_AGENTS_IN_ENVIRONMENT = 10
+    MAX_NUM_OTHER_AGENTS_OBSERVED = MAX_NUM_AGENTS_IN_ENVIRONMENT - 1  # config.py:72 (GA3C-CADRL reads at most 10)
+    MAP_WIDTH = 30          # config.py: the static map's extent (the IG belief grid and distance field are fixed to it)
+    MAP_HEIGHT = 30
+    SUBMAP_RESOLUTION = 0.1
     LASERSCAN_LENGTH = 16
     NEAR_GOAL_THRESHOLD = 0.75
     MAX_TIME_RATIO = 3.0
@@ -228,6 +259,9 @@ class CollisionAvoidanceEnv(object):
         self._benv = None
         self._snap = None
         self._sig = None
+        self.map = None
+        self.planner_seed = 0  # seed of the ig_mcts planner's random streams (the reference draws from np.random)
+        self._ig_key = None
 
     # -- setters of the reference surface ---------------------------------------------------------
     def set_agents(self, agents):
@@ -342,6 +376,8 @@ class CollisionAvoidanceEnv(object):
         if n > M:
             raise ValueError("more agents than Config.MAX_NUM_AGENTS_IN_ENVIRONMENT")
         rects = self._rects(self.default_obstacles)
+        if any(isinstance(a.policy, ig_mcts) for a in specs) and len(rects) == 0:
+            raise ValueError("ig_mcts agents need a world with obstacles: the information-gain primitives work on its raster")
         laser = any(isinstance(s, LaserScanSensor) for a in specs for s in a.sensors)
         sig = (M, max(len(rects), 0), laser, self._game_over_mode(), Config.COLLISION_AV_W_STATIC_AGENT, Config.DT)
         if self._benv is None or sig != self._sig:
@@ -351,6 +387,7 @@ class CollisionAvoidanceEnv(object):
                                                       collide_with_static=sig[4], laserscan=laser, device=self.device,
                                                       dt=Config.DT)
             self._sig = sig
+            self._ig_key = None
         a6 = np.zeros((1, M, 6))
         a6[0, :, 4] = 1.0
         a6[0, :, 5] = 0.1
@@ -368,7 +405,17 @@ class CollisionAvoidanceEnv(object):
         self._benv.set_scenarios(a6, pol, dyn, heading0=h0, n_agents=[n], coop=coop,
                                  obstacles=rects[None] if len(rects) else None,
                                  n_obst=[len(rects)] if len(rects) else None)
+        if any(isinstance(a.policy, GA3CCADRLPolicy) for a in specs):  # the iros18 checkpoint (collision_avoidance_env.py:446-450)
+            mo = min(int(Config.MAX_NUM_OTHER_AGENTS_OBSERVED), M - 1, 10)
+            if self._benv._ga3c is None or self._benv._ga3c.max_observed != mo:
+                self._benv.attach_ga3c("iros18", max_observed=mo)
+        if not any(isinstance(a.policy, ig_mcts) for a in specs) and self._benv._igm is not None:
+            self._benv.detach_ig_mcts()
+            self._ig_key = None
         self._benv.reset()
+        self.map = self._benv.state().get("map_bits")
+        if self.map is not None:
+            self.map = self.map[0]  # [300, 10] bit-packed occupancy raster of this world (Map.py:107-123)
         self.episode_number += 1
         self.episode_step_number = 0
         self._snap = None
@@ -392,9 +439,16 @@ class CollisionAvoidanceEnv(object):
                     continue
                 v = np.atleast_1d(np.asarray(v, dtype=np.float32)).ravel()
                 ext[0, i, :min(2, v.size)] = v[:2]
+        robots = [a.policy for a in self.agents if isinstance(a.policy, ig_mcts)]
+        if robots:
+            self._attach_planner(robots)
         self.episode_step_number += 1
         self.total_number_of_steps += 1
         _, rew, go, _ = self._benv.step(ext)
+        if robots:
+            tr = float(self._benv.team_reward[0].item())
+            for p in robots:
+                p.team_reward = tr
         self._snap = None
         obs = self._obs_dict()
         rewards = rew[0, :len(self.agents)].double().cpu().numpy()
@@ -403,6 +457,23 @@ class CollisionAvoidanceEnv(object):
         game_over = bool(go[0].item())
         which = {a.id: bool(a.is_done) for a in self.agents}
         return obs, rewards, game_over, {'which_agents_done': which}
+
+    def _attach_planner(self, robots):
+        """The robots' common set_param values drive one device planner per env (attached again when they change)."""
+        if any(p.params is None for p in robots):
+            raise RuntimeError("an ig_mcts agent has no parameters: call policy.set_param(...) after reset() and before step()")
+        params = robots[0].params
+        if any(p.params != params for p in robots[1:]):
+            raise ValueError("all ig_mcts agents of the env must share the same set_param planner parameters "
+                             "(one Dec-MCTS planner plans the whole team)")
+        if params["dt"] != self._sig[5]:
+            raise ValueError("ig_mcts.set_param: dt must equal Config.DT")
+        key = (tuple(sorted(params.items())), self.planner_seed, len(robots))
+        if self._ig_key != key or self._benv._igm is None:
+            p = dict(params)
+            del p["dt"]
+            self._benv.attach_ig_mcts(seed=self.planner_seed, **p)
+            self._ig_key = key
 
 
 def get_testcase_two_agents(policies=(LearningPolicy, NonCooperativePolicy)):

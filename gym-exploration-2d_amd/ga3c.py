@@ -41,6 +41,8 @@ class GA3CCADRLPolicy(object):
         self.L.cagym_ga3c_act_workspace_bytes.restype = C.c_size_t
         self.L.cagym_ga3c_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self.L.cagym_ga3c_act.restype = C.c_int
+        self.L.cagym_ga3c_act_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.L.cagym_ga3c_act_merge.restype = C.c_int
         self.L.cagym_ga3c_load_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self.L.cagym_ga3c_load_weights.restype = C.c_int
         self._work = None
@@ -144,3 +146,15 @@ class GA3CCADRLPolicy(object):
             rc = self.L.cagym_ga3c_act(b.h, self.blob.data_ptr(), self.max_observed, self._work.data_ptr(), ext_actions.data_ptr(), b._stream())
         _lib.check(self.L, b.h, rc, "cagym_ga3c_act")
         return ext_actions
+
+    def act_merge(self, ext_in, actions):
+        """The whole action table in one launch (cagym_ga3c_act_merge): actions [N,M,2] f32 gets this policy's action for every
+        active GA3C agent and ext_in's row (or (0, 0) when ext_in is None) for every other slot; ext_in is not written."""
+        b = self.b
+        assert actions.is_contiguous() and actions.dtype == torch.float32
+        if self._work is None:
+            self._work = torch.empty((int(self.L.cagym_ga3c_act_workspace_bytes(b.h)),), dtype=torch.uint8, device=b.device)
+        rc = self.L.cagym_ga3c_act_merge(b.h, self.blob.data_ptr(), self.max_observed, self._work.data_ptr(),
+                                         None if ext_in is None else ext_in.data_ptr(), actions.data_ptr(), b._stream())
+        _lib.check(self.L, b.h, rc, "cagym_ga3c_act_merge")
+        return actions

@@ -31,6 +31,8 @@ class InfoGain(object):
         L.cagym_ig_mi_reward.argtypes = [vp, vp, vp, C.c_int, vp, vp]
         L.cagym_ig_next_pose.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
         L.cagym_ig_rollouts.argtypes = [vp] * 7 + [C.c_int] * 4 + [C.c_double] * 3 + [C.c_uint64, vp, vp, vp, vp, vp]
+        L.cagym_ig_robot_inputs.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+        L.cagym_ig_robot_actions.argtypes = [vp, C.c_int, vp, vp, vp]
         with torch.cuda.device(benv.device):
             _lib.check(L, benv.h, L.cagym_ig_init(benv.h, benv._stream()), "cagym_ig_init")
         d2, bel = vp(), vp()
@@ -44,6 +46,18 @@ class InfoGain(object):
         if shape is not None:
             t = t.reshape(shape)
         return t.contiguous()
+
+    def robot_inputs(self, n_robots, detect_range, obs_oas, poses, detections, n_det):
+        """cagym_ig_robot_inputs: the R robots' poses [N,R,3] and detections [N,R,M-1,2] / n_det [N,R] (the detector emulation of
+        find_targets_in_obs on their rows of obs_oas), written into the given device tensors."""
+        rc = self.L.cagym_ig_robot_inputs(self.b.h, int(n_robots), float(detect_range), obs_oas.data_ptr(), poses.data_ptr(),
+                                          detections.data_ptr(), n_det.data_ptr(), self.b._stream())
+        _lib.check(self.L, self.b.h, rc, "cagym_ig_robot_inputs")
+
+    def robot_actions(self, n_robots, planner_actions, actions):
+        """cagym_ig_robot_actions: the planner's (v, omega) [N,R,2] f64 into the robots' rows of actions [N,M,2] f32."""
+        rc = self.L.cagym_ig_robot_actions(self.b.h, int(n_robots), planner_actions.data_ptr(), actions.data_ptr(), self.b._stream())
+        _lib.check(self.L, self.b.h, rc, "cagym_ig_robot_actions")
 
     def edf(self):
         """[S,300,300] f64 Euclidean distance field in metres (edfMap.map)."""

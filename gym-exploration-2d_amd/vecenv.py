@@ -86,9 +86,17 @@ class CagymVecEnv(object):
     def step_async(self, actions):
         self._actions = actions
 
+    @staticmethod
+    def _external(actions):
+        """None, or a list / tuple of None (the reference's env.step([None])), means no external actions."""
+        if actions is None or (isinstance(actions, (list, tuple)) and all(a is None for a in actions)):
+            return None
+        return actions
+
     def step_wait(self):
         b = self.b
-        _, rew, go, info = b.step(self._actions, auto_reset=True)  # DummyVecEnv auto-reset inside the launch
+        # DummyVecEnv auto-reset inside the launch; an attached GA3C policy fills its agents' rows (BatchedCollisionAvoidanceEnv.step)
+        _, rew, go, info = b.step(self._external(self._actions), auto_reset=True)
         rews = rew[:, 0] if self.single_agent else rew
         return self.flat(), rews, go.bool(), {"flags": info["flags"]}
 

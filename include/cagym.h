@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define CAGYM_VERSION 112 /* 0.1.2: cagym_step_begin / cagym_step_finish, CAGYM_E_DEVICE */
+#define CAGYM_VERSION 112 /* 0.1.2: cagym_step_begin / cagym_step_finish, CAGYM_E_DEVICE.  cagym_ga3c_act_merge, cagym_ig_robot_inputs and
+                             cagym_ig_robot_actions are backward-compatible additions under the same version. */
 
 enum { CAGYM_OK = 0, CAGYM_E_INVALID = -1, CAGYM_E_NODEVICE = -2, CAGYM_E_HIP = -3, CAGYM_E_NOMEM = -4,
        CAGYM_E_STATE = -5, CAGYM_E_UNSUPPORTED = -6,
@@ -45,8 +46,12 @@ enum { CAGYM_POL_STATIC = 0,   /* policies/StaticPolicy.py:9-12            a = (
                                   max_agents - 1 half-plane slots of an LP group: 16 for max_agents 4, 32 for 10, 64
                                   otherwise; 2*max_obstacles <= 32; the obstacle-candidate lists in the LP scratch,
                                   13 B per (ego, candidate); the roll-out's LDS within 160 KB)                      */
-       CAGYM_POL_GA3C = 6,     /* policies/GA3CCADRLPolicy.py:34-43        action supplied by cagym_ga3c_* */
-       CAGYM_POL_IGMCTS = 7 }; /* policies/ig_mcts.py:79-109               (v, omega) supplied by planner  */
+       CAGYM_POL_GA3C = 6,     /* policies/GA3CCADRLPolicy.py:34-43        the step reads ext_actions; cagym_ga3c_act /
+                                  cagym_ga3c_act_merge write these agents' rows (the host env drives them inside step
+                                  once a GA3C policy is attached)                                               */
+       CAGYM_POL_IGMCTS = 7 }; /* policies/ig_mcts.py:79-109               the step reads ext_actions; cagym_ig_robot_inputs ->
+                                  cagym_ig_update_belief -> cagym_dmcts_plan -> cagym_ig_robot_actions write
+                                  these agents' (v, omega) (the host env drives them once ig_mcts is attached)  */
 
 /* dynamics ids (envs/dynamics/) */
 enum { CAGYM_DYN_UNICYCLE = 0,    /* UnicycleDynamics.py:10-24                 */
@@ -216,6 +221,13 @@ int cagym_ga3c_forward(void* env, const float* weights, const float* state, cons
 size_t cagym_ga3c_act_workspace_bytes(void* env);
 int cagym_ga3c_act(void* env, const float* weights, int max_observed, void* work, float* ext_actions, void* stream);
 
+/* cagym_ga3c_act writing the WHOLE action table actions [N*M, 2] in its one launch: every active GA3C agent gets (pref_speed * a0, a1)
+ * as cagym_ga3c_act computes it, every other slot its row of ext_in [N*M, 2] (DEVICE, read-only) or (0, 0) when ext_in is NULL.  ext_in
+ * must not alias actions (CAGYM_E_INVALID), so a step driven this way leaves the caller's action buffer untouched; both 8-byte aligned.
+ * CAGYM_GA3C=mfma32 / valu: a device copy (or clear) of the table, then cagym_ga3c_act's chain. */
+int cagym_ga3c_act_merge(void* env, const float* weights, int max_observed, void* work, const float* ext_in, float* actions,
+                         void* stream);
+
 /* ---- information-gain planner primitives (cfg 5).  All pointers DEVICE.  A visibility set is a
  * [60] u64 mask: bit i of word j <=> belief cell (i, j) (x index i, y index j; 0.5 m cells over 30x30 m). ---- */
 
@@ -321,6 +333,20 @@ typedef struct cagym_dmcts_params {
     uint64_t seed;
 } cagym_dmcts_params;
 size_t cagym_dmcts_workspace_bytes(int n_worlds, const cagym_dmcts_params* params);
+
+/* The env's IG robots: in every world the active slots whose policy id is CAGYM_POL_IGMCTS, in slot order.  Both calls need every
+ * scenario of the pool to hold exactly n_robots of them (counted by cagym_set_scenarios): CAGYM_E_INVALID otherwise, and CAGYM_E_STATE
+ * after a cagym_generate_scenarios whose policies include CAGYM_POL_IGMCTS (the count is random there).  One wave per world.
+ * cagym_ig_robot_inputs: the inputs of ig_mcts.update_belief (policies/ig_mcts.py:117-152) on the current state: poses [N,R,3] f64
+ *   = (x, y, heading); the reference's detector emulation on each robot's OtherAgentsStates rows obs_oas [N,M,M-1,10] f32 (as the last
+ *   step / reset wrote them): a row is a target when column 9 == 1.0 (a static agent) and sqrt(r0^2 + r1^2) <= detect_range, in fp32
+ *   like the table (the FOV test is always true, SURVEY Q24, and left out); detections [N,R,M-1,2] f64 = row[0:2] + pose[0:2] in row
+ *   order (farthest first), n_det [N,R] i32 - the layout cagym_ig_update_belief takes (P = R, Dmax = M-1).
+ * cagym_ig_robot_actions: the planner's (v, omega) [N,R,2] f64 (cagym_dmcts_plan) into the robots' rows of actions [N*M,2] f32
+ *   (round to nearest); other rows are untouched. */
+int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const float* obs_oas, double* poses, double* detections,
+                          int32_t* n_det, void* stream);
+int cagym_ig_robot_actions(void* env, int n_robots, const double* planner_actions, float* actions, void* stream);
 int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* poses, void* workspace,
                      size_t workspace_bytes, double* actions, uint8_t* paths, double* stats, void* stream);
 
