@@ -45,13 +45,22 @@ class CagymGenParams(C.Structure):
                 ("coop", C.c_double)]
 
 
+class CagymGen2Params(C.Structure):
+    """cagym_gen2_params (include/cagym.h)."""
+    _fields_ = [("seed", C.c_uint64), ("kinds_mask", C.c_uint32), ("number_of_agents", C.c_int32), ("fixed_count", C.c_int32),
+                ("ego_policy", C.c_int32), ("ego_dynamics", C.c_int32), ("override_policies", C.c_int32), ("policy_a", C.c_int32),
+                ("policy_b", C.c_int32), ("other_dynamics", C.c_int32), ("n_obst_min", C.c_int32), ("n_obst_max", C.c_int32),
+                ("max_tries", C.c_int32), ("p_b", C.c_double)]
+
+
 class CagymScenarioPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("agents6", "policy", "dynamics", "n_agents", "coop")]
 
 
 EXPORTS = ["cagym_version", "cagym_create", "cagym_destroy", "cagym_last_error", "cagym_set_scenarios",
            "cagym_reset", "cagym_step", "cagym_step_autoreset", "cagym_step_begin", "cagym_step_finish", "cagym_rollout", "cagym_get_state", "cagym_laserscan",
-           "cagym_generate_scenarios", "cagym_get_scenarios", "cagym_occupancy_grid", "cagym_kernel_name"]
+           "cagym_generate_scenarios", "cagym_get_scenarios", "cagym_occupancy_grid", "cagym_kernel_name",
+           "cagym_generate_reference_scenarios", "cagym_get_obstacles"]
 
 _lib = None
 
@@ -86,6 +95,8 @@ def load():
     L.cagym_occupancy_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cagym_generate_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymGenParams), C.POINTER(C.c_int32), C.c_void_p]
     L.cagym_get_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymScenarioPtrs)]
+    L.cagym_generate_reference_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymGen2Params), C.POINTER(C.c_int32), C.c_void_p]
+    L.cagym_get_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cagym_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
     _lib = L
     return L

@@ -156,6 +156,66 @@ class BatchedCollisionAvoidanceEnv(object):
         self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
         return int(nf.value) if check else None
 
+    def generate_reference_scenarios(self, kinds, seed, number_of_agents=None, fixed_count=False, ego_policy=5, ego_dynamics=4,
+                                     other_policies=None, p_b=None, other_dynamics=0, n_obst=None, max_tries=1000, check=True):
+        """Fill the scenario pool ON DEVICE with the reference's own training samplers (cagym_generate_reference_scenarios):
+        kinds = one test_cases.py sampler name or scenarios.GEN_* id, or several (every scenario then draws one uniformly, as
+        _init_agents' np.random.randint stage does; scenarios.reference_curriculum gives the set of a training step).
+        number_of_agents: the samplers' argument (default max_agents); fixed_count takes the top of its range (the seeded branch).
+        ego_dynamics / other_dynamics default to the samplers' FirstOrder / Unicycle; a GA3C ego of the swap and random-position
+        samplers gets UnicycleDynamicsMaxAcc as there.  other_policies=None keeps each sampler's rule (80/20 RVO / NonCooperative,
+        50/50 for random positions, RVO only among rectangles); a pair (a, b) with p_b gives every non-ego agent b with
+        probability p_b else a, a single id all of them.  n_obst=(min, max) narrows the stage samplers' rectangle counts
+        ((0, 4) / (2, 10); None or a negative bound: none): n_obst=(-1, 6) caps stage 2 at 6 and leaves stage 1 at 0..4.  A count
+        that can exceed max_obstacles is refused.  max_tries bounds every rejection loop: the reference's loops are unbounded,
+        and a world that leaves no room for an agent (ten agents among ten stage-2 rectangles can) spins its lane to the bound -
+        1000 keeps a pool of 8192 stage-2 worlds near 10 ms, 100000 takes about 0.3 s.  Returns the number of agents and
+        rectangles whose rejection loop hit max_tries (they keep their last draw) when check=True."""
+        ks = [kinds] if isinstance(kinds, (str, int, np.integer)) else list(kinds)
+        mask = 0
+        for k in ks:
+            mask |= 1 << sc.sampler_kind(k)
+        if number_of_agents is None:
+            number_of_agents = self.M
+        own = other_policies is not None
+        if not own:
+            pa, pb, pp = sc.POLICY_RVO, sc.POLICY_NONCOOP, 0.0
+        elif np.isscalar(other_policies):
+            pa = pb = int(other_policies)
+            pp = 0.0
+        else:
+            pa, pb = int(other_policies[0]), int(other_policies[1])
+            pp = 0.5 if p_b is None else float(p_b)
+        lo, hi = (-1, -1) if n_obst is None else (n_obst, n_obst) if np.isscalar(n_obst) else n_obst
+        P = _lib.CagymGen2Params(int(seed), mask, int(number_of_agents), int(bool(fixed_count)), int(ego_policy),
+                                 int(ego_dynamics), int(own), pa, pb, int(other_dynamics), int(lo), int(hi), int(max_tries), pp)
+        nf = C.c_int32(0)
+        with torch.cuda.device(self.device):
+            rc = self.L.cagym_generate_reference_scenarios(self.h, C.byref(P), C.byref(nf) if check else None, self._stream())
+        _lib.check(self.L, self.h, rc, "cagym_generate_reference_scenarios")
+        # the policies the pool may hold
+        pols = {int(ego_policy)}
+        for k in {sc.sampler_kind(k) for k in ks}:
+            if own:
+                pols |= {pa} if pp < 1.0 else set()
+                pols |= {pb} if pp > 0.0 else set()
+            else:
+                pols |= {sc.POLICY_RVO} if k >= sc.GEN_STAGE_1 else {sc.POLICY_RVO, sc.POLICY_NONCOOP}
+        self._pool_policies = pols
+        self._n_ig = None
+        self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
+        return int(nf.value) if check else None
+
+    def obstacles(self):
+        """Zero-copy device views of the pool's rectangles: obstacles [S, max_obstacles, 4] (xl, yl, xu, yu), n_obst [S]."""
+        o, n = C.c_void_p(), C.c_void_p()
+        _lib.check(self.L, self.h, self.L.cagym_get_obstacles(self.h, C.byref(o), C.byref(n)), "cagym_get_obstacles")
+        if not self.Kobs:
+            return {"obstacles": torch.zeros((self.S, 0, 4), dtype=torch.float64, device=self.device),
+                    "n_obst": torch.zeros((self.S,), dtype=torch.int32, device=self.device)}
+        return {"obstacles": torch.as_tensor(_DevArray(o.value, (self.S, self.Kobs, 4), "f8"), device=self.device),
+                "n_obst": torch.as_tensor(_DevArray(n.value, (self.S,), "i4"), device=self.device)}
+
     def scenarios(self):
         """Zero-copy device views of the scenario pool: agents6 [S,M,6], policy / dynamics [S,M], n_agents [S], coop."""
         sp = _lib.CagymScenarioPtrs()

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "cagym_ga3c.h"
 #include "cagym_ga3c16.h"
 #include "cagym_gen.h"
+#include "cagym_gen2.h"
 #include "cagym_dmcts.h"
 
 namespace {
@@ -358,6 +360,20 @@ int cagym_destroy(void* env) {
     return CAGYM_OK;
 }
 
+// A pool with RVO agents among rectangles: the kernels build obstacle half-planes (RVOPolicy.py:56-57).  The handle's max_obstacles
+// must fit an LP group (4 half-planes per lane; an agent sees at most 2 edges of a rectangle from their right side), the coverage bit
+// masks (<= 32 obstacle lines per ego), the obstacle-neighbour lists (8 B per candidate + 4 B per work item + 1 B per rank, in the LP3
+// scratch) and the roll-out's LDS.
+static int check_obst_rvo_capacity(Env* e) {
+    const int K = e->cfg.max_obstacles, M = e->cfg.max_agents, gw = lp_group_width(e);
+    const Spec2 sp = spec2(e);
+    const int as = cagym_as(M, sp.wpw);
+    if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "RVO agents among obstacles need the generation-3 kernels");
+    if (2 * K + M - 1 > 4 * gw || 2 * K > 32 || (size_t)2 * K * as * 13 > (size_t)4 * sp.nt * 16 || lds3_bytes(e, true, true) > 160 * 1024)
+        return fail(e, CAGYM_E_UNSUPPORTED, "too many rectangles per world for RVO agents at this max_agents (2 * max_obstacles + max_agents - 1 half-planes per ego)");
+    return CAGYM_OK;
+}
+
 int cagym_set_scenarios(void* env, const double* agents6, const double* heading0, const int32_t* policy_id,
                         const int32_t* dynamics_id, const int32_t* n_agents, const double* coop,
                         const double* obstacles, const int32_t* n_obst, void* stream) {
@@ -398,14 +414,9 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
         new_obst_rvo = (any_obst && new_any_rvo) ? 1 : 0;
         new_ko = new_obst_rvo ? 2 * e->cfg.max_obstacles : 0;
         if (new_obst_rvo) {
-            const int K = e->cfg.max_obstacles, gw = lp_group_width(e);
-            const Spec2 sp = spec2(e);
-            const int as = cagym_as((int)M, sp.wpw);
-            if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "RVO agents among obstacles need the generation-3 kernels");
-            // LP group capacity; coverage bit masks (<= 32 obstacle lines per ego); the obstacle-neighbour lists (8 B per candidate + 4 B per
-            // work item + 1 B per rank) borrow the LP3 scratch
-            if (2 * K + (int)M - 1 > 4 * gw || 2 * K > 32 || (size_t)2 * K * as * 13 > (size_t)4 * sp.nt * 16 || lds3_bytes(e, true, true) > 160 * 1024)
-                return fail(e, CAGYM_E_UNSUPPORTED, "too many rectangles per world for RVO agents at this max_agents (2 * max_obstacles + max_agents - 1 half-planes per ego)");
+            const int K = e->cfg.max_obstacles;
+            const int rc = check_obst_rvo_capacity(e);
+            if (rc != CAGYM_OK) return rc;
             for (size_t sc = 0; sc < S; sc++)
                     for (int k = 0; k < no[sc]; k++) {
                         const double* r = obstacles + (sc * K + k) * 4;
@@ -531,6 +542,108 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     e->scenarios_set = true;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
+    return CAGYM_OK;
+}
+
+int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
+    Env* e = reinterpret_cast<Env*>(env);
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    if (!params) return fail(e, CAGYM_E_INVALID, "null params");
+    const cagym_gen2_params& P = *params;
+    const int M = e->cfg.max_agents, K = e->cfg.max_obstacles;
+    if (P.kinds_mask == 0 || (P.kinds_mask >> CAGYM_GEN_NKINDS) != 0) return fail(e, CAGYM_E_INVALID, "kinds_mask: no kind or an unknown kind");
+    if ((P.number_of_agents > 2 ? P.number_of_agents : 2) > M) return fail(e, CAGYM_E_INVALID, "max(number_of_agents, 2) exceeds max_agents");
+    const int32_t pols[3] = {P.ego_policy, P.policy_a, P.policy_b};
+    for (int32_t q : pols)
+        if (q < 0 || q > CAGYM_POL_IGMCTS) return fail(e, CAGYM_E_INVALID, "policy id out of range");
+    if (P.ego_dynamics < 0 || P.ego_dynamics > CAGYM_DYN_FIRSTORDER || P.other_dynamics < 0 || P.other_dynamics > CAGYM_DYN_FIRSTORDER)
+        return fail(e, CAGYM_E_INVALID, "dynamics id out of range");
+    if (P.max_tries < 1 || !(P.p_b >= 0 && P.p_b <= 1)) return fail(e, CAGYM_E_INVALID, "bad generator parameters");
+    if (P.n_obst_max > K) return fail(e, CAGYM_E_INVALID, "n_obst_max exceeds the handle's max_obstacles");
+    if (P.n_obst_min >= 0 && P.n_obst_max >= 0 && P.n_obst_min > P.n_obst_max) return fail(e, CAGYM_E_INVALID, "n_obst_min exceeds n_obst_max");
+    // the policies the pool may hold (each kind's rule unless overridden: RVO / NonCooperative, stages RVO only)
+    const bool own = P.override_policies != 0;
+    auto may = [&](int pol, int kind) {
+        if (P.ego_policy == pol) return true;
+        const int pa = own ? P.policy_a : CAGYM_POL_RVO;
+        const int pb = own ? P.policy_b : (kind >= CAGYM_GEN_STAGE_1 ? CAGYM_POL_RVO : CAGYM_POL_NONCOOP);
+        const double p_b = own ? P.p_b : (kind >= CAGYM_GEN_STAGE_1 ? 0.0 : 0.5);
+        return (pa == pol && p_b < 1.0) || (pb == pol && p_b > 0.0);
+    };
+    bool any_rvo = false, any_ig = false, obst_rvo = false;
+    for (int kind = 0; kind < CAGYM_GEN_NKINDS; kind++) {
+        if (!((P.kinds_mask >> kind) & 1u)) continue;
+        any_rvo |= may(CAGYM_POL_RVO, kind);
+        any_ig |= may(CAGYM_POL_IGMCTS, kind);
+        if (kind == CAGYM_GEN_STAGE_1 || kind == CAGYM_GEN_STAGE_2) {
+            // the reference's randint range (tc.py:2377, 2482) narrowed by the caller's bounds, as the kernel narrows it
+            const int rlo = kind == CAGYM_GEN_STAGE_1 ? 0 : 2, rhi = kind == CAGYM_GEN_STAGE_1 ? 4 : 10;
+            const int lo = P.n_obst_min >= 0 ? std::max(rlo, (int)P.n_obst_min) : rlo;
+            const int hi = P.n_obst_max >= 0 ? std::min(rhi, (int)P.n_obst_max) : rhi;
+            const std::string name = kind == CAGYM_GEN_STAGE_1 ? "train_stage_1" : "train_stage_2";
+            if (hi > K)
+                return fail(e, CAGYM_E_INVALID, "the rectangle count of " + name + " (up to " + std::to_string(hi) +
+                                                    ") exceeds the handle's max_obstacles: cap it with n_obst_max");
+            if (lo > hi)
+                return fail(e, CAGYM_E_INVALID, "the n_obst bounds leave " + name + " no rectangle count (its range is " +
+                                                    std::to_string(rlo) + ".." + std::to_string(rhi) + ")");
+            obst_rvo |= hi > 0 && may(CAGYM_POL_RVO, kind);
+        }
+    }
+    // the counts are drawn on the device: the handle's max_obstacles decides, as cagym_set_scenarios decides it for a pool with a full world
+    if (obst_rvo) {
+        const int rc = check_obst_rvo_capacity(e);
+        if (rc != CAGYM_OK) return rc;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    DEVGUARD(e);
+    CagymDev& D = e->D;
+    Gen2Dev G;
+    G.G.agents6 = const_cast<double*>(D.sc_agents6);
+    G.G.policy = const_cast<int32_t*>(D.sc_policy);
+    G.G.dyn = const_cast<int32_t*>(D.sc_dyn);
+    G.G.nagents = const_cast<int32_t*>(D.sc_nagents);
+    G.G.coop = const_cast<double*>(D.sc_coop);
+    G.G.nobst = const_cast<int32_t*>(D.sc_nobst);
+    G.G.S = e->cfg.n_scenarios;
+    G.G.M = M;
+    G.obst = e->sc_obst;
+    G.prep = reinterpret_cast<float*>(e->sc_obst_prep);
+    G.K = K;
+    if (!e->gen_failed) {
+        int rcf = dalloc(e, &e->gen_failed, 1);
+        if (rcf != CAGYM_OK) return rcf;
+    }
+    int32_t* d_failed = e->gen_failed;
+    HIPCHK(e, hipMemsetAsync(d_failed, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
+    HIPCHK(e, hipGetLastError());
+    if (K > 0) {
+        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)G.G.S), dim3(256), 0, st, e->sc_obst, D.sc_nobst, K,
+                           const_cast<uint32_t*>(D.map_bits));
+        HIPCHK(e, hipGetLastError());
+    }
+    HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
+    if (n_failed_host) {
+        HIPCHK(e, hipMemcpyAsync(n_failed_host, d_failed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+    }
+    D.sc_heading0 = nullptr;  // toward the goal (agent.py:29-31)
+    e->any_rvo = any_rvo ? 1 : 0;
+    e->n_ig = any_ig ? N_IG_RANDOM : 0;
+    e->obst_rvo = obst_rvo ? 1 : 0;
+    e->D.ko = obst_rvo ? 2 * K : 0;
+    e->scenarios_set = true;
+    e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
+    return CAGYM_OK;
+}
+
+int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst) {
+    Env* e = reinterpret_cast<Env*>(env);
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    if (!obst || !n_obst) return fail(e, CAGYM_E_INVALID, "null out");
+    *obst = e->cfg.max_obstacles > 0 ? e->sc_obst : nullptr;
+    *n_obst = e->cfg.max_obstacles > 0 ? e->D.sc_nobst : nullptr;
     return CAGYM_OK;
 }
 

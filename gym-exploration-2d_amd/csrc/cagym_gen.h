@@ -26,9 +26,9 @@ __device__ __forceinline__ double gen_u01(uint64_t seed, uint32_t s, uint32_t k)
     return (double)(h >> 11) * 0x1.0p-53;
 }
 
-__global__ void __launch_bounds__(64) k_generate_scenarios(GenDev G, cagym_gen_params P, int32_t* n_failed) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= G.S) return;
+// scenario s by the rule of train_agents_random_positions; returns the agents whose rejection loop hit max_tries.  Shared by
+// k_generate_scenarios and cagym_gen2.h's RANDOM_POSITIONS kind, which therefore agree bit for bit.
+__device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym_gen_params& P, int s) {
     const int M = G.M;
     uint32_t k = 0;
     int n = P.n_min + (int)(gen_u01(P.seed, s, k++) * (double)(P.n_max - P.n_min + 1));
@@ -73,5 +73,12 @@ __global__ void __launch_bounds__(64) k_generate_scenarios(GenDev G, cagym_gen_p
     }
     G.nagents[s] = n;
     G.nobst[s] = 0;
+    return failed;
+}
+
+__global__ void __launch_bounds__(64) k_generate_scenarios(GenDev G, cagym_gen_params P, int32_t* n_failed) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= G.S) return;
+    const int failed = gen_random_positions(G, P, s);
     if (failed) atomicAdd(n_failed, failed);
 }

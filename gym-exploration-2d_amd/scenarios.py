@@ -28,6 +28,49 @@ DYN_MAXACC = 2           # UnicycleDynamicsMaxAcc.py:17-39
 DYN_SECONDORDER = 3      # UnicycleSecondOrderEulerDynamics.py:12-29
 DYN_FIRSTORDER = 4       # FirstOrderDynamics.py:10-23
 
+# samplers of test_cases.py that run on the device (cagym_generate_reference_scenarios; include/cagym.h)
+GEN_SWAP_CIRCLE = 0      # train_agents_swap_circle      test_cases.py:1192-1282
+GEN_PAIRWISE_SWAP = 1    # train_agents_pairwise_swap    :1283-1364
+GEN_RANDOM_POSITIONS = 2 # train_agents_random_positions :1365-1463
+GEN_STAGE_1 = 3          # train_stage_1                 :2359-2463
+GEN_STAGE_2 = 4          # train_stage_2                 :2464-2572
+REFERENCE_SAMPLERS = {"train_agents_swap_circle": GEN_SWAP_CIRCLE, "train_agents_pairwise_swap": GEN_PAIRWISE_SWAP,
+                      "train_agents_random_positions": GEN_RANDOM_POSITIONS, "train_stage_1": GEN_STAGE_1,
+                      "train_stage_2": GEN_STAGE_2}
+# the training set config.py:91 names beside the IG default
+TRAINING_SCENARIOS = ("train_agents_swap_circle", "train_agents_random_positions", "train_agents_pairwise_swap")
+
+
+def sampler_kind(name):
+    """GEN_* id of a test_cases.py sampler name (or of a GEN_* id itself); ValueError for samplers without a device twin."""
+    if isinstance(name, (int, np.integer)) and 0 <= int(name) < len(REFERENCE_SAMPLERS):
+        return int(name)
+    if name not in REFERENCE_SAMPLERS:
+        raise ValueError("no device sampler for scenario %r; supported: %s" % (name, ", ".join(sorted(REFERENCE_SAMPLERS))))
+    return REFERENCE_SAMPLERS[name]
+
+
+def reference_curriculum(total_steps, names=TRAINING_SCENARIOS):
+    """The training branch of CollisionAvoidanceEnv._init_agents (collision_avoidance_env.py:418-441) at total_steps env steps:
+    (kinds, number_of_agents) - the GEN_* ids the pool draws from (the scenario index, or np.random.randint(2, len(names)) from
+    5e6 steps on, i.e. every name from the third) and the agent count handed to the sampler.  Pass the result to
+    BatchedCollisionAvoidanceEnv.generate_reference_scenarios(kinds, seed, number_of_agents)."""
+    kinds = [sampler_kind(n) for n in names]
+    t = float(total_steps)
+    if t < 2e5:      # supervised learning step
+        idx, n = [0], 2
+    elif t < 1e6:
+        idx, n = [0], 4
+    elif t < 3e6:
+        idx, n = [1], 4
+    elif t < 5e6:
+        idx, n = [2], 6
+    else:
+        idx, n = list(range(2, len(kinds))), (6 if t < 7e6 else 8)
+    if not idx or idx[-1] >= len(kinds):
+        raise ValueError("the curriculum at %g steps needs at least %d scenario names" % (t, (idx[-1] if idx else 2) + 1))
+    return sorted({kinds[i] for i in idx}), n
+
 
 def random_world(rng, M, side=7.5, min_travel=4.0, min_sep=1.5, radius=0.5, pref_speed=1.0):
     """One world: float64 [M, 6] rows [sx, sy, gx, gy, pref_speed, radius]."""

@@ -305,6 +305,65 @@ typedef struct cagym_scenario_ptrs {
 } cagym_scenario_ptrs;
 int cagym_get_scenarios(void* env, cagym_scenario_ptrs* out);
 
+/* ---- on-device samplers of the reference's training scenarios (tc.py:1192-1463, 2359-2572) -------------------
+ * cagym_generate_reference_scenarios fills every scenario of the pool with one sampler of test_cases.py, one lane per scenario,
+ * on the counter-based generator of cagym_generate_scenarios: u(k) = U[0,1) draw k of the scenario's stream (seed, scenario),
+ * U(lo, hi) = lo + (hi - lo) * u(k).  NOT numpy's / random's MT19937 streams: agreement with the reference is distributional.
+ * nmax = max(number_of_agents, 2); a count draw  c(lo, hi) = lo + (int)(u(k) * (hi - lo + 1)), clamped, is still made (and
+ * ignored) when fixed_count != 0, which takes hi (the reference's seeded branch, tc.py:1206-1209).  Distances are
+ * sqrt(dx*dx + dy*dy) in fp64; every rejection loop stops after max_tries attempts, keeps its last draw and adds the agents
+ * (a pair counts 2) or rectangles it placed that way to *n_failed.  Policies of the non-ego agents, per agent in slot order:
+ * u(k) < p_b ? policy_b : policy_a, with (policy_a, policy_b, p_b) = each kind's rule below or, override_policies != 0, the
+ * caller's.  Rows of slots >= n_agents: (0, 0, 0, 0, 1, 0.5), Static, Unicycle.  heading: toward the goal (agent.py:29-31).
+ *   SWAP_CIRCLE (train_agents_swap_circle, tc.py:1192-1282): u0: n = c(2, nmax); n_agents = 2 * (n / 2).  Per pair p:
+ *     distance = U(4, 8), angle = U(-pi, pi) (2 draws per attempt), s = distance * (cos, sin)(angle); slot 2p starts at -s
+ *     with goal s, slot 2p+1 the reverse; pairs p > 0 retry until both s and -s are >= 1.5 m from every earlier start
+ *     (is_pose_valid, :129-133).  Then one policy draw per slot 1..n_agents-1.  Rule: NonCooperative with p 0.2 else RVO
+ *     (uniform > 0.8, :1247-1250); coop 0.5 (ego 1.0); ego dynamics UnicycleDynamicsMaxAcc when ego_policy is GA3C.
+ *   PAIRWISE_SWAP (train_agents_pairwise_swap, :1283-1364): u0: n = c(2, nmax); n positions ~ U(-7.5, 7.5)^2 (2 draws per
+ *     attempt), each after the first >= 2.0 m from the earlier ones; Fisher-Yates shuffle as random.shuffle (i = n-1 .. 1:
+ *     j = (int)(u(k) * (i + 1)), swap i, j); slots 2p / 2p+1 swap positions p's pair; n_agents = 2 * (n / 2).  Policy draws,
+ *     rule, coop and ego dynamics as SWAP_CIRCLE.
+ *   RANDOM_POSITIONS (:1365-1463): exactly cagym_generate_scenarios with n_min = 2 (nmax when fixed_count), n_max = nmax,
+ *     side 7.5, min_travel 4, min_sep 1.5, radius 0.5, pref_speed 1, coop 0.5, ego dynamics as SWAP_CIRCLE; its draws are
+ *     keyed and ordered as there, so both entries give bit-identical pools.  Rule: RVO / NonCooperative at p 0.5 (:1417).
+ *   STAGE_1 / STAGE_2 (train_stage_1 :2359-2463 / train_stage_2 :2464-2572): u0: n_obst = c(lo, hi).  Per
+ *     rectangle: u < 0.5 square of side U(1, 3) / U(1, 2), else wall wx = U(1, 4), wy = wx > 2 ? U(1, 2) : U(3, 4); then per
+ *     attempt the upper corner (xu, yu) ~ U(-4, 6)^2 / U(-8, 10)^2, (xl, yl) = (xu, yu) - size, until no overlap with an earlier
+ *     rectangle (is_shape_valid, :150-170: xl' >= xu || xl >= xu' || yu' <= yl || yu <= yl').  Ego: distance U(6, 8) /
+ *     U(8, 10), angle U(-pi, pi), start s, goal -s, both clear of every rectangle (is_pose_valid_with_obstacles, :135-148:
+ *     x >= xu + 1 || y >= yu + 1 || x <= xl - 1 || y <= yl - 1).  Then u: others = c(1, max(number_of_agents - 1, 1)),
+ *     each placed as the ego and also >= 1.5 m from every earlier start and goal.  Then one policy draw per other agent.
+ *     Rule: every other agent RVO (p_b = 0: other_agents_policy with no mix); coop 1.0; dynamics as given (the reference's
+ *     defaults are FirstOrder for the ego, Unicycle for the others).  [lo, hi] is the reference's range, (0, 4) / (2, 10),
+ *     narrowed by the caller's bounds: lo = max(ref, n_obst_min), hi = min(ref, n_obst_max), a bound < 0 being none - so in
+ *     a mixture n_obst_max caps stage 2 without touching stage 1.  Rectangles: obstacles [S, max_obstacles, 4] = (xl, yl, xu, yu), zero beyond n_obst; their
+ *     RVO prep rows (as cagym_set_scenarios computes them, bit for bit) and rasters are built on the device.
+ * kinds_mask: bit (1 << CAGYM_GEN_*) per kind; with more than one bit every scenario draws its kind uniformly among them
+ * (the np.random.randint stage of _init_agents, env.py:432-438) from a stream of its own, u(seed ^ 0xD1B54A32D192ED03, s, 0),
+ * so a single kind draws nothing for it.  Refused (CAGYM_E_INVALID): an empty or unknown mask, nmax > max_agents, n_obst_max above the
+ * handle's max_obstacles or below n_obst_min, a stage kind of the mask whose hi exceeds max_obstacles (it is never clamped:
+ * capping it, e.g. to 6 for RVO agents at max_agents 4, is the caller's choice) or whose [lo, hi] is empty, ids out of range, max_tries < 1, p_b outside [0, 1].  With RVO agents possible among rectangles the
+ * handle's max_obstacles is checked as cagym_set_scenarios checks it (same codes and messages).  A refused call leaves the
+ * handle as it was; an accepted one commits the handle state as cagym_set_scenarios does (IG robot counts: unknown). */
+enum { CAGYM_GEN_SWAP_CIRCLE = 0, CAGYM_GEN_PAIRWISE_SWAP = 1, CAGYM_GEN_RANDOM_POSITIONS = 2, CAGYM_GEN_STAGE_1 = 3,
+       CAGYM_GEN_STAGE_2 = 4, CAGYM_GEN_NKINDS = 5 };
+typedef struct cagym_gen2_params {
+    uint64_t seed;
+    uint32_t kinds_mask;
+    int32_t number_of_agents, fixed_count;
+    int32_t ego_policy, ego_dynamics;
+    int32_t override_policies, policy_a, policy_b, other_dynamics;
+    int32_t n_obst_min, n_obst_max; /* bounds on the stage kinds' rectangle counts; < 0: none (the reference's range) */
+    int32_t max_tries;
+    double p_b;
+} cagym_gen2_params;
+int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream);
+
+/* zero-copy DEVICE views of the pool's rectangles: obst [S, max_obstacles, 4] (xl, yl, xu, yu), n_obst [S]; both NULL when
+ * max_obstacles is 0 */
+int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst);
+
 /* ---- Dec-MCTS planning step on the device ------------------------------------------------
  * ig_mcts.find_next_action for every IG robot of every world (ig_mcts.py:79-109) with the tree of
  * pydecmcts/DecMCTS.py:92-360 kept on the device: per cycle and robot, Ntree times { sample one communicated
