@@ -4,8 +4,10 @@ The library is linked against the HIP runtime PyTorch-ROCm bundles (torch/lib/li
 SONAME libamdhip64.so.7) so that torch streams and device pointers are valid inside it.
 
 Translation units (compiled in parallel, objects cached under csrc/build/ by source + flag hash):
-  cagym_api.hip                      the C ABI, generation-1 kernels, reset / laserscan / raster / generator, GA3C, IG, Dec-MCTS
-  cagym_k3_tu.hip x 12               one per generation-3 specialisation (cagym_launch3.h: CAGYM_K3_SPECS x OBST)
+  cagym_api.hip                      the C ABI and every kernel it launches itself: generation 1 + reset (cagym_gen1.h), laserscan /
+                                     occupancy grid / raster (cagym_sensors.h), generators, GA3C, IG, Dec-MCTS (HEADERS)
+  cagym_k3_tu.hip x 12               one per generation-3 specialisation (cagym_launch3.h: CAGYM_K3_SPECS x OBST); they see
+                                     K3_HEADERS only
 """
 import concurrent.futures
 import functools
@@ -19,9 +21,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libcagym_hip.so")
-K3_HEADERS = ["cagym_device.h", "cagym_trace.h", "cagym_spin.h", "cagym_orca.h", "cagym_kernels.h", "cagym_kernels3.h", "cagym_split3.h", "cagym_launch3.h",
+# what the generation-3 units include, transitively: an edit of any other header leaves their twelve objects fresh
+K3_HEADERS = ["cagym_device.h", "cagym_trace.h", "cagym_spin.h", "cagym_orca.h", "cagym_kernels3.h", "cagym_split3.h", "cagym_launch3.h",
               "../../include/cagym.h"]
-HEADERS = K3_HEADERS + ["cagym_ig.h", "cagym_ga3c.h", "cagym_ga3c16.h", "cagym_gen.h", "cagym_gen2.h", "cagym_dmcts.h"]
+HEADERS = K3_HEADERS + ["cagym_gen1.h", "cagym_sensors.h", "cagym_ig.h", "cagym_ga3c_state.h", "cagym_ga3c.h", "cagym_ga3c16.h", "cagym_gen.h", "cagym_gen2.h",
+                        "cagym_dmcts.h"]
 
 
 def _k3_specs():
@@ -91,6 +95,11 @@ def _stale(extra):
     return out
 
 
+def _max_jobs():
+    """MAX_JOBS when it is set (a shared host: os.cpu_count() is the whole machine's), else the CPU count"""
+    return max(1, int(os.environ.get("MAX_JOBS") or os.cpu_count() or 2))
+
+
 def needs_build(extra=()):
     return not os.path.exists(LIB) or bool(_stale(list(extra)))
 
@@ -114,7 +123,7 @@ def build(force=False, verbose=False, extra=(), jobs=None):
     todo = [(o, s, d, g) for (o, s, d, _h) in units() for g in [_digest(s, d, _h, extra)]] if force else _stale(extra)
     if not todo and os.path.exists(LIB):
         return LIB
-    jobs = jobs or min(len(todo), max(1, (os.cpu_count() or 2)))
+    jobs = jobs or min(len(todo), _max_jobs())
     if todo:
         with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
             list(ex.map(_compile, [(o, s, d, g, extra, verbose) for (o, s, d, g) in todo]))
@@ -165,7 +174,7 @@ def build_alt(tag, extra, only):
             objs.append(out)
         else:
             objs.append(os.path.join(OBJ, obj))
-    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 2))) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), _max_jobs()))) as ex:
         list(ex.map(subprocess.check_call, jobs))
     lib = os.path.join(CSRC, "libcagym_hip_%s.so" % tag)
     tl = _torch_lib_dir()

@@ -9,7 +9,8 @@
 #include <vector>
 
 #include "../../include/cagym.h"
-#include "cagym_kernels.h"
+#include "cagym_gen1.h"
+#include "cagym_sensors.h"
 #include "cagym_kernels3.h"  // LDS layout helpers; the kernels themselves are instantiated in the cagym_k3_tu.hip units
 #include "cagym_split3.h"
 #include "cagym_launch3.h"
@@ -86,10 +87,25 @@ struct DeviceGuard {
         if (switched) (void)hipSetDevice(prev);
     }
 };
-#define DEVGUARD(e)                                                                                        \
+// The prologue of a launching entry point is two statements.  ENTRY* turns `void* env` into `Env* e` and checks the handle and the
+// state the call needs; ON_DEVICE makes the handle's device current and refuses after a void launch (device_status).  A function's
+// own argument checks stay where they always were, before or after ON_DEVICE: which of two errors wins is part of the ABI.
+#define ENTRY_IF(e, env, state_ok, msg)                                \
+    Env* e = reinterpret_cast<Env*>(env);                              \
+    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");         \
+    if (!(state_ok)) return fail(e, CAGYM_E_STATE, msg)
+#define ENTRY(e, env) ENTRY_IF(e, env, true, "")
+#define ENTRY_POOL(e, env, name) ENTRY_IF(e, env, e->scenarios_set, name " before cagym_set_scenarios")
+#define ENTRY_IG(e, env, name) ENTRY_IF(e, env, e->ig_ready, name " before cagym_ig_init")
+#define ON_DEVICE(e)                                                                                       \
     DeviceGuard _guard((e)->cfg.device);                                                                   \
     if (_guard.status != hipSuccess) return fail(e, CAGYM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_guard.status)); \
     if (int _rc = device_status(e)) return _rc
+// ... of a call that moves the state a pending cagym_step_begin solved for: its velocities must not be consumed any more.
+// (The scenario setters clear `begun` themselves, on success only: a refused call leaves the handle as it was.)
+#define ON_DEVICE_VOIDS_BEGUN(e) \
+    ON_DEVICE(e);                \
+    (e)->begun = false
 
 // A kernel whose bounded intra-workgroup wait expired (cagym_spin.h) wrote its CAGYM_DEVERR_* code into the handle's host-mapped
 // status word: the launches since then produced void results.  Every launching entry point refuses to go on (the word is sticky
@@ -115,12 +131,14 @@ int dalloc(Env* e, T** p, size_t n) {
     return CAGYM_OK;
 }
 
-CagymOut to_out(const cagym_outputs* o) {
+// the kernels' view of the caller's outputs; a handle without a LaserScan sensor passes no laserscan pointer on
+// (scan_as_given: cagym_reset hands k_reset the caller's pointer whatever the handle says, only its follow-up scan is conditional)
+CagymOut to_out(const Env* e, const cagym_outputs* o, bool scan_as_given = false) {
     CagymOut r{};
     if (o) {
         r.obs_oas = o->obs_oas;
         r.obs_ego = o->obs_ego;
-        r.laserscan = o->laserscan;
+        r.laserscan = (e->cfg.laserscan || scan_as_given) ? o->laserscan : nullptr;
         r.reward = o->reward;
         r.flags = o->flags;
         r.game_over = o->game_over;
@@ -141,14 +159,14 @@ CagymOut to_out(const cagym_outputs* o) {
 struct Spec2 {
     int nt, mt, wpw;
 };
-inline Spec2 spec2(const Env* e) {
-    const int M = e->cfg.max_agents;
-    if (M == 10) return {256, 10, e->wpw10};
+inline Spec2 spec2(int M, int wpw10) {
+    if (M == 10) return {256, 10, wpw10};
     if (M == 4) return {256, 4, 0};
     if (M == 20) return {NT20, 20, WPW20};
     if (M <= 12) return {256, 0, 0};
     return {512, 0, 0};
 }
+inline Spec2 spec2(const Env* e) { return spec2(e->cfg.max_agents, e->wpw10); }
 inline int wpw_spec(const Env* e) { return spec2(e).wpw; }
 inline int n_wg2(const Env* e) {
     const int M = e->cfg.max_agents;
@@ -156,10 +174,11 @@ inline int n_wg2(const Env* e) {
     return (e->cfg.n_worlds + wpw - 1) / wpw;
 }
 // obst: the OBST instantiation (worlds may hold rectangles); lines: RVO agents among them (obstacle half-plane rows)
-inline size_t lds3_bytes(const Env* e, bool obst, bool lines) {
-    const int M = e->cfg.max_agents;
-    return cagym_lds3_bytes(M, cagym_as(M, wpw_spec(e)), spec2(e).nt, (obst && lines) ? 2 * e->cfg.max_obstacles : 0, cagym_lpl3(spec2(e).mt, obst), obst, spec2(e).mt);
+inline size_t lds3_bytes(const cagym_config& cfg, const Spec2 sp, bool obst, bool lines) {
+    const int M = cfg.max_agents;
+    return cagym_lds3_bytes(M, cagym_as(M, sp.wpw), sp.nt, (obst && lines) ? 2 * cfg.max_obstacles : 0, cagym_lpl3(sp.mt, obst), obst, sp.mt);
 }
+inline size_t lds3_bytes(const Env* e, bool obst, bool lines) { return lds3_bytes(e->cfg, spec2(e), obst, lines); }
 inline bool has_map(const Env* e) { return e->cfg.max_obstacles > 0; }
 inline size_t scan_bytes(const Env* e) { return (size_t)e->cfg.n_worlds * e->cfg.max_agents * 16 * sizeof(float); }
 inline size_t lds3_bytes(const Env* e) { return lds3_bytes(e, has_map(e), e->obst_rvo != 0); }
@@ -197,15 +216,37 @@ inline const K3Entry* k3_entry(const Env* e) {
         if (r.nt == sp.nt && r.mt == sp.mt && r.wp == sp.wpw) return &r;
     return nullptr;
 }
-// one generation-3 launch of the handle's specialisation (free-space or OBST instantiation)
-inline void launch3(const Env* e, bool rollout, bool auto_reset, const float* ext, int n_steps, const CagymOut& o, hipStream_t st) {
+// one generation-3 launch of the handle's specialisation (free-space or OBST instantiation): the fused step or roll-out
+// (K3_HALF_NONE) or one half of the split step, which differ in their LDS footprint and in who solves the RVO agents
+inline void launch3(const Env* e, int half, bool rollout, bool auto_reset, const float* ext, int n_steps, const CagymOut& o, hipStream_t st) {
+    const int M = e->cfg.max_agents, as = cagym_as(M, wpw_spec(e));
     K3Launch L;
-    L.D = e->D; L.ext = ext; L.out = o; L.n_steps = n_steps; L.any_rvo = e->any_rvo; L.rollout = rollout; L.auto_reset = auto_reset;
-    L.grid = (unsigned)n_wg2(e); L.lds = rollout ? lds3_bytes(e) : lds3_step_bytes(e); L.stream = st;
+    L.D = e->D; L.half = half; L.ext = ext; L.out = o; L.n_steps = n_steps; L.rollout = rollout; L.auto_reset = auto_reset;
+    L.grid = (unsigned)n_wg2(e); L.stream = st;
+    if (half == K3_HALF_PRE) {  // launched only when the pool has RVO agents
+        L.any_rvo = 1;
+        L.lds = cagym_lds3_pre_bytes(M, as, spec2(e).nt, has_map(e) ? e->D.ko : 0);
+        if (L.lds < e->pre_lds_min && e->pre_lds_min <= 64 * 1024) L.lds = e->pre_lds_min;
+    } else if (half == K3_HALF_POST) {  // the velocities are in CagymDev::lp_vel
+        L.any_rvo = 0;
+        L.lds = cagym_lds3_post_bytes(M, as, has_map(e) ? e->D.ko / 2 : 0, has_map(e));
+    } else {
+        L.any_rvo = e->any_rvo;
+        L.lds = rollout ? lds3_bytes(e) : lds3_step_bytes(e);
 #ifdef CAGYM_DIAG_LDS_PAD  // occupancy experiments only (tools/README.md): unused LDS bytes on top, to force fewer workgroups per CU
-    if (const char* pad = getenv("CAGYM_LDS_PAD")) L.lds += (size_t)atoi(pad);
+        if (const char* pad = getenv("CAGYM_LDS_PAD")) L.lds += (size_t)atoi(pad);
 #endif
+    }
     k3_entry(e)->launch[has_map(e) ? 1 : 0](L);
+}
+// A handle without rectangles runs the free-space kernels, which write no laserscan: every beam of an empty map reads 0.0
+// (LaserScanSensor.py:27-58 on an all-free Map), in all n_steps slices of a roll-out.  Generation 1 scans through cagym_laserscan.
+// (HIPCHK's message quotes the call, so both spellings are kept.)
+inline int fill_empty_scan(Env* e, const CagymOut& o, hipStream_t st, int n_steps = 0) {
+    if (e->generation != 3 || has_map(e) || !o.laserscan) return CAGYM_OK;
+    if (n_steps) HIPCHK(e, hipMemsetAsync(o.laserscan, 0, (size_t)n_steps * scan_bytes(e), st));
+    else HIPCHK(e, hipMemsetAsync(o.laserscan, 0, scan_bytes(e), st));
+    return CAGYM_OK;
 }
 
 }  // namespace
@@ -219,9 +260,8 @@ const char* cagym_last_error(void* env) {
     return e ? e->err.c_str() : g_last_error.c_str();
 }
 
-int cagym_create(const cagym_config* cfg, void** env_out) {
-    if (!cfg || !env_out) return fail(nullptr, CAGYM_E_INVALID, "cagym_create: null argument");
-    *env_out = nullptr;
+// ---- cagym_create, step by step (every step reports through fail(); cagym_create destroys the half-made handle on the first error) ----
+static int validate_config(const cagym_config* cfg) {
     if (cfg->n_worlds < 1) return fail(nullptr, CAGYM_E_INVALID, "n_worlds must be >= 1");
     if (cfg->max_agents < 2 || cfg->max_agents > 32)
         return fail(nullptr, CAGYM_E_UNSUPPORTED, "max_agents must be in [2, 32] (a world may not straddle a wavefront)");
@@ -234,13 +274,12 @@ int cagym_create(const cagym_config* cfg, void** env_out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(nullptr, CAGYM_E_NODEVICE, "no HIP device: libcagym_hip has no CPU fallback");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, CAGYM_E_INVALID, "device ordinal out of range");
-    Env* e = new Env();
-    e->cfg = *cfg;
-    DeviceGuard guard(cfg->device);
-    if (guard.status != hipSuccess) {
-        delete e;
-        return fail(nullptr, CAGYM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.status));
-    }
+    return CAGYM_OK;
+}
+
+// the scenario pool, the per-agent and per-world state and the GA3C words, zero-filled
+static int alloc_state(Env* e) {
+    const cagym_config* cfg = &e->cfg;
     CagymDev& D = e->D;
     memset(&D, 0, sizeof(D));
     const size_t N = cfg->n_worlds, M = cfg->max_agents, S = cfg->n_scenarios, NM = N * M, SM = S * M;
@@ -250,11 +289,10 @@ int cagym_create(const cagym_config* cfg, void** env_out) {
     D.inv_dt = 1.0 / cfg->dt;
     D.maxnb = cfg->rvo_max_neighbors > 0 ? cfg->rvo_max_neighbors : (int)M;  // RVOPolicy.py:15: Config.MAX_NUM_AGENTS_IN_ENVIRONMENT
     if (D.maxnb > (int)M - 1) D.maxnb = (int)M - 1;                            // there are at most M - 1 other agents
-    int rc = CAGYM_OK;
     double* d6 = nullptr; double* dcoop = nullptr;
     int32_t *dpol = nullptr, *ddyn = nullptr, *dna = nullptr, *dno = nullptr;
     uint32_t* dmap = nullptr;
-#define A(call) if ((rc = (call)) != CAGYM_OK) { cagym_destroy(e); return rc; }
+#define A(call) if (int rc = (call)) return rc;
     A(dalloc(e, &d6, SM * 6)); A(dalloc(e, &e->sc_heading_buf, SM)); A(dalloc(e, &dcoop, SM));
     A(dalloc(e, &dpol, SM)); A(dalloc(e, &ddyn, SM)); A(dalloc(e, &dna, S)); A(dalloc(e, &dno, S));
     if (cfg->max_obstacles > 0) {
@@ -278,74 +316,100 @@ int cagym_create(const cagym_config* cfg, void** env_out) {
     A(dalloc(e, &e->ga3c_ctr, 4));  // at creation: cagym_ga3c_act may run inside a stream capture (no allocation there)
     A(dalloc(e, &e->ga3c_packed, GA16_PACKED_BYTES));
 #undef A
-    {   // the kernels' status word: pinned host memory mapped into the device's address space (written only when a bounded wait expires)
-        void* hp = nullptr;
-        void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            if (hp) (void)hipHostFree(hp);
-            cagym_destroy(e);
-            return fail(nullptr, CAGYM_E_NOMEM, "hipHostMalloc of the device status word failed");
-        }
-        memset(hp, 0, 64);
-        e->status_host = reinterpret_cast<int32_t*>(hp);
-        D.dev_status = reinterpret_cast<int32_t*>(dp);
+    return CAGYM_OK;
+}
+
+// the kernels' status word: pinned host memory mapped into the device's address space (written only when a bounded wait expires)
+static int alloc_status_word(Env* e) {
+    void* hp = nullptr;
+    void* dp = nullptr;
+    if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
+        if (hp) (void)hipHostFree(hp);
+        return fail(nullptr, CAGYM_E_NOMEM, "hipHostMalloc of the device status word failed");
     }
-    e->err.clear();
-    size_t lds = cagym_lds_bytes((int)M);
-    if (lds > 160 * 1024) { cagym_destroy(e); return fail(nullptr, CAGYM_E_UNSUPPORTED, "LDS budget exceeded"); }
-    // > 64 KiB of dynamic LDS needs the attribute raised
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_reset), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    {
-        const char* g = getenv("CAGYM_KERNEL");
-        if (g && (!strcmp(g, "v1") || !strcmp(g, "1"))) e->generation = 1;
-        else if (g && g[0] && strcmp(g, "v3") && strcmp(g, "3")) {  // a retired or misspelt generation must not silently run the default
-            cagym_destroy(e);
-            return fail(nullptr, CAGYM_E_INVALID, std::string("CAGYM_KERNEL=") + g + ": unknown kernel generation (v1 or v3)");
-        }
-        {
-            hipDeviceProp_t prop;
-            int cus = 256;
-            if (hipGetDeviceProperties(&prop, e->cfg.device) == hipSuccess && prop.multiProcessorCount > 0)
-                cus = prop.multiProcessorCount;
-            e->wpw10 = (e->cfg.n_worlds + 3) / 4 <= 4 * cus ? 4 : 5;  // 4 workgroups per CU fit (128 VGPRs; 30.9 KB of LDS with 4 worlds, 37.7 KB with 5)
-            if (has_map(e) && e->wpw10 == 5) {
-                // worlds with rectangles (OBST instantiation, 135 VGPRs: at most 3 workgroups per CU): 4 worlds per workgroup when their
-                // smaller LDS footprint buys a workgroup per CU (cfg4: 53.4 KB -> 3 per CU, 65.9 KB with 5 worlds -> 2;
-                // profiles/r3/cfg4_occupancy_ab.txt)
-                auto per_cu = [&](int wpw) {
-                    e->wpw10 = wpw;
-                    size_t b = lds3_bytes(e, true, true);
-                    if (b > 160 * 1024) b = lds3_bytes(e, true, false);
-                    const int n = (int)((size_t)160 * 1024 / b);
-                    return n < 3 ? n : 3;
-                };
-                const int n4 = per_cu(4), n5 = per_cu(5);
-                e->wpw10 = n4 > n5 ? 4 : 5;
-            }
-            if (const char* pl = getenv("CAGYM_PRE_LDS")) e->pre_lds_min = (size_t)atol(pl);
-            const char* w = getenv("CAGYM_WPW10");  // diagnostics
-            if (w && (w[0] == '4' || w[0] == '5')) e->wpw10 = w[0] - '0';
-        }
-        int lds3 = (int)lds3_bytes(e, false, false), lds3_obst = (int)lds3_bytes(e, true, true);
-        if (lds3_obst > 160 * 1024) lds3_obst = (int)lds3_bytes(e, true, false);  // too many rectangles for RVO agents: refused at set_scenarios
-        if (e->generation == 3 && lds3 > 160 * 1024) e->generation = 1;
-        // the free-space kernels keep the neighbour keys in the LP scratch (cagym_dsq_aliased): it must hold them
-        if (e->generation == 3 && cagym_dsq_aliased(false, spec2(e).mt) &&
-            (size_t)cagym_as((int)M, wpw_spec(e)) * cagym_mp((int)M) * 8 > (size_t)cagym_lpl3(spec2(e).mt, false) * spec2(e).nt * 16) {
-            cagym_destroy(e);
-            return fail(nullptr, CAGYM_E_UNSUPPORTED, "neighbour keys do not fit the LP scratch of this specialisation");
-        }
-        if (!k3_entry(e)) { cagym_destroy(e); return fail(nullptr, CAGYM_E_UNSUPPORTED, "no kernel specialisation for this shape"); }
+    memset(hp, 0, 64);
+    e->status_host = reinterpret_cast<int32_t*>(hp);
+    e->D.dev_status = reinterpret_cast<int32_t*>(dp);
+    return CAGYM_OK;
+}
+
+// Worlds per workgroup of the M = 10 kernels: 4 while 4 workgroups per CU hold the whole launch (128 VGPRs; 30.9 KB of LDS with 4
+// worlds, 37.7 KB with 5), else 5.  A handle with rectangles (OBST instantiation) that would take 5 takes 4 when the smaller
+// footprint buys a workgroup per CU.  What is priced: lds_obst4 / lds_obst5, the ROLL-OUT layout's bytes with 4 / 5 worlds
+// (lds3_bytes with obstacle half-plane rows, without them when those exceed the CU's 160 KB), and at most 3 workgroups per CU
+// are counted (cfg4: 53.4 KB -> 3 per CU, 65.9 KB with 5 worlds -> 2; profiles/r3/cfg4_occupancy_ab.txt).
+// override: CAGYM_WPW10 = 4 | 5 (diagnostics) wins.
+static int choose_wpw10(const cagym_config& cfg, int cus, const char* override, size_t lds_obst4, size_t lds_obst5) {
+    if (override && (override[0] == '4' || override[0] == '5')) return override[0] - '0';
+    const int wpw = (cfg.n_worlds + 3) / 4 <= 4 * cus ? 4 : 5;
+    if (cfg.max_obstacles <= 0 || wpw == 4) return wpw;
+    auto per_cu = [](size_t b) {
+        const int n = (int)((size_t)160 * 1024 / b);
+        return n < 3 ? n : 3;
+    };
+    return per_cu(lds_obst4) > per_cu(lds_obst5) ? 4 : 5;
+}
+
+// the kernel generation (CAGYM_KERNEL, or 1 when generation 3 does not fit the LDS), worlds per workgroup and CAGYM_PRE_LDS
+static int choose_kernels(Env* e) {
+    const int M = e->cfg.max_agents;
+    if (cagym_lds_bytes(M) > 160 * 1024) return fail(nullptr, CAGYM_E_UNSUPPORTED, "LDS budget exceeded");
+    const char* g = getenv("CAGYM_KERNEL");
+    if (g && (!strcmp(g, "v1") || !strcmp(g, "1"))) e->generation = 1;
+    else if (g && g[0] && strcmp(g, "v3") && strcmp(g, "3"))  // a retired or misspelt generation must not silently run the default
+        return fail(nullptr, CAGYM_E_INVALID, std::string("CAGYM_KERNEL=") + g + ": unknown kernel generation (v1 or v3)");
+    hipDeviceProp_t prop;
+    int cus = 256;
+    if (hipGetDeviceProperties(&prop, e->cfg.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    auto lds_obst = [&](int wpw) {
+        const size_t b = lds3_bytes(e->cfg, spec2(M, wpw), true, true);
+        return b > 160 * 1024 ? lds3_bytes(e->cfg, spec2(M, wpw), true, false) : b;
+    };
+    e->wpw10 = choose_wpw10(e->cfg, cus, getenv("CAGYM_WPW10"), lds_obst(4), lds_obst(5));
+    if (const char* pl = getenv("CAGYM_PRE_LDS")) e->pre_lds_min = (size_t)atol(pl);
+    if (e->generation == 3 && lds3_bytes(e, false, false) > 160 * 1024) e->generation = 1;
+    // the free-space kernels keep the neighbour keys in the LP scratch (cagym_dsq_aliased): it must hold them
+    if (e->generation == 3 && cagym_dsq_aliased(false, spec2(e).mt) &&
+        (size_t)cagym_as(M, wpw_spec(e)) * cagym_mp(M) * 8 > (size_t)cagym_lpl3(spec2(e).mt, false) * spec2(e).nt * 16)
+        return fail(nullptr, CAGYM_E_UNSUPPORTED, "neighbour keys do not fit the LP scratch of this specialisation");
+    if (!k3_entry(e)) return fail(nullptr, CAGYM_E_UNSUPPORTED, "no kernel specialisation for this shape");
+    return CAGYM_OK;
+}
+
+// > 64 KiB of dynamic LDS needs the attribute raised
+static void raise_lds_attributes(Env* e) {
+    const int lds = (int)cagym_lds_bytes(e->cfg.max_agents);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_step), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_reset), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    int lds3 = (int)lds3_bytes(e, false, false), lds3_obst = (int)lds3_bytes(e, true, true);
+    if (lds3_obst > 160 * 1024) lds3_obst = (int)lds3_bytes(e, true, false);  // too many rectangles for RVO agents: refused at set_scenarios
 #ifdef CAGYM_DIAG_LDS_PAD
-        if (const char* pad = getenv("CAGYM_LDS_PAD")) { lds3 += atoi(pad); lds3_obst += atoi(pad); }
+    if (const char* pad = getenv("CAGYM_LDS_PAD")) { lds3 += atoi(pad); lds3_obst += atoi(pad); }
 #endif
-        k3_entry(e)->setattr[0](lds3);
-        if (lds3_obst <= 160 * 1024) k3_entry(e)->setattr[1](lds3_obst);
-    }
+    k3_entry(e)->setattr[0](lds3);
+    if (lds3_obst <= 160 * 1024) k3_entry(e)->setattr[1](lds3_obst);
     (void)hipGetLastError();
+}
+
+int cagym_create(const cagym_config* cfg, void** env_out) {
+    if (!cfg || !env_out) return fail(nullptr, CAGYM_E_INVALID, "cagym_create: null argument");
+    *env_out = nullptr;
+    if (int rc = validate_config(cfg)) return rc;
+    Env* e = new Env();
+    e->cfg = *cfg;
+    DeviceGuard guard(cfg->device);
+    int rc = guard.status == hipSuccess ? CAGYM_OK : fail(nullptr, CAGYM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.status));
+    if (!rc) rc = alloc_state(e);
+    if (!rc) rc = alloc_status_word(e);
+    if (!rc) rc = choose_kernels(e);
+    if (rc) {
+        cagym_destroy(e);
+        return rc;
+    }
+    raise_lds_attributes(e);
+    e->err.clear();
     *env_out = e;
     return CAGYM_OK;
 }
@@ -377,11 +441,10 @@ static int check_obst_rvo_capacity(Env* e) {
 int cagym_set_scenarios(void* env, const double* agents6, const double* heading0, const int32_t* policy_id,
                         const int32_t* dynamics_id, const int32_t* n_agents, const double* coop,
                         const double* obstacles, const int32_t* n_obst, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!agents6 || !policy_id || !dynamics_id) return fail(e, CAGYM_E_INVALID, "agents6 / policy_id / dynamics_id are required");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DEVGUARD(e);
+    ON_DEVICE(e);
     const size_t S = e->cfg.n_scenarios, M = e->cfg.max_agents, SM = S * M;
     // validate ids on the host: the kernels index switch tables with them
     for (size_t k = 0; k < SM; k++) {
@@ -492,9 +555,25 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     return CAGYM_OK;
 }
 
+// the handle's scenario pool as the generator kernels write it
+static GenDev gen_dev(const Env* e) {
+    const CagymDev& D = e->D;
+    GenDev G;
+    G.agents6 = const_cast<double*>(D.sc_agents6);
+    G.policy = const_cast<int32_t*>(D.sc_policy);
+    G.dyn = const_cast<int32_t*>(D.sc_dyn);
+    G.nagents = const_cast<int32_t*>(D.sc_nagents);
+    G.coop = const_cast<double*>(D.sc_coop);
+    G.nobst = const_cast<int32_t*>(D.sc_nobst);
+    G.S = e->cfg.n_scenarios;
+    G.M = e->cfg.max_agents;
+    return G;
+}
+// Env::gen_failed, allocated by the first generator call
+static int gen_failed_word(Env* e) { return e->gen_failed ? CAGYM_OK : dalloc(e, &e->gen_failed, 1); }
+
 int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t* n_failed_host, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!params) return fail(e, CAGYM_E_INVALID, "null params");
     const cagym_gen_params& P = *params;
     const int M = e->cfg.max_agents;
@@ -506,21 +585,10 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
         return fail(e, CAGYM_E_INVALID, "dynamics id out of range");
     if (P.max_tries < 1 || !(P.side > 0) || !(P.p_b >= 0 && P.p_b <= 1)) return fail(e, CAGYM_E_INVALID, "bad generator parameters");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DEVGUARD(e);
+    ON_DEVICE(e);
     CagymDev& D = e->D;
-    GenDev G;
-    G.agents6 = const_cast<double*>(D.sc_agents6);
-    G.policy = const_cast<int32_t*>(D.sc_policy);
-    G.dyn = const_cast<int32_t*>(D.sc_dyn);
-    G.nagents = const_cast<int32_t*>(D.sc_nagents);
-    G.coop = const_cast<double*>(D.sc_coop);
-    G.nobst = const_cast<int32_t*>(D.sc_nobst);
-    G.S = e->cfg.n_scenarios;
-    G.M = M;
-    if (!e->gen_failed) {
-        int rcf = dalloc(e, &e->gen_failed, 1);
-        if (rcf != CAGYM_OK) return rcf;
-    }
+    const GenDev G = gen_dev(e);
+    if (int rc = gen_failed_word(e)) return rc;
     int32_t* d_failed = e->gen_failed;
     HIPCHK(e, hipMemsetAsync(d_failed, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_generate_scenarios, dim3((G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
@@ -546,8 +614,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
 }
 
 int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!params) return fail(e, CAGYM_E_INVALID, "null params");
     const cagym_gen2_params& P = *params;
     const int M = e->cfg.max_agents, K = e->cfg.max_obstacles;
@@ -596,24 +663,14 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
         if (rc != CAGYM_OK) return rc;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DEVGUARD(e);
+    ON_DEVICE(e);
     CagymDev& D = e->D;
     Gen2Dev G;
-    G.G.agents6 = const_cast<double*>(D.sc_agents6);
-    G.G.policy = const_cast<int32_t*>(D.sc_policy);
-    G.G.dyn = const_cast<int32_t*>(D.sc_dyn);
-    G.G.nagents = const_cast<int32_t*>(D.sc_nagents);
-    G.G.coop = const_cast<double*>(D.sc_coop);
-    G.G.nobst = const_cast<int32_t*>(D.sc_nobst);
-    G.G.S = e->cfg.n_scenarios;
-    G.G.M = M;
+    G.G = gen_dev(e);
     G.obst = e->sc_obst;
     G.prep = reinterpret_cast<float*>(e->sc_obst_prep);
     G.K = K;
-    if (!e->gen_failed) {
-        int rcf = dalloc(e, &e->gen_failed, 1);
-        if (rcf != CAGYM_OK) return rcf;
-    }
+    if (int rc = gen_failed_word(e)) return rc;
     int32_t* d_failed = e->gen_failed;
     HIPCHK(e, hipMemsetAsync(d_failed, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
@@ -639,8 +696,7 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
 }
 
 int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!obst || !n_obst) return fail(e, CAGYM_E_INVALID, "null out");
     *obst = e->cfg.max_obstacles > 0 ? e->sc_obst : nullptr;
     *n_obst = e->cfg.max_obstacles > 0 ? e->D.sc_nobst : nullptr;
@@ -648,8 +704,7 @@ int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst) 
 }
 
 int cagym_get_scenarios(void* env, cagym_scenario_ptrs* out) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!out) return fail(e, CAGYM_E_INVALID, "null out");
     out->agents6 = e->D.sc_agents6;
     out->policy = e->D.sc_policy;
@@ -660,13 +715,10 @@ int cagym_get_scenarios(void* env, cagym_scenario_ptrs* out) {
 }
 
 int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const cagym_outputs* out, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_reset before cagym_set_scenarios");
-    DEVGUARD(e);
+    ENTRY_POOL(e, env, "cagym_reset");
+    ON_DEVICE_VOIDS_BEGUN(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    CagymOut o = to_out(out);
-    e->begun = false;
+    const CagymOut o = to_out(e, out, true);
     hipLaunchKernelGGL(k_reset, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, world_mask,
                        advance_episode, o);
     HIPCHK(e, hipGetLastError());
@@ -675,111 +727,66 @@ int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const
 }
 
 int cagym_step(void* env, const float* ext_actions, const cagym_outputs* out, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_step before cagym_set_scenarios");
-    DEVGUARD(e);
-    e->begun = false;
+    ENTRY_POOL(e, env, "cagym_step");
+    ON_DEVICE_VOIDS_BEGUN(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    CagymOut o = to_out(out);
-    if (!e->cfg.laserscan) o.laserscan = nullptr;
-    if (e->generation == 3) {
-        launch3(e, false, false, ext_actions, 1, o, st);
-    } else
-    hipLaunchKernelGGL(k_step, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, ext_actions, o);
+    const CagymOut o = to_out(e, out);
+    if (e->generation == 3) launch3(e, K3_HALF_NONE, false, false, ext_actions, 1, o, st);
+    else hipLaunchKernelGGL(k_step, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, ext_actions, o);
     HIPCHK(e, hipGetLastError());
-    if (e->generation != 3 && e->cfg.laserscan && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);  // generation 3 scans in-kernel
-    // ... in its OBST instantiation; a handle without rectangles runs the free-space kernels: every beam of an empty map reads 0.0
-    // (LaserScanSensor.py:27-58 on an all-free Map)
-    if (e->generation == 3 && !has_map(e) && o.laserscan) HIPCHK(e, hipMemsetAsync(o.laserscan, 0, scan_bytes(e), st));
-    return CAGYM_OK;
+    if (e->generation != 3 && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);  // generation 3 scans in-kernel ...
+    return fill_empty_scan(e, o, st);                                                         // ... in its OBST instantiation
 }
 
 int cagym_step_autoreset(void* env, const float* ext_actions, const cagym_outputs* out, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_step_autoreset before cagym_set_scenarios");
-    DEVGUARD(e);
-    e->begun = false;
+    ENTRY_POOL(e, env, "cagym_step_autoreset");
+    ON_DEVICE_VOIDS_BEGUN(e);
+    if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_step_autoreset needs the generation-3 kernels");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    CagymOut o = to_out(out);
-    if (!e->cfg.laserscan) o.laserscan = nullptr;
-    if (e->generation == 3) {
-        launch3(e, false, true, ext_actions, 1, o, st);
-    } else
-        return fail(e, CAGYM_E_UNSUPPORTED, "cagym_step_autoreset needs the generation-3 kernels");
+    const CagymOut o = to_out(e, out);
+    launch3(e, K3_HALF_NONE, false, true, ext_actions, 1, o, st);
     HIPCHK(e, hipGetLastError());
-    if (!has_map(e) && o.laserscan) HIPCHK(e, hipMemsetAsync(o.laserscan, 0, scan_bytes(e), st));  // empty map: 0.0 everywhere
-    return CAGYM_OK;  // the scan of the (possibly restarted) worlds is part of the launch
+    return fill_empty_scan(e, o, st);  // the scan of the (possibly restarted) worlds is part of the launch
 }
 
 // ---- the split step (csrc/cagym_split3.h) -----------------------------------------------------------------------------------------
 int cagym_step_begin(void* env, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_step_begin before cagym_set_scenarios");
+    ENTRY_POOL(e, env, "cagym_step_begin");
     if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "the split step needs the generation-3 kernels");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     e->begun = true;
     if (!e->any_rvo) return CAGYM_OK;  // no internal RVO policy: nothing to solve ahead of the external actions
-    K3Launch L;
-    L.D = e->D; L.ext = nullptr; L.out = CagymOut{}; L.n_steps = 1; L.any_rvo = 1; L.rollout = false; L.auto_reset = false;
-    L.half = K3_HALF_PRE;
-    L.grid = (unsigned)n_wg2(e);
-    L.lds = cagym_lds3_pre_bytes(e->cfg.max_agents, cagym_as(e->cfg.max_agents, wpw_spec(e)), spec2(e).nt, has_map(e) ? e->D.ko : 0);
-    if (L.lds < e->pre_lds_min && e->pre_lds_min <= 64 * 1024) L.lds = e->pre_lds_min;
-    L.stream = reinterpret_cast<hipStream_t>(stream);
-    k3_entry(e)->launch[has_map(e) ? 1 : 0](L);
+    launch3(e, K3_HALF_PRE, false, false, nullptr, 1, CagymOut{}, reinterpret_cast<hipStream_t>(stream));
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
 
 int cagym_step_finish(void* env, const float* ext_actions, const cagym_outputs* out, int auto_reset, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_step_finish before cagym_set_scenarios");
+    ENTRY_POOL(e, env, "cagym_step_finish");
     if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "the split step needs the generation-3 kernels");
     if (!e->begun) return fail(e, CAGYM_E_STATE, "cagym_step_finish without a cagym_step_begin on the current state");
-    DEVGUARD(e);
-    e->begun = false;
+    ON_DEVICE_VOIDS_BEGUN(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    CagymOut o = to_out(out);
-    if (!e->cfg.laserscan) o.laserscan = nullptr;
-    K3Launch L;
-    L.D = e->D; L.ext = ext_actions; L.out = o; L.n_steps = 1; L.any_rvo = 0; L.rollout = false; L.auto_reset = auto_reset != 0;
-    L.half = K3_HALF_POST;
-    L.grid = (unsigned)n_wg2(e);
-    L.lds = cagym_lds3_post_bytes(e->cfg.max_agents, cagym_as(e->cfg.max_agents, wpw_spec(e)), has_map(e) ? e->D.ko / 2 : 0, has_map(e));
-    L.stream = st;
-    k3_entry(e)->launch[has_map(e) ? 1 : 0](L);
+    const CagymOut o = to_out(e, out);
+    launch3(e, K3_HALF_POST, false, auto_reset != 0, ext_actions, 1, o, st);
     HIPCHK(e, hipGetLastError());
-    if (!has_map(e) && o.laserscan) HIPCHK(e, hipMemsetAsync(o.laserscan, 0, scan_bytes(e), st));  // empty map: 0.0 everywhere
-    return CAGYM_OK;
+    return fill_empty_scan(e, o, st);
 }
 
 int cagym_rollout(void* env, int n_steps, int auto_reset, const cagym_outputs* out, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_rollout before cagym_set_scenarios");
-    DEVGUARD(e);
-    e->begun = false;
+    ENTRY_POOL(e, env, "cagym_rollout");
+    ON_DEVICE_VOIDS_BEGUN(e);
     if (n_steps < 1) return fail(e, CAGYM_E_INVALID, "n_steps must be >= 1");
     if (e->cfg.laserscan && out && out->laserscan && e->generation != 3)
         return fail(e, CAGYM_E_UNSUPPORTED, "cagym_rollout produces laserscan with the generation-3 kernels only");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    CagymOut o = to_out(out);
-    if (!e->cfg.laserscan) o.laserscan = nullptr;
-    size_t lds = cagym_lds_bytes(e->cfg.max_agents);
-    if (e->generation == 3) {
-        launch3(e, true, auto_reset != 0, nullptr, n_steps, o, st);
-    } else if (auto_reset)
-        hipLaunchKernelGGL(k_rollout<true>, dim3(n_waves(e)), dim3(64), lds, st, e->D, n_steps, o);
-    else
-        hipLaunchKernelGGL(k_rollout<false>, dim3(n_waves(e)), dim3(64), lds, st, e->D, n_steps, o);
+    const CagymOut o = to_out(e, out);
+    const size_t lds = cagym_lds_bytes(e->cfg.max_agents);
+    if (e->generation == 3) launch3(e, K3_HALF_NONE, true, auto_reset != 0, nullptr, n_steps, o, st);
+    else if (auto_reset) hipLaunchKernelGGL(k_rollout<true>, dim3(n_waves(e)), dim3(64), lds, st, e->D, n_steps, o);
+    else hipLaunchKernelGGL(k_rollout<false>, dim3(n_waves(e)), dim3(64), lds, st, e->D, n_steps, o);
     HIPCHK(e, hipGetLastError());
-    if (e->generation == 3 && !has_map(e) && o.laserscan)  // empty map: 0.0 everywhere, all n_steps slices
-        HIPCHK(e, hipMemsetAsync(o.laserscan, 0, (size_t)n_steps * scan_bytes(e), st));
-    return CAGYM_OK;
+    return fill_empty_scan(e, o, st, n_steps);
 }
 
 int cagym_kernel_name(void* env, int rollout, int auto_reset, char* buf, int buf_len) {
@@ -798,10 +805,9 @@ int cagym_kernel_name(void* env, int rollout, int auto_reset, char* buf, int buf
 }
 
 int cagym_laserscan(void* env, float* laserscan, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!laserscan) return fail(e, CAGYM_E_INVALID, "null laserscan buffer");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     size_t total = (size_t)e->cfg.n_worlds * e->cfg.max_agents * 16;
     hipLaunchKernelGGL(k_laserscan, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, e->D, laserscan);
@@ -810,11 +816,10 @@ int cagym_laserscan(void* env, float* laserscan, void* stream) {
 }
 
 int cagym_occupancy_grid(void* env, uint8_t* grid, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!grid) return fail(e, CAGYM_E_INVALID, "null grid buffer");
     if (e->cfg.max_obstacles <= 0) return fail(e, CAGYM_E_STATE, "cagym_occupancy_grid needs an env created with max_obstacles > 0");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_occupancy_grid, dim3((unsigned)((size_t)e->cfg.n_worlds * e->cfg.max_agents)), dim3(256), 0, st, e->D, grid);
     HIPCHK(e, hipGetLastError());
@@ -847,10 +852,9 @@ __global__ void __launch_bounds__(256) k_pack_stats(CagymDev D, int32_t* __restr
 }
 
 int cagym_pack_episode_stats(void* env, int32_t* records, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!records) return fail(e, CAGYM_E_INVALID, "null records buffer");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipLaunchKernelGGL(k_pack_stats, dim3((unsigned)((e->cfg.n_worlds + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, records);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
@@ -858,13 +862,14 @@ int cagym_pack_episode_stats(void* env, int32_t* records, void* stream) {
 
 // which forward kernel (read per call: the A/B tests flip it inside one process): default = split-f16 matrix cores
 // (cagym_ga3c16.h); CAGYM_GA3C=mfma32: round 2's exact-fp32 matrix-core kernel; =valu: round 1's vector kernel
-enum { GA_KERNEL_H16 = 0, GA_KERNEL_MFMA32 = 1, GA_KERNEL_VALU = 2, GA_KERNEL_BAD = -1 };
-static int ga3c_kernel_choice() {
+enum { GA_KERNEL_H16 = 0, GA_KERNEL_MFMA32 = 1, GA_KERNEL_VALU = 2 };
+static int ga3c_kernel_choice(Env* e, int* kernel) {
     const char* which = getenv("CAGYM_GA3C");
-    if (!which || !which[0] || !strcmp(which, "h16")) return GA_KERNEL_H16;
-    if (!strcmp(which, "mfma32")) return GA_KERNEL_MFMA32;
-    if (!strcmp(which, "valu")) return GA_KERNEL_VALU;
-    return GA_KERNEL_BAD;
+    if (!which || !which[0] || !strcmp(which, "h16")) *kernel = GA_KERNEL_H16;
+    else if (!strcmp(which, "mfma32")) *kernel = GA_KERNEL_MFMA32;
+    else if (!strcmp(which, "valu")) *kernel = GA_KERNEL_VALU;
+    else return fail(e, CAGYM_E_INVALID, "CAGYM_GA3C: unknown forward kernel (h16, mfma32 or valu)");
+    return CAGYM_OK;
 }
 
 // the handle's packed copy of `weights`: made on `st` the first time a blob (by address) is used; a caller that rewrites the
@@ -882,10 +887,9 @@ static int ga3c_pack(Env* e, const float* weights, hipStream_t st, bool force) {
 }
 
 int cagym_ga3c_load_weights(void* env, const float* weights, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!weights) return fail(e, CAGYM_E_INVALID, "null weights");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     return ga3c_pack(e, weights, reinterpret_cast<hipStream_t>(stream), true);
 }
 
@@ -898,11 +902,21 @@ static void launch_ga3c_state(Env* e, int max_observed, const int32_t* agent_idx
 }
 
 int cagym_ga3c_state(void* env, int max_observed, float* state, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!state || max_observed < 1 || max_observed > 10) return fail(e, CAGYM_E_INVALID, "bad arguments (max_observed in 1..10)");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     launch_ga3c_state(e, max_observed, nullptr, (long long)e->cfg.n_worlds * e->cfg.max_agents, nullptr, state, reinterpret_cast<hipStream_t>(stream));
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// The default forward kernel of cagym_ga3c_act / cagym_ga3c_act_merge, one launch: list, state rows and network per workgroup of
+// 32 worlds (cagym_ga3c16.h).  merge: the status lanes also copy the rows of every other agent from ext_in (null: zeros).
+static int ga3c_act_h16(Env* e, const float* weights, int max_observed, float* actions, bool merge, const float* ext_in, hipStream_t st) {
+    if (int rc = ga3c_pack(e, weights, st, false)) return rc;
+    const bool lpa16 = e->cfg.max_agents <= 16;
+    auto* kernel = merge ? (lpa16 ? k_ga3c_act_h16<16, true> : k_ga3c_act_h16<32, true>) : (lpa16 ? k_ga3c_act_h16<16, false> : k_ga3c_act_h16<32, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((e->cfg.n_worlds + 31) / 32)), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, actions, ext_in);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
@@ -915,26 +929,14 @@ size_t cagym_ga3c_act_workspace_bytes(void* env) {
 }
 
 int cagym_ga3c_act(void* env, const float* weights, int max_observed, void* work, float* ext_actions, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!weights || !work || !ext_actions || max_observed < 1 || max_observed > 10)
         return fail(e, CAGYM_E_INVALID, "bad arguments (max_observed in 1..10)");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int which = ga3c_kernel_choice();
-    if (which == GA_KERNEL_BAD) return fail(e, CAGYM_E_INVALID, "CAGYM_GA3C: unknown forward kernel (h16, mfma32 or valu)");
-    if (which == GA_KERNEL_H16) {  // one launch: list, state rows and network per workgroup of 32 worlds (cagym_ga3c16.h); `work` is not used
-        if (int rc = ga3c_pack(e, weights, st, false)) return rc;
-        const unsigned grid = (unsigned)((e->cfg.n_worlds + 31) / 32);
-        if (e->cfg.max_agents <= 16)
-            hipLaunchKernelGGL((k_ga3c_act_h16<16, false>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions,
-                               (const float*)nullptr);
-        else
-            hipLaunchKernelGGL((k_ga3c_act_h16<32, false>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, ext_actions,
-                               (const float*)nullptr);
-        HIPCHK(e, hipGetLastError());
-        return CAGYM_OK;
-    }
+    int which;
+    if (int rc = ga3c_kernel_choice(e, &which)) return rc;
+    if (which == GA_KERNEL_H16) return ga3c_act_h16(e, weights, max_observed, ext_actions, false, nullptr, st);  // `work` is not used
     // CAGYM_GA3C=mfma32 / valu (A/B): the three-launch chain of rounds 2 - 3
     const size_t total = (size_t)e->cfg.n_worlds * e->cfg.max_agents;
     int32_t* idx = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(work) + 256);
@@ -961,28 +963,18 @@ int cagym_ga3c_act(void* env, const float* weights, int max_observed, void* work
 }
 
 int cagym_ga3c_act_merge(void* env, const float* weights, int max_observed, void* work, const float* ext_in, float* actions, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!weights || !work || !actions || max_observed < 1 || max_observed > 10)
         return fail(e, CAGYM_E_INVALID, "bad arguments (max_observed in 1..10)");
     const size_t total = (size_t)e->cfg.n_worlds * e->cfg.max_agents;
     if (ext_in && ext_in < actions + 2 * total && actions < ext_in + 2 * total) return fail(e, CAGYM_E_INVALID, "ext_in aliases actions");
     if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(ext_in)) & 7)
         return fail(e, CAGYM_E_INVALID, "actions / ext_in must be 8-byte aligned");
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int which = ga3c_kernel_choice();
-    if (which == GA_KERNEL_BAD) return fail(e, CAGYM_E_INVALID, "CAGYM_GA3C: unknown forward kernel (h16, mfma32 or valu)");
-    if (which == GA_KERNEL_H16) {  // cagym_ga3c_act's launch; its status lanes copy the other rows
-        if (int rc = ga3c_pack(e, weights, st, false)) return rc;
-        const unsigned grid = (unsigned)((e->cfg.n_worlds + 31) / 32);
-        if (e->cfg.max_agents <= 16)
-            hipLaunchKernelGGL((k_ga3c_act_h16<16, true>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, actions, ext_in);
-        else
-            hipLaunchKernelGGL((k_ga3c_act_h16<32, true>), dim3(grid), dim3(512), 0, st, e->D, e->ga3c_packed, max_observed, actions, ext_in);
-        HIPCHK(e, hipGetLastError());
-        return CAGYM_OK;
-    }
+    int which;
+    if (int rc = ga3c_kernel_choice(e, &which)) return rc;
+    if (which == GA_KERNEL_H16) return ga3c_act_h16(e, weights, max_observed, actions, true, ext_in, st);
     // CAGYM_GA3C=mfma32 / valu (A/B): the table first, then cagym_ga3c_act's chain over it
     if (ext_in) HIPCHK(e, hipMemcpyAsync(actions, ext_in, total * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
     else HIPCHK(e, hipMemsetAsync(actions, 0, total * 2 * sizeof(float), st));
@@ -1016,15 +1008,14 @@ int cagym_debug_wgtrace(unsigned long long* out, int n_wg) {
 
 int cagym_ga3c_forward(void* env, const float* weights, const float* state, const int32_t* agent_idx, int B,
                        float* ext_actions, int32_t* action_index, float* probs, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!weights || !state || !agent_idx || B < 0) return fail(e, CAGYM_E_INVALID, "bad arguments");
     if (B == 0) return CAGYM_OK;
-    DEVGUARD(e);
+    ON_DEVICE(e);
     // 32 agents per workgroup reuse every weight 32 times; small batches take 16 so that each CU still gets >= 2 workgroups
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int which = ga3c_kernel_choice();
-    if (which == GA_KERNEL_BAD) return fail(e, CAGYM_E_INVALID, "CAGYM_GA3C: unknown forward kernel (h16, mfma32 or valu)");
+    int which;
+    if (int rc = ga3c_kernel_choice(e, &which)) return rc;
     if (which == GA_KERNEL_H16) {
         if (int rc = ga3c_pack(e, weights, st, false)) return rc;
         hipLaunchKernelGGL(k_ga3c_forward_h16, dim3((unsigned)((B + 31) / 32)), dim3(512), 0, st, e->ga3c_packed, state, agent_idx, B, e->D.pref,
@@ -1043,20 +1034,12 @@ int cagym_ga3c_forward(void* env, const float* weights, const float* state, cons
 }
 
 // ---- information-gain primitives -----------------------------------------------------------------
-static int ig_check(Env* e, const char* what) {
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->ig_ready) return fail(e, CAGYM_E_STATE, std::string(what) + " before cagym_ig_init");
-    return CAGYM_OK;
-}
-
 int cagym_ig_init(void* env, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
-    if (!e->scenarios_set) return fail(e, CAGYM_E_STATE, "cagym_ig_init before cagym_set_scenarios");
+    ENTRY_POOL(e, env, "cagym_ig_init");
     if (e->cfg.max_obstacles <= 0 || !e->D.map_bits)
         return fail(e, CAGYM_E_UNSUPPORTED, "information-gain primitives need obstacle rasters (max_obstacles > 0)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DEVGUARD(e);
+    ON_DEVICE(e);
     const size_t S = e->cfg.n_scenarios, N = e->cfg.n_worlds;
     if (!e->G.d2) {
         int rc;
@@ -1076,10 +1059,8 @@ int cagym_ig_init(void* env, void* stream) {
 }
 
 int cagym_ig_reset_belief(void* env, const uint8_t* world_mask, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_reset_belief");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_reset_belief");
+    ON_DEVICE(e);
     hipLaunchKernelGGL(k_ig_fill_belief, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), e->G, world_mask);
     HIPCHK(e, hipGetLastError());
@@ -1087,10 +1068,8 @@ int cagym_ig_reset_belief(void* env, const uint8_t* world_mask, void* stream) {
 }
 
 int cagym_ig_get(void* env, uint32_t** edf_d2, double** belief) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_get");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_get");
+    ON_DEVICE(e);
     if (edf_d2) *edf_d2 = e->G.d2;
     if (belief) *belief = e->G.belief;
     return CAGYM_OK;
@@ -1098,10 +1077,8 @@ int cagym_ig_get(void* env, uint32_t** edf_d2, double** belief) {
 
 int cagym_ig_visible_cells(void* env, const double* poses, const int32_t* world, int Q, double fov_rad, double range,
                            uint64_t* masks, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_visible_cells");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_visible_cells");
+    ON_DEVICE(e);
     if (Q < 0 || !poses || !world || !masks) return fail(e, CAGYM_E_INVALID, "bad arguments");
     if (Q == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_ig_visible, dim3((unsigned)Q), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), e->G, poses,
@@ -1113,10 +1090,8 @@ int cagym_ig_visible_cells(void* env, const double* poses, const int32_t* world,
 int cagym_ig_update_belief(void* env, const double* poses, const int32_t* n_poses, const double* detections,
                            const int32_t* n_det, int P, int Dmax, double fov_rad, double range, uint64_t* observed,
                            void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_update_belief");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_update_belief");
+    ON_DEVICE(e);
     if (P < 1 || Dmax < 1 || !poses || !detections || !n_det) return fail(e, CAGYM_E_INVALID, "bad arguments");
     hipLaunchKernelGGL(k_ig_update, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        e->G, poses, n_poses, detections, n_det, P, Dmax, fov_rad, range,
@@ -1126,10 +1101,8 @@ int cagym_ig_update_belief(void* env, const double* poses, const int32_t* n_pose
 }
 
 int cagym_ig_mi_reward(void* env, const uint64_t* masks, const int32_t* world, int Q, double* reward, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_mi_reward");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_mi_reward");
+    ON_DEVICE(e);
     if (Q < 0 || !masks || !world || !reward) return fail(e, CAGYM_E_INVALID, "bad arguments");
     if (Q == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_ig_reward, dim3((unsigned)Q), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->G,
@@ -1140,10 +1113,8 @@ int cagym_ig_mi_reward(void* env, const uint64_t* masks, const int32_t* world, i
 
 int cagym_ig_next_pose(void* env, const double* poses, const double* actions, const int32_t* world,
                        const double* radius, int Q, int xdt, double dt, double* next, uint8_t* feasible, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_next_pose");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_next_pose");
+    ON_DEVICE(e);
     if (Q < 0 || xdt < 1 || xdt > 1000 || !poses || !actions || !world || !radius || !next || !feasible)
         return fail(e, CAGYM_E_INVALID, "bad arguments");
     if (Q == 0) return CAGYM_OK;
@@ -1158,10 +1129,8 @@ int cagym_ig_rollouts(void* env, const double* pose0, const uint64_t* observed0,
                       const int32_t* world, const int32_t* n_steps, const double* radius, int Q, int nsims,
                       int max_steps, int xdt, double dt, double fov_rad, double range, uint64_t seed, double* rewards,
                       uint8_t* actions, double* final_pose, uint64_t* observed_out, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_ig_rollouts");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_ig_rollouts");
+    ON_DEVICE(e);
     if (Q < 0 || nsims < 1 || max_steps < 0 || max_steps > 255 || xdt < 1 || xdt > 1000 || !pose0 || !observed0 ||
         !exclude || !world || !n_steps || !radius || !rewards)
         return fail(e, CAGYM_E_INVALID, "bad arguments");
@@ -1188,11 +1157,10 @@ static int ig_robots_check(Env* e, int n_robots, const char* what) {
 
 int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const float* obs_oas, double* poses, double* detections,
                           int32_t* n_det, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!obs_oas || !poses || !detections || !n_det) return fail(e, CAGYM_E_INVALID, "null argument");
     if (int rc = ig_robots_check(e, n_robots, "cagym_ig_robot_inputs")) return rc;
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipLaunchKernelGGL(k_ig_robot_inputs, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D,
                        n_robots, (float)detect_range, obs_oas, poses, detections, n_det);
     HIPCHK(e, hipGetLastError());
@@ -1200,12 +1168,11 @@ int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const fl
 }
 
 int cagym_ig_robot_actions(void* env, int n_robots, const double* planner_actions, float* actions, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    if (!e) return fail(nullptr, CAGYM_E_INVALID, "null env");
+    ENTRY(e, env);
     if (!planner_actions || !actions) return fail(e, CAGYM_E_INVALID, "null argument");
     if (reinterpret_cast<uintptr_t>(actions) & 7) return fail(e, CAGYM_E_INVALID, "actions must be 8-byte aligned");
     if (int rc = ig_robots_check(e, n_robots, "cagym_ig_robot_actions")) return rc;
-    DEVGUARD(e);
+    ON_DEVICE(e);
     hipLaunchKernelGGL(k_ig_robot_actions, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D,
                        n_robots, planner_actions, actions);
     HIPCHK(e, hipGetLastError());
@@ -1230,10 +1197,8 @@ size_t cagym_dmcts_workspace_bytes(int n_worlds, const cagym_dmcts_params* p) {
 
 int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* poses, void* workspace,
                      size_t workspace_bytes, double* actions, uint8_t* paths, double* stats, void* stream) {
-    Env* e = reinterpret_cast<Env*>(env);
-    int rc = ig_check(e, "cagym_dmcts_plan");
-    if (rc) return rc;
-    DEVGUARD(e);
+    ENTRY_IG(e, env, "cagym_dmcts_plan");
+    ON_DEVICE(e);
     if (!params || !poses || !workspace || !actions || !paths || !stats) return fail(e, CAGYM_E_INVALID, "null argument");
     const cagym_dmcts_params& p = *params;
     if (p.n_robots < 1 || p.n_robots > DM_MAXR || p.horizon < 1 || p.horizon > DM_MAXH || p.Nsims < 1 || p.Nsims > DM_MAXSIMS ||

@@ -425,3 +425,41 @@ __device__ __forceinline__ bool wall_row_hit(const uint32_t* map, int cell, int 
     const uint32_t upto = (x1 & 31) == 31 ? 0xffffffffu : ((1u << ((x1 & 31) + 1)) - 1u);
     return ok && (w1 == w0 ? (a & upto & ~below) : ((a & ~below) | (b & upto))) != 0u;
 }
+
+// ---- shared by the step kernels of both generations (cagym_gen1.h, cagym_kernels3.h) ----
+struct LaneCtx {
+    int lane, wl, slot, base, world, n, wpw, worlds_valid;
+    int episode;  // episodes started by this world (every lane of the world tracks it)
+    bool valid;   // lane maps to an existing world
+    bool active;  // slot < n_agents[world]
+};
+
+__device__ __forceinline__ uint64_t world_mask64(const LaneCtx& C) {
+    uint64_t m = C.n >= 64 ? ~0ull : ((1ull << C.n) - 1ull);
+    return m << C.base;
+}
+
+// fold the finished episode of this lane's world into the cumulative statistics (lane slot 0 writes)
+__device__ __forceinline__ void fold_episode_stats(const CagymDev& D, const LaneCtx& C, const Agent& A, float& ep_ret,
+                                                   int& ep_len) {
+    uint64_t wm = world_mask64(C);
+    bool live = C.valid && C.active;
+    int goal = __popcll(__ballot(live && (A.st & CAGYM_FLAG_AT_GOAL)) & wm);
+    int coll = __popcll(__ballot(live && (A.st & CAGYM_FLAG_IN_COLLISION)) & wm);
+    int tout = __popcll(__ballot(live && (A.st & CAGYM_FLAG_RAN_OUT_OF_TIME)) & wm);
+    if (C.valid && C.slot == 0) {
+        // every load before the first store: written as six "+=" the compiler must assume the arrays alias and waits for each
+        // read-modify-write in turn - four dependent HBM round trips (~3.6 us per restarted world in the step kernels)
+        const float r0 = D.stat_return[C.world];
+        const int e0 = D.stat_episodes[C.world], s0 = D.stat_steps[C.world];
+        const int o0 = D.stat_outcomes[C.world * 3 + 0], o1 = D.stat_outcomes[C.world * 3 + 1], o2 = D.stat_outcomes[C.world * 3 + 2];
+        D.stat_return[C.world] = r0 + ep_ret;
+        D.stat_episodes[C.world] = e0 + 1;
+        D.stat_steps[C.world] = s0 + ep_len;
+        D.stat_outcomes[C.world * 3 + 0] = o0 + goal;
+        D.stat_outcomes[C.world * 3 + 1] = o1 + coll;
+        D.stat_outcomes[C.world * 3 + 2] = o2 + tout;
+    }
+    ep_ret = 0.f;
+    ep_len = 0;
+}

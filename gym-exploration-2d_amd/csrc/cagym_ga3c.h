@@ -13,6 +13,7 @@
 // restatement and the known answer of SURVEY.md 8(c).
 #pragma once
 #include "cagym_device.h"
+#include "cagym_ga3c_state.h"
 
 #define GA_H 64
 #define GA_W 256

@@ -2,9 +2,6 @@
 //   -DK3_NT=<lanes> -DK3_MT=<compile-time M> -DK3_WP=<worlds per workgroup> -DK3_OBST=<0|1>
 // (gym-exploration-2d_amd/build.py), or included by cagym_api.hip under -DCAGYM_MONOLITHIC.
 #include <hip/hip_runtime.h>
-#ifndef CAGYM_MONOLITHIC
-#define CAGYM_K3_UNIT 1  // cagym_kernels.h: device functions only, its __global__ kernels belong to cagym_api.hip
-#endif
 #include "cagym_kernels3.h"
 #include "cagym_split3.h"
 #include "cagym_launch3.h"

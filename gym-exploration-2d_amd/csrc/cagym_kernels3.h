@@ -16,11 +16,12 @@
 //   (rare)    a world was reset in S2: keys, distances, preferred velocities and half-planes are rebuilt in two extra phases
 //
 // Wave 0 waits for the other LP waves on an LDS counter (release/acquire at workgroup scope), not on a barrier, so the
-// row workers never stop between C and D.  Arithmetic is shared with generation 1 (cagym_device.h, cagym_orca.h):
+// row workers never stop between C and D.  Arithmetic is shared with generation 1 (cagym_gen1.h) through cagym_device.h and cagym_orca.h:
 // both produce bit-identical results (tests/test_hip_parity.py); generation 2 (phase-split, one barrier-separated phase after
 // the other) was retired once generation 3 reproduced it bit for bit.
 #pragma once
-#include "cagym_kernels.h"
+#include "cagym_device.h"
+#include "cagym_orca.h"
 
 #include "cagym_spin.h"   // lds_wait_ge: the bounded intra-workgroup wait
 #include "cagym_trace.h"  // STAMP / WGTRACE / WAVETRACE / PMARK: diagnostic hooks, empty in the shipped library

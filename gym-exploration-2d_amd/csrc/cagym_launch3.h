@@ -5,6 +5,9 @@
 // build in parallel and an edit of the kernels re-links in the time of the slowest one (was: one 2.5-minute unit).
 // -DCAGYM_MONOLITHIC makes cagym_api.hip include all of them again (diagnostic builds: tools/build_alt.sh, and a plain
 // `hipcc -c cagym_api.hip` of the tree).
+// A unit sees cagym_kernels3.h, cagym_split3.h and what they include (cagym_device.h, cagym_orca.h, cagym_spin.h, cagym_trace.h) and
+// nothing else: generation 1 (cagym_gen1.h), the sensor kernels (cagym_sensors.h) and GA3C (cagym_ga3c_state.h, ...) belong to
+// cagym_api.hip alone, an edit there leaves the twelve objects fresh (build.py: K3_HEADERS).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "cagym_device.h"

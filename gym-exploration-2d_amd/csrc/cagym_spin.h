@@ -6,7 +6,7 @@
 // when it gives up the caller records CAGYM_DEVERR_* in the handle's device status word (CagymDev::dev_status: host-mapped
 // memory, read by the next entry point of the C ABI, which then fails with CAGYM_E_DEVICE) and goes on with whatever the
 // counter says - results of that launch are void, but every wave reaches the end of the grid.
-// The loop is a template over (load, pause) so that tests/test_abi.py can compile and exercise exactly this logic on the CPU
+// The loop is a template over (load, pause) so that tests/test_laser_audit.py can compile and exercise exactly this logic on the CPU
 // (tests/spin_check.cpp); on the device `load` is a workgroup-scope acquire load and `pause` is s_sleep.
 #pragma once
 

@@ -1,4 +1,4 @@
-/* cagym_oracle_grid.c -- TEST INFRASTRUCTURE (CPU oracle), twin of k_occupancy_grid (csrc/cagym_kernels.h).
+/* cagym_oracle_grid.c -- TEST INFRASTRUCTURE (CPU oracle), twin of k_occupancy_grid (csrc/cagym_sensors.h).
  * OccupancyGridSensor.sense (gym_collision_avoidance/envs/sensors/OccupancyGridSensor.py:70-98, 131-143) with
  * Map.world_coordinates_to_map_indices (Map.py:40-47) and Map.getSubmapByIndices (Map.py:81-105): the 300x300
  * occupancy raster as float is rotated about the agent's cell by -heading with cv2.getRotationMatrix2D +

@@ -38,7 +38,7 @@ def one(job):
 def main():
     extra = sys.argv[1:]
     jobs = [(o, s, d, extra) for (o, s, d, _h) in b.units() if o.startswith("k3_")]
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=int(os.environ.get("MAX_JOBS") or os.cpu_count() or 4)) as ex:
         res = list(ex.map(one, jobs))
     print("%-64s %5s %5s %5s %8s %4s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ"))
     for obj, rows, rc in res:
