@@ -240,9 +240,16 @@ class BatchedCollisionAvoidanceEnv(object):
             rc = self.L.cagym_reset(self.h, None if m is None else m.data_ptr(), int(bool(advance_episode)),
                                     C.byref(self._out), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_reset")
-        if self._igm is not None:  # a new episode: prior beliefs (of the masked worlds) and no communicated plans (of any world)
-            self._igm.ig.reset_belief(m)
-            self._igm.planner.reset()
+        g = self._igm
+        if g is not None and g.episodic and m is not None:
+            # a manual restart of the masked worlds only: prior belief, no communicated plans, running team return zeroed; it is
+            # not a finished episode, so nothing is folded into the episode statistics (cagym_ig_episode_boundary without FOLD)
+            g.ig.episode_boundary(g.planner.P, g.planner.workspace, None, m, 0)
+        elif g is not None:  # a new episode: prior beliefs (of the masked worlds) and no communicated plans (of any world)
+            g.ig.reset_belief(m)
+            g.planner.reset()
+            if g.episodic:
+                g.ig.episode_stats["running"].zero_()
         return self._obs()
 
     # ---- policies driven inside step(): GA3C-CADRL (collision_avoidance_env.py:287-340) and ig_mcts (:342-379) ------------------
@@ -257,12 +264,21 @@ class BatchedCollisionAvoidanceEnv(object):
         return self._ga3c
 
     def attach_ig_mcts(self, detect_fov=60.0, detect_range=5.0, xdt=5, Ntree=30, Nsims=10, mcts_cp=1.0, mcts_horizon=4,
-                       mcts_gamma=0.95, Ncycles=5, parallelize_agents=False, radius=0.5, seed=0):
+                       mcts_gamma=0.95, Ncycles=5, parallelize_agents=False, radius=0.5, seed=0, episodic=False):
         """From now on step() plans the (v, omega) of every IG robot itself (ig_mcts.set_param + find_next_action, the Dec-MCTS
         cycles of collision_avoidance_env.py:342-379): robot poses and detections (cagym_ig_robot_inputs), belief update, the
         team's MI reward into self.team_reward, Dec-MCTS plan (seeded counter-based streams), the robots' rows of the action
         table (cagym_ig_robot_actions), then the step.  One belief per world, shared by its robots.  Every scenario of the pool
-        must hold the same number of IG robots.  Not available under auto-reset or in rollout()."""
+        must hold the same number of IG robots.
+        episodic=False (default): one team episode per handle, as the reference's experiment loop runs it; step(auto_reset=True)
+        and rollout() are refused, and reset(world_mask=...) forgets the plans of every world.
+        episodic=True: every step ends with one cagym_ig_episode_boundary launch.  It adds the step's team reward to the
+        world's running return (ig_episode_stats()) and, under auto_reset, restarts the planner and the belief of exactly the
+        worlds whose game_over the step just set: the terminal step's reward belongs to the episode that ends, the next step's
+        belief update is the first observation of the new episode on the new scenario's distance field, and its first planning
+        cycle hears nothing (DummyVecEnv's reset() builds new ig_mcts objects).  rollout() chains such steps; CagymVecEnv works.
+        reset(world_mask=m) restarts the masked worlds alone and zeroes their running return without counting an episode;
+        reset() restarts everything and zeroes every running return."""
         from .ig import InfoGain
         from .dmcts import DeviceDecMCTSPlanner
         R = self._n_ig if self._n_ig is not None else 0
@@ -270,7 +286,7 @@ class BatchedCollisionAvoidanceEnv(object):
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
         N, K, dev = self.N, self.K, self.device
         g = type("IgState", (), {})()
-        g.ig, g.R, g.range = ig, R, float(detect_range)
+        g.ig, g.R, g.range, g.episodic = ig, R, float(detect_range), bool(episodic)
         g.poses = torch.zeros((N, max(R, 1), 3), dtype=torch.float64, device=dev)
         g.det = torch.zeros((N, max(R, 1), K, 2), dtype=torch.float64, device=dev)
         g.n_det = torch.zeros((N, max(R, 1)), dtype=torch.int32, device=dev)
@@ -293,8 +309,18 @@ class BatchedCollisionAvoidanceEnv(object):
     def _drives_ga3c(self):
         return self._ga3c is not None and sc.POLICY_GA3C in self._pool_policies
 
-    def _internal_actions(self, a):
-        """The action table the step reads: the caller's `a` (or None) when nothing is attached, else the env's own buffer."""
+    def ig_episode_stats(self):
+        """Zero-copy device views of the IG team's per-world episode accumulators (an episodic attach_ig_mcts keeps them):
+        running [N] f64 team return of the episode in progress, sum [N] f64 over the finished episodes, last [N] f64 return of
+        the last finished one, episodes [N] i32 finished episodes."""
+        if self._igm is None:
+            raise RuntimeError("ig_episode_stats() needs attach_ig_mcts")
+        return dict(self._igm.ig.episode_stats)
+
+    def _internal_actions(self, a, team_reward_out=None, oas=None):
+        """The action table the step reads: the caller's `a` (or None) when nothing is attached, else the env's own buffer.
+        team_reward_out: where the team reward of this step goes (rollout: slice t of its buffer); oas: the OtherAgentsStates
+        table the last step wrote, when that is not self.obs_oas (rollout: slice t - 1)."""
         ga3c = self._drives_ga3c()
         if not ga3c and self._igm is None:
             return a
@@ -307,9 +333,9 @@ class BatchedCollisionAvoidanceEnv(object):
             table.copy_(a)
         if self._igm is not None:
             g = self._igm
-            g.ig.robot_inputs(g.R, g.range, self.obs_oas, g.poses, g.det, g.n_det)
+            g.ig.robot_inputs(g.R, g.range, self.obs_oas if oas is None else oas, g.poses, g.det, g.n_det)
             observed = g.ig.update_belief(g.poses, g.det, g.n_det)
-            self.team_reward = g.ig.mi_reward(observed, g.world)  # before the move, as the reference computes it
+            self.team_reward = g.ig.mi_reward(observed, g.world, out=team_reward_out)  # before the move, as the reference computes it
             planned, _ = g.planner.plan(g.poses)
             g.ig.robot_actions(g.R, planned, table)
         return table
@@ -319,9 +345,10 @@ class BatchedCollisionAvoidanceEnv(object):
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read."""
-        if auto_reset and self._igm is not None:
+        if auto_reset and self._igm is not None and not self._igm.episodic:
             raise RuntimeError("step(auto_reset=True) with ig_mcts attached: the planner's per-world restart (beliefs, "
-                               "communicated plans) is not implemented; step without auto-reset and reset() yourself")
+                               "communicated plans) is not implemented for this attach; attach_ig_mcts(episodic=True), or step "
+                               "without auto-reset and reset() yourself")
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
@@ -329,7 +356,15 @@ class BatchedCollisionAvoidanceEnv(object):
         fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
         rc = fn(self.h, None if a is None else a.data_ptr(), C.byref(self._out), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_step")
+        self._ig_boundary(self.team_reward, self.game_over if auto_reset else None)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
+
+    def _ig_boundary(self, team_reward, game_over):
+        """The episodic IG team's end of a step: the running return, and the restart of the worlds the step just finished."""
+        g = self._igm
+        if g is not None and g.episodic:
+            from .ig import EPISODE_FOLD
+            g.ig.episode_boundary(g.planner.P, g.planner.workspace, team_reward, game_over, EPISODE_FOLD)
 
     # ---- the split step: env.step() in two launches (include/cagym.h: cagym_step_begin / cagym_step_finish) ------------------
     def step_begin(self, stream=None):
@@ -383,14 +418,44 @@ class BatchedCollisionAvoidanceEnv(object):
             buf["ego"] = torch.empty((T, N, M, _lib.EGO_WIDTH), dtype=torch.float32, device=dev)
             if self.laserscan:
                 buf["laserscan"] = torch.empty((T, N, M, 16), dtype=torch.float32, device=dev)
+        if self._igm is not None:
+            buf["team_reward"] = torch.empty((T, N), dtype=torch.float64, device=dev)
         return buf
 
     def rollout(self, n_steps, auto_reset=True, out=None):
         """n_steps env steps in one launch (all agents internally driven); returns [T, ...] buffers.  With GA3C attached and
         GA3C agents in the pool: T x (cagym_ga3c_act_merge, step), each step writing slice t of the buffers - no host
-        synchronisation, so the chain can be captured in a graph."""
+        synchronisation, so the chain can be captured in a graph.  With an episodic attach_ig_mcts: T x (robot inputs, belief
+        update, team reward into out["team_reward"][t], plan, robot actions, step, episode boundary), no host synchronisation
+        either; not under stream capture (the planner's call_base is a kernel argument the host advances per call)."""
+        if self._igm is not None and not self._igm.episodic:
+            raise RuntimeError("rollout() with ig_mcts attached is not implemented for this attach (the planner needs per-world "
+                               "restarts): attach_ig_mcts(episodic=True)")
         if self._igm is not None:
-            raise RuntimeError("rollout() with ig_mcts attached is not implemented (the planner needs per-world restarts)")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("rollout() with ig_mcts attached cannot be captured in a graph: the planner's call_base is a "
+                                   "by-value kernel argument that the host advances with every planning step")
+            if out is None:
+                out = self.alloc_rollout(n_steps)
+            if out.get("team_reward") is None:
+                out["team_reward"] = torch.empty((int(n_steps), self.N), dtype=torch.float64, device=self.device)
+            fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
+            keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
+            # the robots' detector reads the OtherAgentsStates table of the step before: slice t - 1, or the env's own table, which
+            # every step writes when the caller asked for no observation slices and which ends up holding the last step's rows
+            sliced = out.get("other_agents_states") is not None
+            for t in range(int(n_steps)):
+                a = self._internal_actions(None, team_reward_out=out["team_reward"][t],
+                                           oas=out["other_agents_states"][t - 1] if sliced and t > 0 else None)
+                o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in keys])
+                if not sliced:
+                    o.obs_oas = self.obs_oas.data_ptr()
+                rc = fn(self.h, a.data_ptr(), C.byref(o), self._stream())
+                _lib.check(self.L, self.h, rc, "cagym_step")
+                self._ig_boundary(out["team_reward"][t], out["game_over"][t] if auto_reset else None)
+            if sliced and int(n_steps) > 0:
+                self.obs_oas.copy_(out["other_agents_states"][int(n_steps) - 1])
+            return out
         if out is None:
             out = self.alloc_rollout(n_steps)
         if self._drives_ga3c():

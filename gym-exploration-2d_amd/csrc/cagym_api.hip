@@ -23,6 +23,7 @@
 #include "cagym_gen.h"
 #include "cagym_gen2.h"
 #include "cagym_dmcts.h"
+#include "cagym_ig_episode.h"
 
 namespace {
 
@@ -39,6 +40,7 @@ struct Env {
     double* sc_heading_buf = nullptr;
     IgDev G{};
     uint32_t* ig_any = nullptr;
+    IgEpisode ig_ep{};  // the team reward's per-world episode accumulators (cagym_ig_episode_boundary)
     int32_t* gen_failed = nullptr;  // device word: agents whose rejection loop hit max_tries (cagym_generate_scenarios)
     int32_t* ga3c_ctr = nullptr;    // device words of cagym_ga3c_act's list (k_ga3c_select): ticket, list start, list length
     unsigned char* ga3c_packed = nullptr;   // the weight blob as split f16 operand fragments (k_ga3c_pack16, cagym_ga3c16.h)
@@ -1047,9 +1049,17 @@ int cagym_ig_init(void* env, void* stream) {
         if ((rc = dalloc(e, &e->G.belief, N * IG_BEL * IG_BEL)) != CAGYM_OK) return rc;
         if ((rc = dalloc(e, &e->G.mi, N * IG_BEL * IG_BEL)) != CAGYM_OK) return rc;
         if ((rc = dalloc(e, &e->ig_any, S)) != CAGYM_OK) return rc;
+        if ((rc = dalloc(e, &e->ig_ep.running, N)) != CAGYM_OK) return rc;
+        if ((rc = dalloc(e, &e->ig_ep.sum, N)) != CAGYM_OK) return rc;
+        if ((rc = dalloc(e, &e->ig_ep.last, N)) != CAGYM_OK) return rc;
+        if ((rc = dalloc(e, &e->ig_ep.episodes, N)) != CAGYM_OK) return rc;
     }
     e->G.N = (int)N; e->G.S = (int)S; e->G.map_bits = e->D.map_bits; e->G.sc_nobst = e->D.sc_nobst; e->G.episode = e->D.episode;
     HIPCHK(e, hipMemsetAsync(e->ig_any, 0, S * sizeof(uint32_t), st));
+    HIPCHK(e, hipMemsetAsync(e->ig_ep.running, 0, N * sizeof(double), st));
+    HIPCHK(e, hipMemsetAsync(e->ig_ep.sum, 0, N * sizeof(double), st));
+    HIPCHK(e, hipMemsetAsync(e->ig_ep.last, 0, N * sizeof(double), st));
+    HIPCHK(e, hipMemsetAsync(e->ig_ep.episodes, 0, N * sizeof(int32_t), st));
     hipLaunchKernelGGL(k_ig_edt_cols, dim3((unsigned)S), dim3(320), 0, st, e->G, e->ig_any);
     hipLaunchKernelGGL(k_ig_edt_rows, dim3((unsigned)(S * CAGYM_MAPD)), dim3(320), 0, st, e->G, e->ig_any);
     hipLaunchKernelGGL(k_ig_fill_belief, dim3((unsigned)N), dim3(256), 0, st, e->G, (const uint8_t*)nullptr);
@@ -1072,6 +1082,16 @@ int cagym_ig_get(void* env, uint32_t** edf_d2, double** belief) {
     ON_DEVICE(e);
     if (edf_d2) *edf_d2 = e->G.d2;
     if (belief) *belief = e->G.belief;
+    return CAGYM_OK;
+}
+
+int cagym_ig_get_episode_stats(void* env, double** running, double** sum, double** last, int32_t** episodes) {
+    ENTRY_IG(e, env, "cagym_ig_get_episode_stats");
+    ON_DEVICE(e);
+    if (running) *running = e->ig_ep.running;
+    if (sum) *sum = e->ig_ep.sum;
+    if (last) *last = e->ig_ep.last;
+    if (episodes) *episodes = e->ig_ep.episodes;
     return CAGYM_OK;
 }
 
@@ -1241,6 +1261,34 @@ int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* 
                            buf[(p.Ncycles - c) & 1], buf[(p.Ncycles - c - 1) & 1], dist, actions, paths, stats);
         HIPCHK(e, hipGetLastError());
     }
+    return CAGYM_OK;
+}
+
+int cagym_ig_episode_boundary(void* env, const cagym_dmcts_params* params, const double* team_reward, const uint8_t* restart_mask,
+                              uint32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_episode_boundary");
+    ON_DEVICE(e);
+    if (!params || !workspace) return fail(e, CAGYM_E_INVALID, "null argument");
+    cagym_dmcts_params p = *params;
+    if (p.n_robots < 1 || p.n_robots > DM_MAXR || p.Ntree < 1 || p.Ncycles < 1 || (size_t)p.Ntree * p.Ncycles > 100000)
+        return fail(e, CAGYM_E_INVALID, "Dec-MCTS parameters out of range (n_robots<=8, horizon<=8, Nsims<=32, comm_n<=8)");
+    if (p.parallel_agents > 1) return fail(e, CAGYM_E_INVALID, "Dec-MCTS parallel_agents must be 0 or 1");
+    if (flags & ~(uint32_t)(CAGYM_IG_EPISODE_FOLD | CAGYM_IG_EPISODE_PLANS_ONLY))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_episode_boundary: unknown flags");
+    const int N = e->cfg.n_worlds;
+    if (workspace_bytes < cagym_dmcts_workspace_bytes(N, &p)) return fail(e, CAGYM_E_INVALID, "workspace too small");
+    // the second publication buffer sits behind the sequential layout (cagym_dmcts_workspace_bytes); it is there when the
+    // workspace is large enough for the agent-parallel mode, whatever the mode of this call
+    p.parallel_agents = 0;
+    const size_t seq_bytes = cagym_dmcts_workspace_bytes(N, &p);
+    p.parallel_agents = 1;
+    const bool has_pub2 = workspace_bytes >= cagym_dmcts_workspace_bytes(N, &p);
+    unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
+    DmPublished* pub = reinterpret_cast<DmPublished*>(base);
+    DmPublished* pub2 = has_pub2 ? reinterpret_cast<DmPublished*>(base + dm_align(seq_bytes)) : nullptr;
+    hipLaunchKernelGGL(k_ig_episode_boundary, dim3((unsigned)N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->G, e->ig_ep,
+                       p.n_robots, (unsigned int)flags, team_reward, restart_mask, pub, pub2);
+    HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
 

@@ -286,13 +286,19 @@ __global__ void __launch_bounds__(320) k_ig_edt_rows(IgDev G, const uint32_t* an
     row[x] = best;
 }
 
-__global__ void __launch_bounds__(256) k_ig_fill_belief(IgDev G, const uint8_t* mask) {
-    const int w = blockIdx.x;
-    if (mask && !mask[w]) return;
+// world w's belief at the prior and its MI cache at ig_cell_mi(prior), by the `nthreads` threads of a block (k_ig_fill_belief and the
+// episode boundary, cagym_ig_episode.h: one statement of what a fresh belief is)
+__device__ __forceinline__ void ig_fill_world_prior(const IgDev& G, int w, int tid, int nthreads) {
     double* b = G.belief + (size_t)w * IG_BEL * IG_BEL;
     double* m = G.mi + (size_t)w * IG_BEL * IG_BEL;
     const double mi1 = ig_cell_mi(1.0);
-    for (int q = threadIdx.x; q < IG_BEL * IG_BEL; q += blockDim.x) { b[q] = 1.0; m[q] = mi1; }  // prior (targetMap.py:8)
+    for (int q = tid; q < IG_BEL * IG_BEL; q += nthreads) { b[q] = 1.0; m[q] = mi1; }  // prior (targetMap.py:8)
+}
+
+__global__ void __launch_bounds__(256) k_ig_fill_belief(IgDev G, const uint8_t* mask) {
+    const int w = blockIdx.x;
+    if (mask && !mask[w]) return;
+    ig_fill_world_prior(G, w, threadIdx.x, blockDim.x);
 }
 
 __global__ void __launch_bounds__(128) k_ig_visible(IgDev G, const double* poses, const int32_t* world, double fov,

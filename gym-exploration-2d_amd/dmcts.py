@@ -288,9 +288,16 @@ class DeviceDecMCTSPlanner(object):
         self.stats = torch.zeros((self.N, self.R, 3), dtype=torch.float64, device=dev)
         self.calls = 0
 
-    def reset(self):
-        """Forget the communicated plans at the next plan() (new episode)."""
-        self.P.reset_comms = 1
+    def reset(self, world_mask=None):
+        """Forget the communicated plans (new episode).  None: of every world, at the next plan().  A DEVICE mask [N] (uint8 /
+        bool): of exactly those worlds, now, by one launch on the current stream (cagym_ig_episode_boundary, plans only) - the
+        counterpart of DecMCTSPlanner.reset(worlds=...)."""
+        if world_mask is None:
+            self.P.reset_comms = 1
+            return
+        from .ig import EPISODE_PLANS_ONLY
+        m = self._torch.as_tensor(world_mask, device=self.b.device).to(self._torch.uint8).reshape(self.N).contiguous()
+        self.ig.episode_boundary(self.P, self.workspace, None, m, EPISODE_PLANS_ONLY)
 
     @property
     def parallelize_agents(self):

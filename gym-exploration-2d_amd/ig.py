@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 
+EPISODE_FOLD, EPISODE_PLANS_ONLY = 1, 2  # CAGYM_IG_EPISODE_* (include/cagym.h)
 FOV_DEG60 = 60.0 * np.pi / 180  # detect_fov=60.0 -> targetMap.sensFOV (ig_mcts.py:67)
 PRIMITIVES = np.array([[v, w] for v in (0.0, 2.0, 4.0) for w in (-0.5 * np.pi, 0.0, 0.5 * np.pi)])  # ig_mcts.py:247-253
 
@@ -33,6 +34,8 @@ class InfoGain(object):
         L.cagym_ig_rollouts.argtypes = [vp] * 7 + [C.c_int] * 4 + [C.c_double] * 3 + [C.c_uint64, vp, vp, vp, vp, vp]
         L.cagym_ig_robot_inputs.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
         L.cagym_ig_robot_actions.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.cagym_ig_get_episode_stats.argtypes = [vp] + [C.POINTER(vp)] * 4
+        L.cagym_ig_episode_boundary.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
         with torch.cuda.device(benv.device):
             _lib.check(L, benv.h, L.cagym_ig_init(benv.h, benv._stream()), "cagym_ig_init")
         d2, bel = vp(), vp()
@@ -40,6 +43,11 @@ class InfoGain(object):
         from .batched_env import _DevArray
         self.edf_d2 = torch.as_tensor(_DevArray(d2.value, (benv.S, 300, 300), "i4"), device=benv.device)
         self.belief = torch.as_tensor(_DevArray(bel.value, (benv.N, 60, 60), "f8"), device=benv.device)
+        acc = [vp() for _ in range(4)]
+        _lib.check(L, benv.h, L.cagym_ig_get_episode_stats(benv.h, *[C.byref(a) for a in acc]), "cagym_ig_get_episode_stats")
+        # the team reward's per-world episode accumulators (cagym_ig_episode_boundary); zeroed by cagym_ig_init
+        self.episode_stats = {k: torch.as_tensor(_DevArray(a.value, (benv.N,), ts), device=benv.device)
+                              for k, a, ts in zip(("running", "sum", "last", "episodes"), acc, ("f8", "f8", "f8", "i4"))}
 
     def _t(self, x, dtype, shape=None):
         t = torch.as_tensor(x, device=self.b.device).to(dtype)
@@ -69,6 +77,19 @@ class InfoGain(object):
             rc = self.L.cagym_ig_reset_belief(self.b.h, None if m is None else m.data_ptr(), self.b._stream())
         _lib.check(self.L, self.b.h, rc, "cagym_ig_reset_belief")
 
+    def episode_boundary(self, params, workspace, team_reward=None, restart_mask=None, flags=0):
+        """cagym_ig_episode_boundary on the current stream: running += team_reward [N] f64; the worlds of the DEVICE mask
+        restart_mask [N] u8 get a prior belief, no communicated plans (params / workspace: the planner's) and running = 0, after
+        folding it into sum / last / episodes with EPISODE_FOLD.  EPISODE_PLANS_ONLY: only the plans are forgotten."""
+        if restart_mask is not None and (restart_mask.dtype != torch.uint8 or not restart_mask.is_cuda or not restart_mask.is_contiguous()):
+            restart_mask = self._t(restart_mask, torch.uint8, (self.b.N,))
+        if team_reward is not None and (team_reward.dtype != torch.float64 or not team_reward.is_contiguous()):
+            team_reward = self._t(team_reward, torch.float64, (self.b.N,))
+        rc = self.L.cagym_ig_episode_boundary(self.b.h, C.byref(params), None if team_reward is None else team_reward.data_ptr(),
+                                              None if restart_mask is None else restart_mask.data_ptr(), int(flags),
+                                              workspace.data_ptr(), workspace.numel(), self.b._stream())
+        _lib.check(self.L, self.b.h, rc, "cagym_ig_episode_boundary")
+
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
         world = self._t(world, torch.int32, (-1,))
@@ -97,10 +118,12 @@ class InfoGain(object):
         _lib.check(self.L, self.b.h, rc, "cagym_ig_update_belief")
         return obs
 
-    def mi_reward(self, masks, world):
+    def mi_reward(self, masks, world, out=None):
+        """out: a contiguous f64 [Q] device tensor to write into (default: a new one)."""
         masks = self._t(masks, torch.int64, (-1, 60))
         world = self._t(world, torch.int32, (-1,))
-        out = torch.empty((masks.shape[0],), dtype=torch.float64, device=self.b.device)
+        if out is None:
+            out = torch.empty((masks.shape[0],), dtype=torch.float64, device=self.b.device)
         with torch.cuda.device(self.b.device):
             rc = self.L.cagym_ig_mi_reward(self.b.h, masks.data_ptr(), world.data_ptr(), masks.shape[0],
                                            out.data_ptr(), self.b._stream())

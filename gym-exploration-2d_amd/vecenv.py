@@ -95,10 +95,14 @@ class CagymVecEnv(object):
 
     def step_wait(self):
         b = self.b
-        # DummyVecEnv auto-reset inside the launch; an attached GA3C policy fills its agents' rows (BatchedCollisionAvoidanceEnv.step)
+        # DummyVecEnv auto-reset inside the launch; an attached GA3C policy or (episodic) ig_mcts team fills its agents' rows and
+        # restarts with its worlds (BatchedCollisionAvoidanceEnv.step)
         _, rew, go, info = b.step(self._external(self._actions), auto_reset=True)
         rews = rew[:, 0] if self.single_agent else rew
-        return self.flat(), rews, go.bool(), {"flags": info["flags"]}
+        infos = {"flags": info["flags"]}
+        if getattr(b, "_igm", None) is not None:  # an episodic attach_ig_mcts: the team's MI reward of this step, [N] f64
+            infos["team_reward"] = b.team_reward
+        return self.flat(), rews, go.bool(), infos
 
     def step(self, actions):
         self.step_async(actions)

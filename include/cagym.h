@@ -241,6 +241,11 @@ int cagym_ig_reset_belief(void* env, const uint8_t* world_mask, void* stream);
  * changes through cagym_ig_reset_belief / cagym_ig_update_belief only: the library keeps the per-cell mutual information of the
  * belief beside it (the reward sums of cagym_ig_mi_reward / cagym_ig_rollouts / cagym_dmcts_plan read that cache). */
 int cagym_ig_get(void* env, uint32_t** edf_d2, double** belief);
+/* Zero-copy DEVICE views of the team reward's per-world episode accumulators (cagym_ig_episode_boundary keeps them): running [N]
+ * f64 = sum of the team reward over the steps of the episode in progress, sum [N] f64 = sum of the finished episodes' returns,
+ * last [N] f64 = return of the last finished episode, episodes [N] i32 = finished episodes.  Owned by the handle, allocated with
+ * the IG state, zeroed by every cagym_ig_init.  Any pointer may be NULL. */
+int cagym_ig_get_episode_stats(void* env, double** running, double** sum, double** last, int32_t** episodes);
 /* targetMap.getVisibleCells (targetMap.py:43-84) for Q poses (x, y, phi) of worlds world[q]. */
 int cagym_ig_visible_cells(void* env, const double* poses, const int32_t* world, int Q, double fov_rad,
                            double range, uint64_t* masks, void* stream);
@@ -408,6 +413,31 @@ int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const fl
 int cagym_ig_robot_actions(void* env, int n_robots, const double* planner_actions, float* actions, void* stream);
 int cagym_dmcts_plan(void* env, const cagym_dmcts_params* params, const double* poses, void* workspace,
                      size_t workspace_bytes, double* actions, uint8_t* paths, double* stats, void* stream);
+
+/* The episode boundary of the IG team, per world: ONE launch (one workgroup per world) on `stream`, to be enqueued behind the step
+ * (cagym_step_autoreset) that ended the episodes.  team_reward DEVICE [N] f64 (cagym_ig_mi_reward of this step's observation) or
+ * NULL; restart_mask DEVICE [N] u8 or NULL - in a stepping loop the game_over output the step just wrote; workspace: the planner's
+ * (cagym_dmcts_plan), params: the planner's (n_robots, Ntree, Ncycles and parallel_agents locate the publications; the rest is
+ * not read).  For every world w, in this order:
+ *   running[w] += team_reward[w]                       (fp64, in step order; skipped when team_reward is NULL)
+ *   if restart_mask[w]:
+ *     with CAGYM_IG_EPISODE_FOLD: sum[w] += running[w], last[w] = running[w], episodes[w] += 1  (the terminal step's reward
+ *       belongs to the episode that ends); without it (a manual restart) they are left alone;
+ *     running[w] = 0;
+ *     the world's belief returns to the prior (the doubles of cagym_ig_reset_belief) - the next cagym_ig_update_belief is the
+ *       first observation of the new episode, on the distance field of the world's new scenario;
+ *     its n_robots communicated plans are forgotten: its robots hear nothing in cycle 0 of the next cagym_dmcts_plan, in
+ *       either mode, a mode switch included (a workspace sized for mode 1 has the second publication buffer cleared too).
+ * Nothing of a world that is not masked is touched except running[w].  A NULL mask restarts nothing: the call only accumulates.
+ * CAGYM_IG_EPISODE_PLANS_ONLY: the masked worlds only lose their communicated plans (what reset_comms does to all worlds, at
+ * once instead of at the next plan); beliefs and all four accumulators stay, team_reward is not read.
+ * Nothing else of the planner survives a planning step (trees, counters and distributions are rebuilt by cycle 0), and the
+ * generator keys keep running on call_base.  Errors as cagym_dmcts_plan: CAGYM_E_STATE before cagym_ig_init, CAGYM_E_INVALID for
+ * a NULL params / workspace, n_robots, Ntree or Ncycles out of range, parallel_agents > 1, unknown flags, or a workspace smaller
+ * than cagym_dmcts_workspace_bytes(n_worlds, params). */
+enum { CAGYM_IG_EPISODE_FOLD = 1, CAGYM_IG_EPISODE_PLANS_ONLY = 2 };
+int cagym_ig_episode_boundary(void* env, const cagym_dmcts_params* params, const double* team_reward, const uint8_t* restart_mask,
+                              uint32_t flags, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
