@@ -279,21 +279,45 @@ class BatchedCollisionAvoidanceEnv(object):
         cycle hears nothing (DummyVecEnv's reset() builds new ig_mcts objects).  rollout() chains such steps; CagymVecEnv works.
         reset(world_mask=m) restarts the masked worlds alone and zeroes their running return without counting an episode;
         reset() restarts everything and zeroes every running return."""
-        from .ig import InfoGain
         from .dmcts import DeviceDecMCTSPlanner
+        g = self._ig_state("ig_mcts", detect_fov, detect_range, xdt, episodic)
+        g.planner = DeviceDecMCTSPlanner(g.ig, g.R, radius=radius, Ntree=Ntree, Nsims=Nsims, horizon=mcts_horizon, c_p=mcts_cp,
+                                         gamma=mcts_gamma, Ncycles=Ncycles, seed=seed, parallelize_agents=parallelize_agents)
+        self._igm = g
+        self._alloc_act()
+        return g.planner
+
+    def _ig_state(self, kind, detect_fov, detect_range, xdt, episodic):
+        """What step() needs of an attached IG policy, whichever it is: the primitives and the robots' input buffers."""
+        from .ig import InfoGain
         R = self._n_ig if self._n_ig is not None else 0
         self._igm = None
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
         N, K, dev = self.N, self.K, self.device
         g = type("IgState", (), {})()
-        g.ig, g.R, g.range, g.episodic = ig, R, float(detect_range), bool(episodic)
+        g.kind, g.ig, g.R, g.range, g.episodic = kind, ig, R, float(detect_range), bool(episodic)
         g.poses = torch.zeros((N, max(R, 1), 3), dtype=torch.float64, device=dev)
         g.det = torch.zeros((N, max(R, 1), K, 2), dtype=torch.float64, device=dev)
         g.n_det = torch.zeros((N, max(R, 1)), dtype=torch.int32, device=dev)
         g.world = torch.arange(N, dtype=torch.int32, device=dev)
         ig.robot_inputs(R, g.range, self.obs_oas, g.poses, g.det, g.n_det)  # refuses a pool without R robots in every scenario
-        g.planner = DeviceDecMCTSPlanner(ig, R, radius=radius, Ntree=Ntree, Nsims=Nsims, horizon=mcts_horizon, c_p=mcts_cp,
-                                         gamma=mcts_gamma, Ncycles=Ncycles, seed=seed, parallelize_agents=parallelize_agents)
+        return g
+
+    def attach_ig_greedy(self, detect_fov=60.0, detect_range=5.0, radius=0.5, coordinate=False, episodic=False):
+        """From now on step() chooses the (v, omega) of every IG robot by the one-step greedy rule of policies/ig_greedy.py
+        (find_next_action with the intended update([pose], [targets])): robot poses and detections
+        (cagym_ig_robot_inputs), belief update, the team's MI reward into self.team_reward, ONE cagym_ig_greedy_plan launch, the
+        robots' rows of the action table (cagym_ig_robot_actions), then the step - attach_ig_mcts's sequence with the greedy
+        plan in place of the Dec-MCTS one, and it replaces an attached ig_mcts (attach_ig_mcts replaces this; detach_ig_mcts
+        clears either).  One belief per world, shared by its robots; coordinate=True lets a world's robots choose in slot order,
+        each without the cells the earlier ones chose (the reference's robots each own a map and cannot collide on cells).
+        episodic: as attach_ig_mcts (the policy keeps nothing across steps, so a restart is the belief and the running return).
+        Returns the ig.GreedyPlanner, which holds the last plan's choice / mi / claimed."""
+        from .ig import GreedyPlanner
+        if self._n_ig is not None and self._n_ig > 8:
+            raise ValueError("attach_ig_greedy: at most 8 IG robots per world (cagym_ig_greedy_plan), the pool has %d" % self._n_ig)
+        g = self._ig_state("ig_greedy", detect_fov, detect_range, 1, episodic)
+        g.planner = GreedyPlanner(g.ig, g.R, radius=radius, coordinate=coordinate)
         self._igm = g
         self._alloc_act()
         return g.planner
@@ -314,7 +338,7 @@ class BatchedCollisionAvoidanceEnv(object):
         running [N] f64 team return of the episode in progress, sum [N] f64 over the finished episodes, last [N] f64 return of
         the last finished one, episodes [N] i32 finished episodes."""
         if self._igm is None:
-            raise RuntimeError("ig_episode_stats() needs attach_ig_mcts")
+            raise RuntimeError("ig_episode_stats() needs attach_ig_mcts or attach_ig_greedy")
         return dict(self._igm.ig.episode_stats)
 
     def _internal_actions(self, a, team_reward_out=None, oas=None):
@@ -346,9 +370,10 @@ class BatchedCollisionAvoidanceEnv(object):
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
-            raise RuntimeError("step(auto_reset=True) with ig_mcts attached: the planner's per-world restart (beliefs, "
-                               "communicated plans) is not implemented for this attach; attach_ig_mcts(episodic=True), or step "
-                               "without auto-reset and reset() yourself")
+            k = self._igm.kind
+            raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
+                               "communicated plans) is not implemented for this attach; attach_%s(episodic=True), or step "
+                               "without auto-reset and reset() yourself" % (k, k))
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
@@ -429,10 +454,14 @@ class BatchedCollisionAvoidanceEnv(object):
         update, team reward into out["team_reward"][t], plan, robot actions, step, episode boundary), no host synchronisation
         either; not under stream capture (the planner's call_base is a kernel argument the host advances per call)."""
         if self._igm is not None and not self._igm.episodic:
-            raise RuntimeError("rollout() with ig_mcts attached is not implemented for this attach (the planner needs per-world "
-                               "restarts): attach_ig_mcts(episodic=True)")
+            k = self._igm.kind
+            raise RuntimeError("rollout() with %s attached is not implemented for this attach (the planner needs per-world "
+                               "restarts): attach_%s(episodic=True)" % (k, k))
         if self._igm is not None:
             if torch.cuda.is_current_stream_capturing():
+                if self._igm.kind == "ig_greedy":
+                    raise RuntimeError("rollout() with ig_greedy attached cannot be captured in a graph: the chain allocates its "
+                                       "observed-set buffers per step and has not been validated under capture")
                 raise RuntimeError("rollout() with ig_mcts attached cannot be captured in a graph: the planner's call_base is a "
                                    "by-value kernel argument that the host advances with every planning step")
             if out is None:

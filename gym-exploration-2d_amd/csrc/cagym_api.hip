@@ -1,6 +1,7 @@
 // cagym_api.hip -- C ABI of libcagym_hip.so (include/cagym.h): handle, device buffers, launches.
 // No torch types, no CPU fallback: without a HIP device cagym_create fails.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -24,6 +25,7 @@
 #include "cagym_gen2.h"
 #include "cagym_dmcts.h"
 #include "cagym_ig_episode.h"
+#include "cagym_ig_greedy.h"
 
 namespace {
 
@@ -1288,6 +1290,31 @@ int cagym_ig_episode_boundary(void* env, const cagym_dmcts_params* params, const
     DmPublished* pub2 = has_pub2 ? reinterpret_cast<DmPublished*>(base + dm_align(seq_bytes)) : nullptr;
     hipLaunchKernelGGL(k_ig_episode_boundary, dim3((unsigned)N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->G, e->ig_ep,
                        p.n_robots, (unsigned int)flags, team_reward, restart_mask, pub, pub2);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const double* poses, double* actions, uint8_t* choice,
+                         double* mi, uint64_t* claimed, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_greedy_plan");
+    ON_DEVICE(e);
+    if (!params || !poses || !actions || !choice) return fail(e, CAGYM_E_INVALID, "null argument");
+    const cagym_ig_greedy_params& p = *params;
+    if (p.n_robots < 1 || p.n_robots > DM_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: n_robots must be 1..8");
+    if (p.coordinate != 0 && p.coordinate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: coordinate must be 0 or 1");
+    // (the negated comparisons refuse NaN)
+    if (!(p.dt > 0.0 && p.fov_rad > 0.0 && p.range > 0.0 && p.radius >= 0.0) || !std::isfinite(p.dt) || !std::isfinite(p.fov_rad) ||
+        !std::isfinite(p.range) || !std::isfinite(p.radius))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: dt, fov_rad and range must be finite and positive, radius finite and not negative");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(p.v[k]) || !std::isfinite(p.w[k])) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: non-finite candidate");
+    IgGreedyParams P;
+    P.R = p.n_robots; P.coordinate = p.coordinate; P.dt = p.dt; P.radius = p.radius; P.fov = p.fov_rad; P.range = p.range;
+    P.v0 = p.v[0]; P.v1 = p.v[1]; P.v2 = p.v[2]; P.w0 = p.w[0]; P.w1 = p.w[1]; P.w2 = p.w[2];
+    const size_t N = (size_t)e->cfg.n_worlds;
+    hipLaunchKernelGGL(k_ig_greedy, dim3((unsigned)(p.coordinate ? N : N * p.n_robots)), dim3(IGG_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), e->G, P, poses, actions, choice, mi,
+                       reinterpret_cast<unsigned long long*>(claimed));
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

@@ -56,6 +56,15 @@ class GA3CCADRLPolicy(_Policy):
     policy_id, str = sc.POLICY_GA3C, "GA3C_CADRL"
 
 
+def _check_ig_map(who, map_size, map_res):
+    """The device belief grid and distance field are fixed to the reference's map: other values are refused."""
+    if tuple(np.asarray(map_size, dtype=np.float64).ravel()) != (float(Config.MAP_WIDTH), float(Config.MAP_HEIGHT)):
+        raise ValueError("%s: map_size must be (Config.MAP_WIDTH, Config.MAP_HEIGHT) = (%r, %r), got %r"
+                         % (who, Config.MAP_WIDTH, Config.MAP_HEIGHT, map_size))
+    if float(map_res) != float(Config.SUBMAP_RESOLUTION):
+        raise ValueError("%s: map_res must be Config.SUBMAP_RESOLUTION = %r, got %r" % (who, Config.SUBMAP_RESOLUTION, map_res))
+
+
 class ig_mcts(_Policy):
     """Marker of policies/ig_mcts.py.  set_param records the planner parameters; the env plans every robot inside step()
     (BatchedCollisionAvoidanceEnv.attach_ig_mcts) and writes the world's team reward to `team_reward` after each step."""
@@ -75,16 +84,33 @@ class ig_mcts(_Policy):
         (Config.MAP_WIDTH x MAP_HEIGHT at SUBMAP_RESOLUTION), so other values are refused; occ_map is the env's raster
         (env.map) and is not copied.  parallelize_sims is ignored: every tree grow runs its Nsims roll-outs in parallel on the
         device anyway.  The planner's random streams are seeded (CollisionAvoidanceEnv.planner_seed), not np.random."""
-        if tuple(np.asarray(map_size, dtype=np.float64).ravel()) != (float(Config.MAP_WIDTH), float(Config.MAP_HEIGHT)):
-            raise ValueError("ig_mcts.set_param: map_size must be (Config.MAP_WIDTH, Config.MAP_HEIGHT) = (%r, %r), got %r"
-                             % (Config.MAP_WIDTH, Config.MAP_HEIGHT, map_size))
-        if float(map_res) != float(Config.SUBMAP_RESOLUTION):
-            raise ValueError("ig_mcts.set_param: map_res must be Config.SUBMAP_RESOLUTION = %r, got %r"
-                             % (Config.SUBMAP_RESOLUTION, map_res))
+        _check_ig_map("ig_mcts.set_param", map_size, map_res)
         self.ego_agent = ego_agent
         self.params = {"detect_fov": float(detect_fov), "detect_range": float(detect_range), "dt": float(dt), "xdt": int(xdt),
                        "Ntree": int(Ntree), "Nsims": int(Nsims), "mcts_cp": float(mcts_cp), "mcts_horizon": int(mcts_horizon),
                        "mcts_gamma": float(mcts_gamma), "Ncycles": int(Ncycles), "parallelize_agents": bool(parallelize_agents)}
+
+
+class ig_greedy(_Policy):
+    """Marker of policies/ig_greedy.py, the one-step greedy baseline of ig_mcts.  init_maps records the detector; the env
+    chooses every robot's action inside step() (BatchedCollisionAvoidanceEnv.attach_ig_greedy) and writes the world's team
+    reward to `team_reward` after each step."""
+    policy_id, str = sc.POLICY_IGMCTS, "ig_greedy"  # the robots' slots are the ones the step reads from the action table
+
+    def __init__(self):
+        self.params = None
+        self.ego_agent = None
+        self.team_reward = None
+
+    def init_maps(self, ego_agent, occ_map, map_size, map_res, detect_fov, detect_range, dt=0.1):
+        """ig_greedy.init_maps (ig_greedy.py:18-30); map_size, map_res and dt are checked as ig_mcts.set_param checks them."""
+        _check_ig_map("ig_greedy.init_maps", map_size, map_res)
+        self.ego_agent = ego_agent
+        self.params = {"detect_fov": float(detect_fov), "detect_range": float(detect_range), "dt": float(dt),
+                       "radius": float(getattr(ego_agent, "radius", 0.5))}
+
+
+_IG_POLICIES = (ig_mcts, ig_greedy)
 
 
 class UnicycleDynamics(object):
@@ -376,8 +402,8 @@ class CollisionAvoidanceEnv(object):
         if n > M:
             raise ValueError("more agents than Config.MAX_NUM_AGENTS_IN_ENVIRONMENT")
         rects = self._rects(self.default_obstacles)
-        if any(isinstance(a.policy, ig_mcts) for a in specs) and len(rects) == 0:
-            raise ValueError("ig_mcts agents need a world with obstacles: the information-gain primitives work on its raster")
+        if any(isinstance(a.policy, _IG_POLICIES) for a in specs) and len(rects) == 0:
+            raise ValueError("ig_mcts / ig_greedy agents need a world with obstacles: the information-gain primitives work on its raster")
         laser = any(isinstance(s, LaserScanSensor) for a in specs for s in a.sensors)
         sig = (M, max(len(rects), 0), laser, self._game_over_mode(), Config.COLLISION_AV_W_STATIC_AGENT, Config.DT)
         if self._benv is None or sig != self._sig:
@@ -409,7 +435,7 @@ class CollisionAvoidanceEnv(object):
             mo = min(int(Config.MAX_NUM_OTHER_AGENTS_OBSERVED), M - 1, 10)
             if self._benv._ga3c is None or self._benv._ga3c.max_observed != mo:
                 self._benv.attach_ga3c("iros18", max_observed=mo)
-        if not any(isinstance(a.policy, ig_mcts) for a in specs) and self._benv._igm is not None:
+        if not any(isinstance(a.policy, _IG_POLICIES) for a in specs) and self._benv._igm is not None:
             self._benv.detach_ig_mcts()
             self._ig_key = None
         self._benv.reset()
@@ -439,8 +465,12 @@ class CollisionAvoidanceEnv(object):
                     continue
                 v = np.atleast_1d(np.asarray(v, dtype=np.float32)).ravel()
                 ext[0, i, :min(2, v.size)] = v[:2]
-        robots = [a.policy for a in self.agents if isinstance(a.policy, ig_mcts)]
-        if robots:
+        robots = [a.policy for a in self.agents if isinstance(a.policy, _IG_POLICIES)]
+        if robots and any(type(p) is not type(robots[0]) for p in robots[1:]):
+            raise ValueError("ig_mcts and ig_greedy agents cannot share an env: one policy drives the whole team")
+        if robots and isinstance(robots[0], ig_greedy):
+            self._attach_greedy(robots)
+        elif robots:
             self._attach_planner(robots)
         self.episode_step_number += 1
         self.total_number_of_steps += 1
@@ -473,6 +503,23 @@ class CollisionAvoidanceEnv(object):
             p = dict(params)
             del p["dt"]
             self._benv.attach_ig_mcts(seed=self.planner_seed, **p)
+            self._ig_key = key
+
+
+    def _attach_greedy(self, robots):
+        """The robots' common init_maps values drive one greedy policy per env (attached again when they change)."""
+        if any(p.params is None for p in robots):
+            raise RuntimeError("an ig_greedy agent has no maps: call policy.init_maps(...) after reset() and before step()")
+        params = robots[0].params
+        if any(p.params != params for p in robots[1:]):
+            raise ValueError("all ig_greedy agents of the env must share the same init_maps values and radius "
+                             "(one launch chooses for the whole team)")
+        if params["dt"] != self._sig[5]:
+            raise ValueError("ig_greedy.init_maps: dt must equal Config.DT")
+        key = ("ig_greedy", tuple(sorted(params.items())), len(robots))
+        if self._ig_key != key or self._benv._igm is None:
+            self._benv.attach_ig_greedy(detect_fov=params["detect_fov"], detect_range=params["detect_range"],
+                                        radius=params["radius"])
             self._ig_key = key
 
 

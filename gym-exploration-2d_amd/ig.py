@@ -15,6 +15,13 @@ from . import _lib
 EPISODE_FOLD, EPISODE_PLANS_ONLY = 1, 2  # CAGYM_IG_EPISODE_* (include/cagym.h)
 FOV_DEG60 = 60.0 * np.pi / 180  # detect_fov=60.0 -> targetMap.sensFOV (ig_mcts.py:67)
 PRIMITIVES = np.array([[v, w] for v in (0.0, 2.0, 4.0) for w in (-0.5 * np.pi, 0.0, 0.5 * np.pi)])  # ig_mcts.py:247-253
+GREEDY_V, GREEDY_W = (0.0, 2.0, 4.0), (-np.pi, 0.0, np.pi)  # ig_greedy.py:65-66: candidate c = 3 a + b is (v[a], w[b])
+
+
+class GreedyParams(C.Structure):
+    """cagym_ig_greedy_params (include/cagym.h)."""
+    _fields_ = [("n_robots", C.c_int32), ("coordinate", C.c_int32)] + \
+               [(n, C.c_double) for n in ("dt", "radius", "fov_rad", "range")] + [("v", C.c_double * 3), ("w", C.c_double * 3)]
 
 
 class InfoGain(object):
@@ -36,6 +43,7 @@ class InfoGain(object):
         L.cagym_ig_robot_actions.argtypes = [vp, C.c_int, vp, vp, vp]
         L.cagym_ig_get_episode_stats.argtypes = [vp] + [C.POINTER(vp)] * 4
         L.cagym_ig_episode_boundary.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
+        L.cagym_ig_greedy_plan.argtypes = [vp, C.POINTER(GreedyParams), vp, vp, vp, vp, vp, vp]
         with torch.cuda.device(benv.device):
             _lib.check(L, benv.h, L.cagym_ig_init(benv.h, benv._stream()), "cagym_ig_init")
         d2, bel = vp(), vp()
@@ -145,6 +153,31 @@ class InfoGain(object):
         _lib.check(self.L, self.b.h, rc, "cagym_ig_next_pose")
         return nxt, ok
 
+    def greedy_plan(self, poses, coordinate=False, radius=0.5, v=GREEDY_V, w=GREEDY_W, out=None):
+        """cagym_ig_greedy_plan: ig_greedy.greedy_action for the R robots of every world, poses [N,R,3] f64 (a contiguous device
+        tensor is taken as it is).  One launch on the current stream, no synchronisation.  coordinate=True: a world's robots
+        choose in slot order, each without the cells the earlier ones chose.  Returns the dict of device tensors it wrote:
+        actions [N,R,2] f64, choice [N,R] u8 (255: no feasible candidate), mi [N,R,9] f64 (-1: infeasible), claimed [N,60] i64;
+        `out`: such a dict to write into again (default: new tensors)."""
+        N, dev = self.b.N, self.b.device
+        if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous()):
+            poses = self._t(poses, torch.float64)
+        poses = poses.reshape(N, -1, 3)
+        R = poses.shape[1]
+        if out is None:
+            out = {"actions": torch.empty((N, R, 2), dtype=torch.float64, device=dev),
+                   "choice": torch.empty((N, R), dtype=torch.uint8, device=dev),
+                   "mi": torch.empty((N, R, 9), dtype=torch.float64, device=dev),
+                   "claimed": torch.empty((N, 60), dtype=torch.int64, device=dev)}
+        P = GreedyParams(R, int(bool(coordinate)), self.dt, float(radius), self.fov, self.range,
+                         (C.c_double * 3)(*[float(x) for x in v]), (C.c_double * 3)(*[float(x) for x in w]))
+        ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
+        with torch.cuda.device(dev):
+            rc = self.L.cagym_ig_greedy_plan(self.b.h, C.byref(P), poses.data_ptr(), ptr("actions"), ptr("choice"), ptr("mi"),
+                                             ptr("claimed"), self.b._stream())
+        _lib.check(self.L, self.b.h, rc, "cagym_ig_greedy_plan")
+        return out
+
     def rollouts(self, pose0, observed0, exclude, world, n_steps, radius, nsims, seed, max_steps=None,
                  want_observed=False):
         """nsims random roll-outs per query; returns (rewards [Q,nsims], actions [Q,nsims,H], final_pose) and, with
@@ -169,6 +202,34 @@ class InfoGain(object):
                                           None if obs_out is None else obs_out.data_ptr(), self.b._stream())
         _lib.check(self.L, self.b.h, rc, "cagym_ig_rollouts")
         return (rew, acts, fin, obs_out) if want_observed else (rew, acts, fin)
+
+
+class GreedyPlanner(object):
+    """The greedy policy of a handle's IG robots (BatchedCollisionAvoidanceEnv.attach_ig_greedy): plan() is one
+    cagym_ig_greedy_plan launch; `choice` [N,R] u8, `mi` [N,R,9] f64, `claimed` [N,60] i64 and `actions` [N,R,2] f64 hold the
+    last plan.  The policy keeps nothing across steps.  P / workspace: a minimum-size Dec-MCTS parameter block and workspace,
+    there solely so that cagym_ig_episode_boundary finds publications to clear when it restarts a world."""
+
+    def __init__(self, ig, n_robots, radius=0.5, coordinate=False):
+        from .dmcts import DmctsParams
+        self.ig, self.R = ig, int(n_robots)
+        self.radius, self.coordinate = float(radius), bool(coordinate)
+        self.P = DmctsParams(self.R, 1, 1, 1, 1, 1, ig.xdt, 1, 0, 0, 1.0, 1.0, self.radius, ig.dt, ig.fov, ig.range, 0)
+        ig.L.cagym_dmcts_workspace_bytes.restype = C.c_size_t
+        ig.L.cagym_dmcts_workspace_bytes.argtypes = [C.c_int, C.POINTER(DmctsParams)]
+        self.workspace = torch.zeros(ig.L.cagym_dmcts_workspace_bytes(ig.b.N, C.byref(self.P)), dtype=torch.uint8, device=ig.b.device)
+        self._out = None
+        self.actions = self.choice = self.mi = self.claimed = None
+
+    def reset(self, world_mask=None):
+        """Nothing to forget: every plan starts from the poses and the belief alone."""
+
+    def plan(self, poses):
+        """poses [N,R,3].  Returns device tensors (actions [N,R,2], choice [N,R] u8)."""
+        self._out = self.ig.greedy_plan(poses, coordinate=self.coordinate, radius=self.radius, out=self._out)
+        o = self._out
+        self.actions, self.choice, self.mi, self.claimed = o["actions"], o["choice"], o["mi"], o["claimed"]
+        return self.actions, self.choice
 
 
 def find_targets_in_obs(other_agents_states, detect_range=5.0):

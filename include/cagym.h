@@ -439,6 +439,36 @@ enum { CAGYM_IG_EPISODE_FOLD = 1, CAGYM_IG_EPISODE_PLANS_ONLY = 2 };
 int cagym_ig_episode_boundary(void* env, const cagym_dmcts_params* params, const double* team_reward, const uint8_t* restart_mask,
                               uint32_t flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The one-step greedy information-gain policy (policies/ig_greedy.py:64-94) for every IG robot of every world -------------
+ * ONE launch, no host synchronisation.  poses DEVICE [N,R,3] (x, y, heading; cagym_ig_robot_inputs writes this layout).  Per robot
+ * and candidate c = 3 a + b = (v[a], w[b]), in this order (the reference: v = {0, 2, 4}, w = {-pi, 0, pi}, ig_greedy.py:65-68):
+ *   next = pose + (v cos(heading), v sin(heading), w) dt    (one Euler step, the arithmetic of cagym_ig_next_pose's sub-step);
+ *   feasible <=> EDF(next) > radius + 0.1 on the distance field of the world's current scenario, for v = 0 as well;
+ *   mi[c] = sum of cell MI over getVisibleCells(next) on the world's current belief; an infeasible candidate gets -1.0 (cell MI is
+ *   never negative).  The first candidate with strictly the largest mi wins (the running maximum starts at -1).
+ * Outputs DEVICE: actions [N,R,2] f64 = the winner's (v, w), choice [N,R] u8 = its index, mi [N,R,9] f64 (may be NULL),
+ * claimed [N,60] u64 (may be NULL; see coordinate).  Deviations from the reference: a candidate whose next cell
+ * lies outside the 300 x 300 raster is infeasible (the reference wraps a negative index and raises beyond 299); with no feasible
+ * candidate choice = 255 and the action is (0, 0) (the reference returns the scalar -1).
+ * coordinate = 0: every robot on its own, as in the reference; one workgroup per (world, robot); claimed is written as the empty set.
+ * coordinate = 1 (not in the reference, whose robots each own a map; here a world's robots share one belief): the robots of a
+ *   world go in slot order with a claimed set that starts empty; robot k's mi[c] sums over visible(next_c) & ~claimed (the set
+ *   difference of mcts_reward, ig_mcts.py:234-241), and after its choice claimed |= visible(next_best); a robot with choice 255
+ *   claims nothing; claimed out is the final set.  Robot 0's results are those of coordinate = 0.  One workgroup per world.
+ * The masks are those of cagym_ig_visible_cells and every mi[c] is, bit for bit, what cagym_ig_mi_reward returns for the same mask
+ * (after & ~claimed); the same call twice writes identical bytes.
+ * Errors: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params / poses / actions / choice, n_robots outside 1..8,
+ * coordinate outside {0, 1}, a non-finite or non-positive dt, fov_rad or range, a negative or non-finite radius, a non-finite
+ * candidate; CAGYM_E_DEVICE as every launching entry. */
+typedef struct cagym_ig_greedy_params {
+    int32_t n_robots;   /* 1..8, as cagym_dmcts_plan */
+    int32_t coordinate; /* 0: every robot on its own (the reference); 1: sequential team allocation */
+    double dt, radius, fov_rad, range;
+    double v[3], w[3];
+} cagym_ig_greedy_params;
+int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const double* poses, double* actions, uint8_t* choice,
+                         double* mi, uint64_t* claimed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
