@@ -57,10 +57,22 @@ class CagymScenarioPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("agents6", "policy", "dynamics", "n_agents", "coop")]
 
 
+EPREC_KEEP = {"first": 0, "last": 1}  # CAGYM_EPREC_KEEP_*
+# cagym_episode_record_ptrs: (field, typestr, shape in terms of S / N / M)
+EPREC_FIELDS = [("t", "f8", "SM"), ("extra_t", "f8", "SM"), ("flags", "u1", "SM"), ("ret", "f8", "S"), ("steps", "i4", "S"),
+                ("outcome", "i4", "S"), ("count", "i4", "S"), ("t_run", "f8", "NM"), ("ret_run", "f8", "N"),
+                ("steps_run", "i4", "N"), ("atgoal_run", "u4", "N"), ("cursor", "i4", "N"), ("desync", "i4", "1")]
+
+
+class CagymEpisodeRecordPtrs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _, _ in EPREC_FIELDS]
+
+
 EXPORTS = ["cagym_version", "cagym_create", "cagym_destroy", "cagym_last_error", "cagym_set_scenarios",
            "cagym_reset", "cagym_step", "cagym_step_autoreset", "cagym_step_begin", "cagym_step_finish", "cagym_rollout", "cagym_get_state", "cagym_laserscan",
            "cagym_generate_scenarios", "cagym_get_scenarios", "cagym_occupancy_grid", "cagym_kernel_name",
-           "cagym_generate_reference_scenarios", "cagym_get_obstacles"]
+           "cagym_generate_reference_scenarios", "cagym_get_obstacles", "cagym_episode_records_init",
+           "cagym_episode_records_update", "cagym_episode_records_restart", "cagym_episode_records_get"]
 
 _lib = None
 
@@ -98,6 +110,10 @@ def load():
     L.cagym_generate_reference_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymGen2Params), C.POINTER(C.c_int32), C.c_void_p]
     L.cagym_get_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cagym_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    L.cagym_episode_records_init.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.cagym_episode_records_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.cagym_episode_records_restart.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.cagym_episode_records_get.argtypes = [C.c_void_p, C.POINTER(CagymEpisodeRecordPtrs)]
     _lib = L
     return L
 

@@ -67,6 +67,9 @@ class BatchedCollisionAvoidanceEnv(object):
         self._pool_policies = set()
         self._n_ig = None         # IG robots per scenario (-1: the scenarios differ; None: a generated pool)
         self.team_reward = None   # [N] f64: the team's MI reward of the last step with ig_mcts attached (policy.team_reward)
+        self._rec = None          # keep mode of attach_episode_records, None while detached
+        self._rec_views = None
+        self._rec_priv = {}       # rollout buffers of a caller whose `out` lacks reward / flags / game_over
 
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
@@ -374,6 +377,7 @@ class BatchedCollisionAvoidanceEnv(object):
             raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
                                "communicated plans) is not implemented for this attach; attach_%s(episodic=True), or step "
                                "without auto-reset and reset() yourself" % (k, k))
+        self._records_contract(auto_reset, "step")
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
@@ -382,7 +386,89 @@ class BatchedCollisionAvoidanceEnv(object):
         rc = fn(self.h, None if a is None else a.data_ptr(), C.byref(self._out), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_step")
         self._ig_boundary(self.team_reward, self.game_over if auto_reset else None)
+        if self._rec is not None:
+            self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
+
+    # ---- per-scenario episode records (include/cagym.h: cagym_episode_records_*) ---------------------------------------------
+    def attach_episode_records(self, keep="first"):
+        """From now on every auto-resetting step is followed, on the same stream, by ONE cagym_episode_records_update launch
+        that rebuilds from the step's outputs what the reference reads from prev_episode_agents at the end of an episode
+        (experiments/src/env_utils.py:41-62): per scenario of the pool the agents' t and extra time to goal, terminal flags,
+        agent 0's return, the step count and the outcome bits.  step / step_finish / step_overlapped with auto_reset=True and
+        rollout(auto_reset=True) (single launch, GA3C chain and episodic IG chain) feed it; CagymVecEnv inherits it through
+        step().  keep="first": a row is written by the first episode that ends on its scenario (a suite's table is complete
+        once episode_records()["count"].min() >= 1); keep="last": the newest finished episode overwrites it (training
+        monitors).  The recorder takes every step exactly once and in order, so step(auto_reset=False) and
+        rollout(auto_reset=False) are refused while attached.  Attaching again clears the table.  Needs a scenario pool."""
+        if keep not in _lib.EPREC_KEEP:
+            raise ValueError("attach_episode_records: keep must be 'first' or 'last', got %r" % (keep,))
+        rc = self.L.cagym_episode_records_init(self.h, _lib.EPREC_KEEP[keep], self._stream())
+        _lib.check(self.L, self.h, rc, "cagym_episode_records_init")
+        self._rec = keep
+        return self
+
+    def detach_episode_records(self):
+        """Stop feeding the recorder (its table stays readable through the C ABI; attach again to clear and resume)."""
+        self._rec = None
+
+    def _records_contract(self, auto_reset, what):
+        if self._rec is not None and not auto_reset:
+            raise RuntimeError("%s(auto_reset=False) with episode records attached: cagym_episode_records_update takes the outputs "
+                               "of auto-reset stepping only, every step exactly once and in order (include/cagym.h); "
+                               "detach_episode_records() first" % what)
+
+    def _records_update(self, flags, reward, game_over, T):
+        rc = self.L.cagym_episode_records_update(self.h, flags.data_ptr(), reward.data_ptr(), game_over.data_ptr(), int(T),
+                                                 self._stream())
+        _lib.check(self.L, self.h, rc, "cagym_episode_records_update")
+
+    def _records_out(self, out, n_steps):
+        """reward / flags / game_over slices for the recorder: the caller's, or private ones where `out` has none."""
+        if self._rec is None:
+            return out
+        T = int(n_steps)
+        shapes = {"reward": ((T, self.N, self.M), torch.float32), "flags": ((T, self.N, self.M), torch.uint8),
+                  "game_over": ((T, self.N), torch.uint8)}
+        full = dict(out)
+        for k, (shape, dt) in shapes.items():
+            if full.get(k) is None:
+                buf = self._rec_priv.get(k)
+                if buf is None or tuple(buf.shape) != shape:
+                    buf = self._rec_priv[k] = torch.empty(shape, dtype=dt, device=self.device)
+                full[k] = buf
+        return full
+
+    def restart_episode_records(self, world_mask=None, clear_table=False):
+        """The masked worlds (None = all) forget the episode in progress; clear_table also empties the table and desync."""
+        m = None
+        if world_mask is not None:
+            m = torch.as_tensor(world_mask, device=self.device).to(torch.uint8).contiguous()
+        rc = self.L.cagym_episode_records_restart(self.h, None if m is None else m.data_ptr(), int(bool(clear_table)), self._stream())
+        _lib.check(self.L, self.h, rc, "cagym_episode_records_restart")
+
+    def episode_records(self, check=True):
+        """Zero-copy device views of the recorder: the table t / extra_t [S, M] f64, flags [S, M] u8, ret [S] f64, steps /
+        outcome / count [S] i32, the running t_run [N, M], ret_run, steps_run, atgoal_run, cursor [N], and desync [1].  Raises
+        RuntimeError when the recorder saw a skipped, doubled or non-auto-reset step (desync != 0; this synchronises).  The pool's
+        n_agents [S] rides along for stats.suite_statistics."""
+        if self._rec_views is None:
+            rp = _lib.CagymEpisodeRecordPtrs()
+            _lib.check(self.L, self.h, self.L.cagym_episode_records_get(self.h, C.byref(rp)), "cagym_episode_records_get")
+            dims = {"S": (self.S,), "SM": (self.S, self.M), "N": (self.N,), "NM": (self.N, self.M), "1": (1,)}
+            v = {}
+            for name, ts, shape in _lib.EPREC_FIELDS:
+                t = torch.as_tensor(_DevArray(getattr(rp, name), dims[shape], ts), device=self.device)
+                v[name] = t.view(torch.int32) if ts == "u4" else t
+            v["n_agents"] = self.scenarios()["n_agents"]
+            self._rec_views = v
+        if check:
+            d = int(self._rec_views["desync"].item())
+            if d:
+                raise RuntimeError("episode records are out of step with the env in %d world-launches (desync): the recorder was "
+                                   "fed a step twice, skipped one, or saw a step without auto-reset; attach_episode_records() "
+                                   "again to clear" % d)
+        return dict(self._rec_views)
 
     def _ig_boundary(self, team_reward, game_over):
         """The episodic IG team's end of a step: the running return, and the restart of the worlds the step just finished."""
@@ -410,11 +496,14 @@ class BatchedCollisionAvoidanceEnv(object):
         """Second half of step(): everything else, with every agent's action in hand.  Same results as step(), bit for bit.
         Takes every action from the caller: refused while attach_ga3c / attach_ig_mcts drive agents inside step()."""
         self._refuse_split()
+        self._records_contract(auto_reset, "step_finish")
         a = None
         if actions is not None:
             a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
         rc = self.L.cagym_step_finish(self.h, None if a is None else a.data_ptr(), C.byref(self._out), int(bool(auto_reset)), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_step_finish")
+        if self._rec is not None:
+            self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
 
     def step_overlapped(self, policy, actions, auto_reset=False):
@@ -453,6 +542,7 @@ class BatchedCollisionAvoidanceEnv(object):
         synchronisation, so the chain can be captured in a graph.  With an episodic attach_ig_mcts: T x (robot inputs, belief
         update, team reward into out["team_reward"][t], plan, robot actions, step, episode boundary), no host synchronisation
         either; not under stream capture (the planner's call_base is a kernel argument the host advances per call)."""
+        self._records_contract(auto_reset, "rollout")
         if self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
             raise RuntimeError("rollout() with %s attached is not implemented for this attach (the planner needs per-world "
@@ -468,6 +558,7 @@ class BatchedCollisionAvoidanceEnv(object):
                 out = self.alloc_rollout(n_steps)
             if out.get("team_reward") is None:
                 out["team_reward"] = torch.empty((int(n_steps), self.N), dtype=torch.float64, device=self.device)
+            caller_out, out = out, self._records_out(out, n_steps)
             fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
             keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
             # the robots' detector reads the OtherAgentsStates table of the step before: slice t - 1, or the env's own table, which
@@ -484,9 +575,12 @@ class BatchedCollisionAvoidanceEnv(object):
                 self._ig_boundary(out["team_reward"][t], out["game_over"][t] if auto_reset else None)
             if sliced and int(n_steps) > 0:
                 self.obs_oas.copy_(out["other_agents_states"][int(n_steps) - 1])
-            return out
+            if self._rec is not None:  # one launch over the chain's T slices, behind its last step
+                self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
+            return caller_out
         if out is None:
             out = self.alloc_rollout(n_steps)
+        caller_out, out = out, self._records_out(out, n_steps)
         if self._drives_ga3c():
             fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
             keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
@@ -495,13 +589,17 @@ class BatchedCollisionAvoidanceEnv(object):
                 o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in keys])
                 rc = fn(self.h, self._act.data_ptr(), C.byref(o), self._stream())
                 _lib.check(self.L, self.h, rc, "cagym_step")
-            return out
+            if self._rec is not None:  # one launch over the chain's T slices, behind its last step
+                self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
+            return caller_out
         o = self._outputs(out.get("other_agents_states"), out.get("ego"), out.get("laserscan"), out.get("reward"),
                           out.get("flags"), out.get("game_over"))
         # (no torch.cuda.device context here and in step(): the library switches to the handle's device itself - DEVGUARD)
         rc = self.L.cagym_rollout(self.h, int(n_steps), int(bool(auto_reset)), C.byref(o), self._stream())
         _lib.check(self.L, self.h, rc, "cagym_rollout")
-        return out
+        if self._rec is not None:
+            self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
+        return caller_out
 
     def kernel_name(self, rollout=True, auto_reset=True):
         """The kernel instantiation the library launches for this handle (as rocprofv3 --kernel-trace names it)."""

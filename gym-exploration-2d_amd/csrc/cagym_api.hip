@@ -26,6 +26,7 @@
 #include "cagym_dmcts.h"
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
+#include "cagym_episode_records.h"
 
 namespace {
 
@@ -56,6 +57,8 @@ struct Env {
     size_t pre_lds_min = 0;  // CAGYM_PRE_LDS (bytes, read at creation): the PRE half asks for at least this much LDS per workgroup - a cap on how
                              // many of its workgroups share a CU with the caller's policy kernel (tools/cfg4_overlap.py)
     bool begun = false;  // cagym_step_begin was enqueued and no cagym_step_finish has consumed its velocities yet
+    EpRec rec{};         // per-scenario episode records (cagym_episode_records_init allocates them)
+    bool rec_ready = false;
     int n_ig = 0;        // IG robots (active CAGYM_POL_IGMCTS slots) of every scenario of the pool; N_IG_UNEQUAL when the scenarios
                          // differ, N_IG_RANDOM when cagym_generate_scenarios may have drawn some (cagym_ig_robot_inputs / _actions)
 };
@@ -250,6 +253,17 @@ inline int fill_empty_scan(Env* e, const CagymOut& o, hipStream_t st, int n_step
     if (e->generation != 3 || has_map(e) || !o.laserscan) return CAGYM_OK;
     if (n_steps) HIPCHK(e, hipMemsetAsync(o.laserscan, 0, (size_t)n_steps * scan_bytes(e), st));
     else HIPCHK(e, hipMemsetAsync(o.laserscan, 0, scan_bytes(e), st));
+    return CAGYM_OK;
+}
+
+
+// the episode recorder's restart / clear launch (csrc/cagym_episode_records.h); a no-op for handles that never initialised it
+inline int eprec_restart(Env* e, const uint8_t* world_mask, bool clear_table, hipStream_t st) {
+    if (!e->rec_ready) return CAGYM_OK;
+    const size_t rows = (size_t)std::max(e->cfg.n_worlds, clear_table ? e->cfg.n_scenarios : 0) * e->cfg.max_agents;
+    const unsigned grid = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_episode_records_restart, dim3(grid), dim3(256), 0, st, e->D, e->rec, world_mask, clear_table ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
 
@@ -556,7 +570,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->D.ko = new_ko;
     e->scenarios_set = true;
     e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
-    return CAGYM_OK;
+    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
 }
 
 // the handle's scenario pool as the generator kernels write it
@@ -614,7 +628,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     e->scenarios_set = true;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return CAGYM_OK;
+    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
 }
 
 int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
@@ -696,7 +710,7 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
     e->D.ko = obst_rvo ? 2 * K : 0;
     e->scenarios_set = true;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return CAGYM_OK;
+    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
 }
 
 int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst) {
@@ -726,6 +740,7 @@ int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const
     hipLaunchKernelGGL(k_reset, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, world_mask,
                        advance_episode, o);
     HIPCHK(e, hipGetLastError());
+    if (int rc = eprec_restart(e, world_mask, false, st)) return rc;  // an abandoned episode leaves no record
     if (e->cfg.laserscan && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);
     return CAGYM_OK;
 }
@@ -1316,6 +1331,64 @@ int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const 
                        reinterpret_cast<hipStream_t>(stream), e->G, P, poses, actions, choice, mi,
                        reinterpret_cast<unsigned long long*>(claimed));
     HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- per-scenario episode records (csrc/cagym_episode_records.h) --------------------------------------------------------------------
+int cagym_episode_records_init(void* env, int keep, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_records_init");
+    if (keep != CAGYM_EPREC_KEEP_FIRST && keep != CAGYM_EPREC_KEEP_LAST) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_init: unknown keep mode");
+    ON_DEVICE(e);
+    if (!e->rec.t) {
+        const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, S = e->cfg.n_scenarios;
+        EpRec R{};
+#define A(call) if (int rc = (call)) return rc;
+        A(dalloc(e, &R.extra_t, S * M)); A(dalloc(e, &R.flags, S * M)); A(dalloc(e, &R.ret, S)); A(dalloc(e, &R.steps, S));
+        A(dalloc(e, &R.outcome, S)); A(dalloc(e, &R.count, S)); A(dalloc(e, &R.claim, S));
+        A(dalloc(e, &R.t_run, N * M)); A(dalloc(e, &R.ret_run, N)); A(dalloc(e, &R.steps_run, N)); A(dalloc(e, &R.atgoal_run, N));
+        A(dalloc(e, &R.cursor, N)); A(dalloc(e, &R.desync, 1)); A(dalloc(e, &R.seq, 1));
+        A(dalloc(e, &R.t, S * M));  // last: the handle holds the records only when every allocation succeeded
+#undef A
+        e->rec = R;
+    }
+    e->rec.keep = keep;
+    e->rec_ready = true;
+    return eprec_restart(e, nullptr, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_episode_records_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_records_update");
+    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_update before cagym_episode_records_init");
+    if (!flags || !reward || !game_over) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_update: flags, reward and game_over are required");
+    if (T < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_update: T must be >= 1");
+    ON_DEVICE(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (e->cfg.n_scenarios % e->cfg.n_worlds == 0) {  // s % N == w: one writer per row
+        const int waves_per_wg = EPREC_NT / CAGYM_WAVE;
+        hipLaunchKernelGGL(k_episode_records_update, dim3((unsigned)((n_waves(e) + waves_per_wg - 1) / waves_per_wg)), dim3(EPREC_NT), 0, st,
+                           e->D, e->rec, flags, reward, game_over, T);
+    } else {
+        hipLaunchKernelGGL(k_episode_records_update_shared, dim3(1), dim3(EPREC_NT_SHARED), 0, st, e->D, e->rec, flags, reward, game_over, T);
+    }
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_episode_records_restart(void* env, const uint8_t* world_mask, int clear_table, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_records_restart");
+    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_restart before cagym_episode_records_init");
+    ON_DEVICE(e);
+    return eprec_restart(e, world_mask, clear_table != 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out) {
+    ENTRY_POOL(e, env, "cagym_episode_records_get");
+    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_get before cagym_episode_records_init");
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    const EpRec& R = e->rec;
+    out->t = R.t; out->extra_t = R.extra_t; out->flags = R.flags; out->ret = R.ret; out->steps = R.steps; out->outcome = R.outcome;
+    out->count = R.count; out->t_run = R.t_run; out->ret_run = R.ret_run; out->steps_run = R.steps_run; out->atgoal_run = R.atgoal_run;
+    out->cursor = R.cursor; out->desync = R.desync;
     return CAGYM_OK;
 }
 

@@ -73,3 +73,49 @@ def summarize(gathered):
     return {"episodes": float(eps_n), "mean_return": float(u["return_sum"].sum()) / eps,
             "mean_steps": float(int(u["steps"].sum())) / eps, "frac_goal": goal / agents,
             "frac_collision": coll / agents, "frac_timeout": tout / agents}
+
+
+# ---- the reference's test-suite table from per-scenario episode records (env.episode_records()) ------------------------------------
+OUTCOME_COLLISION, OUTCOME_ALL_AT_GOAL, OUTCOME_STUCK = 1, 2, 4  # bits of the records' outcome column (env_utils.py:55-60)
+
+
+def suite_statistics(records, first=0, count=None, include=None):
+    """What experiments/src/process_full_test_suite_pickles.py:90-116 prints for one policy, from the table of
+    BatchedCollisionAvoidanceEnv.episode_records() (torch tensors, on the device they live on), over the scenarios
+    first .. first + count - 1 (default: to the end of the pool):
+      n_cases, n_run (rows with count > 0);
+      pct_collision (any agent in collision), pct_stuck (no collision and not all at goal, env_utils.py:72-74), in percent of
+        n_cases as the reference counts them;
+      clean [n_cases] bool: run, no collision, all at goal - the rows the reference intersects across policies;
+      extra_time_pctls: the 50 / 75 / 90th percentiles (np.percentile's default, linear interpolation) of the per-case mean of
+        extra_t over the case's active agents (slots < n_agents; every slot when the records carry no n_agents), taken over the
+        rows of `include` (a [n_cases] bool mask, e.g. the intersection of several policies' clean rows; default: this
+        table's clean rows).  NaN when no row is included."""
+    cnt = records["count"]
+    S = int(cnt.shape[0])
+    first = int(first)
+    last = S if count is None else first + int(count)
+    if not (0 <= first < last <= S):
+        raise ValueError("suite_statistics: cases %d..%d outside the pool of %d scenarios" % (first, last, S))
+    sl = slice(first, last)
+    cnt, outcome, extra = cnt[sl], records["outcome"][sl], records["extra_t"][sl]
+    n_cases = last - first
+    run = cnt > 0
+    coll = run & ((outcome & OUTCOME_COLLISION) != 0)
+    goal = (outcome & OUTCOME_ALL_AT_GOAL) != 0
+    stuck = run & ~coll & ~goal
+    clean = run & ~coll & goal
+    M = int(extra.shape[1])
+    if records.get("n_agents") is not None:
+        n = records["n_agents"][sl].to(torch.int64)
+    else:
+        n = torch.full((n_cases,), M, dtype=torch.int64, device=extra.device)
+    live = torch.arange(M, device=extra.device)[None, :] < n[:, None]
+    mean_extra = (extra * live).sum(dim=1) / n.clamp(min=1).to(extra.dtype)
+    inc = clean if include is None else torch.as_tensor(include, device=extra.device).to(torch.bool).reshape(n_cases)
+    vals = mean_extra[inc]
+    q = torch.tensor([0.5, 0.75, 0.9], dtype=extra.dtype, device=extra.device)
+    pct = torch.quantile(vals, q, interpolation="linear") if vals.numel() else torch.full((3,), float("nan"), dtype=extra.dtype,
+                                                                                         device=extra.device)
+    return {"n_cases": n_cases, "n_run": int(run.sum()), "pct_collision": 100.0 * float(coll.sum()) / n_cases,
+            "pct_stuck": 100.0 * float(stuck.sum()) / n_cases, "clean": clean, "extra_time_pctls": pct}

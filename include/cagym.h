@@ -469,6 +469,56 @@ typedef struct cagym_ig_greedy_params {
 int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const double* poses, double* actions, uint8_t* choice,
                          double* mi, uint64_t* claimed, void* stream);
 
+/* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
+ * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
+ * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
+ * reads at the end of an episode from the step's OUTPUTS (flags, reward, game_over) and the scenario pool, in a launch of its own
+ * beside the step kernels (csrc/cagym_episode_records.h).  Agent.t follows from the flags alone: 0 at the start of an episode, += dt
+ * every step unless the agent's AT_GOAL bit was set in the flags of the previous step of the same episode (agent.py:147-159, 184-186).
+ * Table, one row per scenario s of the pool, written when an episode on s ends:
+ *   t [S,M] f64, extra_t [S,M] f64 = t - (|start - goal| - 0.75) / pref_speed (agent.py:59), flags [S,M] u8 the terminal CAGYM_FLAG_*
+ *   byte, ret [S] f64 = sum of agent 0's reward in step order (score += rew[0]), steps [S] i32, outcome [S] i32 (bit 0: any agent
+ *   IN_COLLISION, bit 1: all agents AT_GOAL, bit 2: any agent neither; env_utils.py:55-60), count [S] i32 finished episodes seen.
+ *   Slots >= the pool's n_agents[s] hold zeros and take no part in outcome.
+ * Running, per world: t_run [N,M] f64, ret_run [N] f64, steps_run [N] i32, atgoal_run [N] u32 (bit per slot), cursor [N] i32 = the
+ * episode index the recorder believes the world is on (row s = (w + cursor * N) % S).  desync: one i32 word.
+ * keep: CAGYM_EPREC_KEEP_FIRST: a row is written by the first episode that ends on it and later episodes only count (a suite's
+ *   table is complete and stable once every count >= 1); CAGYM_EPREC_KEEP_LAST: the newest finished episode overwrites the row.
+ *   When two worlds end episodes on one scenario, the order is (step, world): one of them owns the whole row, count adds both.
+ * cagym_episode_records_init: allocate (once) and clear; a second call clears again and may change keep.
+ * cagym_episode_records_update: ONE launch over T consecutive steps: flags [T,N,M] u8, reward [T,N,M] f32, game_over [T,N] u8 (DEVICE).
+ *   CONTRACT: the outputs of auto-reset stepping only (cagym_step_autoreset, cagym_step_finish with auto_reset, cagym_rollout with
+ *   auto_reset), every step exactly once and in order, enqueued behind the step(s) that wrote them and before the next stepping call
+ *   on the handle.  No argument advances on the host, so the call can be captured in a graph with the steps.  After the last slice
+ *   the kernel compares cursor and steps_run of every world with the episode index and episode length the step kernels keep; on a
+ *   mismatch (a skipped, doubled or non-auto-reset step) it adds 1 to desync, takes the handle's values and drops the world's
+ *   running values.  A pool whose n_scenarios is a multiple of n_worlds has one writer per row and runs on the whole device; any
+ *   other pool is walked by one workgroup in step order (rows may be shared).
+ * cagym_episode_records_restart: the masked worlds (DEVICE [N] u8, NULL = all) forget the episode in progress and take the handle's
+ *   episode index; clear_table != 0 also clears the table and desync.
+ * cagym_episode_records_get: zero-copy DEVICE views, owned by the handle.
+ * Once initialised: a successful cagym_reset enqueues the restart for its mask on its stream (an abandoned episode leaves no record);
+ * a successful cagym_set_scenarios / cagym_generate_scenarios / cagym_generate_reference_scenarios clears the table and every running
+ * value (the table describes the pool).  Handles that never called init behave as before.
+ * Errors: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before cagym_set_scenarios, and for update / restart / get before init;
+ * CAGYM_E_INVALID for a NULL flags / reward / game_over / out, T < 1 or an unknown keep; CAGYM_E_DEVICE as every launching entry. */
+enum { CAGYM_EPREC_KEEP_FIRST = 0, CAGYM_EPREC_KEEP_LAST = 1 };
+typedef struct cagym_episode_record_ptrs {
+    const double *t, *extra_t;
+    const uint8_t* flags;
+    const double* ret;
+    const int32_t *steps, *outcome, *count;
+    const double *t_run, *ret_run;
+    const int32_t* steps_run;
+    const uint32_t* atgoal_run;
+    const int32_t* cursor;
+    const int32_t* desync;
+} cagym_episode_record_ptrs;
+int cagym_episode_records_init(void* env, int keep, void* stream);
+int cagym_episode_records_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream);
+int cagym_episode_records_restart(void* env, const uint8_t* world_mask, int clear_table, void* stream);
+int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out);
+
 #ifdef __cplusplus
 }
 #endif
