@@ -68,18 +68,81 @@ class CagymEpisodeRecordPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in EPREC_FIELDS]
 
 
-EXPORTS = ["cagym_version", "cagym_create", "cagym_destroy", "cagym_last_error", "cagym_set_scenarios",
-           "cagym_reset", "cagym_step", "cagym_step_autoreset", "cagym_step_begin", "cagym_step_finish", "cagym_rollout", "cagym_get_state", "cagym_laserscan",
-           "cagym_generate_scenarios", "cagym_get_scenarios", "cagym_occupancy_grid", "cagym_kernel_name",
-           "cagym_generate_reference_scenarios", "cagym_get_obstacles", "cagym_episode_records_init",
-           "cagym_episode_records_update", "cagym_episode_records_restart", "cagym_episode_records_get"]
+class DmctsParams(C.Structure):
+    """cagym_dmcts_params (include/cagym.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_robots", "Ntree", "Nsims", "horizon", "Ncycles", "comm_n", "xdt", "reset_comms")] + \
+               [("call_base", C.c_uint32), ("parallel_agents", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("c_p", "gamma", "radius", "dt", "fov_rad", "range")] + [("seed", C.c_uint64)]
+
+
+class GreedyParams(C.Structure):
+    """cagym_ig_greedy_params (include/cagym.h)."""
+    _fields_ = [("n_robots", C.c_int32), ("coordinate", C.c_int32)] + \
+               [(n, C.c_double) for n in ("dt", "radius", "fov_rad", "range")] + [("v", C.c_double * 3), ("w", C.c_double * 3)]
+
+
+# ---- the prototypes of include/cagym.h: name -> argtypes; every function returns int except those of _RESTYPES ----------------
+_vp, _int, _dbl, _P = C.c_void_p, C.c_int, C.c_double, C.POINTER
+_OUT = _P(CagymOutputs)
+_RESTYPES = {"cagym_last_error": C.c_char_p, "cagym_ga3c_act_workspace_bytes": C.c_size_t,
+             "cagym_dmcts_workspace_bytes": C.c_size_t}
+_ARGTYPES = {
+    "cagym_version": [],
+    "cagym_create": [_P(CagymConfig), _P(_vp)],
+    "cagym_destroy": [_vp],
+    "cagym_last_error": [_vp],
+    "cagym_set_scenarios": [_vp] * 10,
+    "cagym_reset": [_vp, _vp, _int, _OUT, _vp],
+    "cagym_step": [_vp, _vp, _OUT, _vp],
+    "cagym_step_autoreset": [_vp, _vp, _OUT, _vp],
+    "cagym_step_begin": [_vp, _vp],
+    "cagym_step_finish": [_vp, _vp, _OUT, _int, _vp],
+    "cagym_rollout": [_vp, _int, _int, _OUT, _vp],
+    "cagym_get_state": [_vp, _P(CagymStatePtrs)],
+    "cagym_pack_episode_stats": [_vp, _vp, _vp],
+    "cagym_kernel_name": [_vp, _int, _int, C.c_char_p, _int],
+    "cagym_laserscan": [_vp, _vp, _vp],
+    "cagym_occupancy_grid": [_vp, _vp, _vp],
+    "cagym_generate_scenarios": [_vp, _P(CagymGenParams), _P(C.c_int32), _vp],
+    "cagym_get_scenarios": [_vp, _P(CagymScenarioPtrs)],
+    "cagym_generate_reference_scenarios": [_vp, _P(CagymGen2Params), _P(C.c_int32), _vp],
+    "cagym_get_obstacles": [_vp, _P(_vp), _P(_vp)],
+    "cagym_ga3c_state": [_vp, _int, _vp, _vp],
+    "cagym_ga3c_load_weights": [_vp, _vp, _vp],
+    "cagym_ga3c_forward": [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp],
+    "cagym_ga3c_act_workspace_bytes": [_vp],
+    "cagym_ga3c_act": [_vp, _vp, _int, _vp, _vp, _vp],
+    "cagym_ga3c_act_merge": [_vp, _vp, _int, _vp, _vp, _vp, _vp],
+    "cagym_ig_init": [_vp, _vp],
+    "cagym_ig_reset_belief": [_vp, _vp, _vp],
+    "cagym_ig_get": [_vp, _P(_vp), _P(_vp)],
+    "cagym_ig_get_episode_stats": [_vp] + [_P(_vp)] * 4,
+    "cagym_ig_visible_cells": [_vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp],
+    "cagym_ig_update_belief": [_vp, _vp, _vp, _vp, _vp, _int, _int, _dbl, _dbl, _vp, _vp],
+    "cagym_ig_mi_reward": [_vp, _vp, _vp, _int, _vp, _vp],
+    "cagym_ig_next_pose": [_vp, _vp, _vp, _vp, _vp, _int, _int, _dbl, _vp, _vp, _vp],
+    "cagym_ig_rollouts": [_vp] * 7 + [_int] * 4 + [_dbl] * 3 + [C.c_uint64, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_robot_inputs": [_vp, _int, _dbl, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_robot_actions": [_vp, _int, _vp, _vp, _vp],
+    "cagym_ig_episode_boundary": [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_size_t, _vp],
+    "cagym_ig_greedy_plan": [_vp, _P(GreedyParams), _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],
+    "cagym_dmcts_plan": [_vp, _P(DmctsParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
+    "cagym_episode_records_init": [_vp, _int, _vp],
+    "cagym_episode_records_update": [_vp, _vp, _vp, _vp, _int, _vp],
+    "cagym_episode_records_restart": [_vp, _vp, _int, _vp],
+    "cagym_episode_records_get": [_vp, _P(CagymEpisodeRecordPtrs)],
+}
+# exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
+_DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],
+                   "cagym_debug_wgtrace": [_vp, _int]}
 
 _lib = None
 
 
 def load():
-    """Load the HIP library.  torch is imported first so that the library binds to the HIP runtime
-    torch already mapped (same SONAME); there is deliberately no CPU / pure-Python fallback."""
+    """Load the HIP library and declare every prototype of include/cagym.h.  torch is imported first so that the library binds to
+    the HIP runtime torch already mapped (same SONAME); there is deliberately no CPU / pure-Python fallback."""
     global _lib
     if _lib is not None:
         return _lib
@@ -89,31 +152,11 @@ def load():
             "libcagym_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `python gym-exploration-2d_amd/build.py`; there is no CPU fallback." % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    L.cagym_version.restype = C.c_int
-    L.cagym_last_error.restype = C.c_char_p
-    L.cagym_last_error.argtypes = [C.c_void_p]
-    L.cagym_create.argtypes = [C.POINTER(CagymConfig), C.POINTER(C.c_void_p)]
-    L.cagym_destroy.argtypes = [C.c_void_p]
-    L.cagym_set_scenarios.argtypes = [C.c_void_p] * 10
-    L.cagym_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CagymOutputs), C.c_void_p]
-    L.cagym_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CagymOutputs), C.c_void_p]
-    L.cagym_step_autoreset.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CagymOutputs), C.c_void_p]
-    L.cagym_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CagymOutputs), C.c_void_p]
-    L.cagym_step_begin.argtypes = [C.c_void_p, C.c_void_p]
-    L.cagym_step_finish.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CagymOutputs), C.c_int, C.c_void_p]
-    L.cagym_get_state.argtypes = [C.c_void_p, C.POINTER(CagymStatePtrs)]
-    L.cagym_laserscan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cagym_pack_episode_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cagym_occupancy_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cagym_generate_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymGenParams), C.POINTER(C.c_int32), C.c_void_p]
-    L.cagym_get_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymScenarioPtrs)]
-    L.cagym_generate_reference_scenarios.argtypes = [C.c_void_p, C.POINTER(CagymGen2Params), C.POINTER(C.c_int32), C.c_void_p]
-    L.cagym_get_obstacles.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-    L.cagym_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
-    L.cagym_episode_records_init.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.cagym_episode_records_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.cagym_episode_records_restart.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.cagym_episode_records_get.argtypes = [C.c_void_p, C.POINTER(CagymEpisodeRecordPtrs)]
+    protos = dict(_ARGTYPES)
+    protos.update((n, a) for n, a in _DEBUG_ARGTYPES.items() if hasattr(L, n))
+    for name, argtypes in protos.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, _RESTYPES.get(name, C.c_int)
     _lib = L
     return L
 
@@ -122,3 +165,13 @@ def check(L, env, rc, what):
     if rc != 0:
         msg = L.cagym_last_error(env)
         raise RuntimeError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def call(L, env, name, *args):
+    """L.<name>(env, *args); a non-zero return raises check()'s RuntimeError under that name."""
+    check(L, env, getattr(L, name)(env, *args), name)
+
+
+def ptr(t):
+    """A tensor's device address, or None (NULL) for None."""
+    return None if t is None else t.data_ptr()

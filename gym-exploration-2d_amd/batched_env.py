@@ -12,6 +12,9 @@ import torch
 
 from . import _lib
 from . import scenarios as sc
+from .dmcts import DeviceDecMCTSPlanner
+from .ga3c import GA3CCADRLPolicy
+from .ig import EPISODE_FOLD, GreedyPlanner, InfoGain
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> hipStream_t as an int
 
@@ -26,6 +29,12 @@ class _DevArray(object):
                                          "version": 2, "strides": None}
 
 
+class _IgState(object):
+    """What step() needs of an attached IG policy, whichever it is: the primitives, the planner and the robots' input buffers."""
+    __slots__ = ("kind", "ig", "R", "range", "episodic", "poses", "det", "n_det", "world", "planner")
+
+
+_OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
 GAME_OVER_MODES = {"agent0": _lib.GO_AGENT0, "all": _lib.GO_ALL, "learning": _lib.GO_LEARNING}
 
 
@@ -49,6 +58,9 @@ class BatchedCollisionAvoidanceEnv(object):
                                     int(rvo_max_neighbors), 0)  # rvo_max_neighbors 0 = max_agents (RVOPolicy.py:15)
         self.h = C.c_void_p()
         _lib.check(self.L, None, self.L.cagym_create(C.byref(self.cfg), C.byref(self.h)), "cagym_create")
+        # the calls inside per-step loops, resolved once
+        self._step_fn = (self.L.cagym_step, self.L.cagym_step_autoreset)
+        self._rollout_fn, self._records_fn = self.L.cagym_rollout, self.L.cagym_episode_records_update
         N, M, K = self.N, self.M, self.K
         dev = self.device
         self.obs_oas = torch.zeros((N, M, K, 10), dtype=torch.float32, device=dev)
@@ -74,8 +86,20 @@ class BatchedCollisionAvoidanceEnv(object):
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
     def _outputs(oas, ego, laser, reward, flags, go):
-        p = lambda t: None if t is None else t.data_ptr()
+        p = _lib.ptr
         return _lib.CagymOutputs(p(oas), p(ego), p(laser), p(reward), p(flags), p(go))
+
+    def _actions(self, actions):
+        """The caller's actions as a contiguous f32 [N, M, 2] device tensor, or None."""
+        if actions is None:
+            return None
+        return torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
+
+    def _mask(self, world_mask):
+        """A world mask as a contiguous u8 device tensor, or None (= every world)."""
+        if world_mask is None:
+            return None
+        return torch.as_tensor(world_mask, device=self.device).to(torch.uint8).contiguous()
 
     def _stream(self):
         # torch's current stream of the handle's device (the raw-handle accessor costs 0.3 us, the Stream object 2 us per launch)
@@ -113,10 +137,7 @@ class BatchedCollisionAvoidanceEnv(object):
             ob[:, :o.shape[1]] = o
             no = np.ascontiguousarray(np.asarray(n_obst, dtype=np.int32).reshape(S))
         p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_set_scenarios(self.h, p(a6), p(h0), p(pol), p(dyn), p(na), p(co), p(ob), p(no),
-                                            self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_set_scenarios")
+        _lib.call(self.L, self.h, "cagym_set_scenarios", p(a6), p(h0), p(pol), p(dyn), p(na), p(co), p(ob), p(no), self._stream())
         live = np.arange(M)[None, :] < (na if na is not None else np.full(S, M))[:, None]
         self._pool_policies = set(np.unique(pol[live]).tolist())
         counts = ((pol == sc.POLICY_IGMCTS) & live).sum(axis=1)
@@ -124,16 +145,14 @@ class BatchedCollisionAvoidanceEnv(object):
         if self._igm is not None and self._n_ig != self._igm.R:  # the attached planner was sized for another team
             self.detach_ig_mcts()
         if self._igm is not None:  # new rasters: their distance fields and fresh beliefs (cagym_ig_init)
-            _lib.check(self.L, self.h, self.L.cagym_ig_init(self.h, self._stream()), "cagym_ig_init")
+            _lib.call(self.L, self.h, "cagym_ig_init", self._stream())
 
     def sense_occupancy_grid(self, out=None):
         """'local_grid' observation of every agent (OccupancyGridSensor.sense): uint8 [N, M, 60, 60], 1 = occupied.
         Parity unpinned (cv2.warpAffine is restated, OpenCV is not installed): see include/cagym.h."""
         if out is None:
             out = torch.empty((self.N, self.M, 60, 60), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_occupancy_grid(self.h, out.data_ptr(), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_occupancy_grid")
+        _lib.call(self.L, self.h, "cagym_occupancy_grid", out.data_ptr(), self._stream())
         return out
 
     def generate_scenarios(self, seed, n_agents=None, ego_policy=5, ego_dynamics=0, other_policies=(5, 1), p_b=0.5,
@@ -151,9 +170,7 @@ class BatchedCollisionAvoidanceEnv(object):
                                 float(p_b), float(side), float(min_travel), float(min_sep), float(radius),
                                 float(pref_speed), float(coop))
         nf = C.c_int32(0)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_generate_scenarios(self.h, C.byref(P), C.byref(nf) if check else None, self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_generate_scenarios")
+        _lib.call(self.L, self.h, "cagym_generate_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
         self._pool_policies = {int(ego_policy), int(other_policies[0]), int(other_policies[1])}
         self._n_ig = None
         self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
@@ -193,9 +210,7 @@ class BatchedCollisionAvoidanceEnv(object):
         P = _lib.CagymGen2Params(int(seed), mask, int(number_of_agents), int(bool(fixed_count)), int(ego_policy),
                                  int(ego_dynamics), int(own), pa, pb, int(other_dynamics), int(lo), int(hi), int(max_tries), pp)
         nf = C.c_int32(0)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_generate_reference_scenarios(self.h, C.byref(P), C.byref(nf) if check else None, self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_generate_reference_scenarios")
+        _lib.call(self.L, self.h, "cagym_generate_reference_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
         # the policies the pool may hold
         pols = {int(ego_policy)}
         for k in {sc.sampler_kind(k) for k in ks}:
@@ -212,7 +227,7 @@ class BatchedCollisionAvoidanceEnv(object):
     def obstacles(self):
         """Zero-copy device views of the pool's rectangles: obstacles [S, max_obstacles, 4] (xl, yl, xu, yu), n_obst [S]."""
         o, n = C.c_void_p(), C.c_void_p()
-        _lib.check(self.L, self.h, self.L.cagym_get_obstacles(self.h, C.byref(o), C.byref(n)), "cagym_get_obstacles")
+        _lib.call(self.L, self.h, "cagym_get_obstacles", C.byref(o), C.byref(n))
         if not self.Kobs:
             return {"obstacles": torch.zeros((self.S, 0, 4), dtype=torch.float64, device=self.device),
                     "n_obst": torch.zeros((self.S,), dtype=torch.int32, device=self.device)}
@@ -222,7 +237,7 @@ class BatchedCollisionAvoidanceEnv(object):
     def scenarios(self):
         """Zero-copy device views of the scenario pool: agents6 [S,M,6], policy / dynamics [S,M], n_agents [S], coop."""
         sp = _lib.CagymScenarioPtrs()
-        _lib.check(self.L, self.h, self.L.cagym_get_scenarios(self.h, C.byref(sp)), "cagym_get_scenarios")
+        _lib.call(self.L, self.h, "cagym_get_scenarios", C.byref(sp))
         S, M = self.S, self.M
         spec = {"agents6": ((S, M, 6), "f8"), "policy": ((S, M), "i4"), "dynamics": ((S, M), "i4"),
                 "n_agents": ((S,), "i4"), "coop": ((S, M), "f8")}
@@ -236,13 +251,8 @@ class BatchedCollisionAvoidanceEnv(object):
         return obs
 
     def reset(self, world_mask=None, advance_episode=False):
-        m = None
-        if world_mask is not None:
-            m = torch.as_tensor(world_mask, device=self.device).to(torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_reset(self.h, None if m is None else m.data_ptr(), int(bool(advance_episode)),
-                                    C.byref(self._out), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_reset")
+        m = self._mask(world_mask)
+        _lib.call(self.L, self.h, "cagym_reset", _lib.ptr(m), int(bool(advance_episode)), C.byref(self._out), self._stream())
         g = self._igm
         if g is not None and g.episodic and m is not None:
             # a manual restart of the masked worlds only: prior belief, no communicated plans, running team return zeroed; it is
@@ -261,7 +271,6 @@ class BatchedCollisionAvoidanceEnv(object):
         (GA3CCADRLPolicy.find_next_action): one cagym_ga3c_act_merge launch writes the whole action table - the network's action
         for the GA3C agents, the caller's rows for every other slot - into a buffer of the env, and the step reads that.  The env
         keeps the policy (and its weight blob, which the handle caches by address) for as long as it is attached."""
-        from .ga3c import GA3CCADRLPolicy
         self._ga3c = GA3CCADRLPolicy(self, checkpoint=checkpoint, max_observed=max_observed)
         self._alloc_act()
         return self._ga3c
@@ -282,29 +291,27 @@ class BatchedCollisionAvoidanceEnv(object):
         cycle hears nothing (DummyVecEnv's reset() builds new ig_mcts objects).  rollout() chains such steps; CagymVecEnv works.
         reset(world_mask=m) restarts the masked worlds alone and zeroes their running return without counting an episode;
         reset() restarts everything and zeroes every running return."""
-        from .dmcts import DeviceDecMCTSPlanner
-        g = self._ig_state("ig_mcts", detect_fov, detect_range, xdt, episodic)
-        g.planner = DeviceDecMCTSPlanner(g.ig, g.R, radius=radius, Ntree=Ntree, Nsims=Nsims, horizon=mcts_horizon, c_p=mcts_cp,
-                                         gamma=mcts_gamma, Ncycles=Ncycles, seed=seed, parallelize_agents=parallelize_agents)
-        self._igm = g
-        self._alloc_act()
-        return g.planner
+        return self._attach_ig("ig_mcts", detect_fov, detect_range, xdt, episodic, lambda g: DeviceDecMCTSPlanner(
+            g.ig, g.R, radius=radius, Ntree=Ntree, Nsims=Nsims, horizon=mcts_horizon, c_p=mcts_cp, gamma=mcts_gamma, Ncycles=Ncycles,
+            seed=seed, parallelize_agents=parallelize_agents))
 
-    def _ig_state(self, kind, detect_fov, detect_range, xdt, episodic):
-        """What step() needs of an attached IG policy, whichever it is: the primitives and the robots' input buffers."""
-        from .ig import InfoGain
+    def _attach_ig(self, kind, detect_fov, detect_range, xdt, episodic, make_planner):
+        """Attach an IG policy, whichever it is: the primitives, the robots' input buffers, then its planner."""
         R = self._n_ig if self._n_ig is not None else 0
         self._igm = None
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
         N, K, dev = self.N, self.K, self.device
-        g = type("IgState", (), {})()
+        g = _IgState()
         g.kind, g.ig, g.R, g.range, g.episodic = kind, ig, R, float(detect_range), bool(episodic)
         g.poses = torch.zeros((N, max(R, 1), 3), dtype=torch.float64, device=dev)
         g.det = torch.zeros((N, max(R, 1), K, 2), dtype=torch.float64, device=dev)
         g.n_det = torch.zeros((N, max(R, 1)), dtype=torch.int32, device=dev)
         g.world = torch.arange(N, dtype=torch.int32, device=dev)
         ig.robot_inputs(R, g.range, self.obs_oas, g.poses, g.det, g.n_det)  # refuses a pool without R robots in every scenario
-        return g
+        g.planner = make_planner(g)
+        self._igm = g
+        self._alloc_act()
+        return g.planner
 
     def attach_ig_greedy(self, detect_fov=60.0, detect_range=5.0, radius=0.5, coordinate=False, episodic=False):
         """From now on step() chooses the (v, omega) of every IG robot by the one-step greedy rule of policies/ig_greedy.py
@@ -316,14 +323,10 @@ class BatchedCollisionAvoidanceEnv(object):
         each without the cells the earlier ones chose (the reference's robots each own a map and cannot collide on cells).
         episodic: as attach_ig_mcts (the policy keeps nothing across steps, so a restart is the belief and the running return).
         Returns the ig.GreedyPlanner, which holds the last plan's choice / mi / claimed."""
-        from .ig import GreedyPlanner
         if self._n_ig is not None and self._n_ig > 8:
             raise ValueError("attach_ig_greedy: at most 8 IG robots per world (cagym_ig_greedy_plan), the pool has %d" % self._n_ig)
-        g = self._ig_state("ig_greedy", detect_fov, detect_range, 1, episodic)
-        g.planner = GreedyPlanner(g.ig, g.R, radius=radius, coordinate=coordinate)
-        self._igm = g
-        self._alloc_act()
-        return g.planner
+        return self._attach_ig("ig_greedy", detect_fov, detect_range, 1, episodic,
+                               lambda g: GreedyPlanner(g.ig, g.R, radius=radius, coordinate=coordinate))
 
     def detach_ig_mcts(self):
         self._igm = None
@@ -367,6 +370,19 @@ class BatchedCollisionAvoidanceEnv(object):
             g.ig.robot_actions(g.R, planned, table)
         return table
 
+    def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None):
+        """One step with whatever is attached, three parts in stream order: the internal actions (_internal_actions), the step
+        launch into the CagymOutputs `o`, and the episodic IG team's end of the step - its running return and the restart of the
+        worlds of `restart` (under auto_reset the game_over tensor `o` points at, else None).  (No torch.cuda.device context
+        here or anywhere else around the C ABI: every launching entry makes the handle's device current itself.)"""
+        a = self._internal_actions(a, team_reward_out, oas)
+        rc = self._step_fn[bool(auto_reset)](self.h, _lib.ptr(a), C.byref(o), self._stream())
+        if rc:
+            _lib.check(self.L, self.h, rc, "cagym_step")
+        g = self._igm
+        if g is not None and g.episodic:
+            g.ig.episode_boundary(g.planner.P, g.planner.workspace, self.team_reward, restart, EPISODE_FOLD)
+
     def step(self, actions=None, auto_reset=False):
         """One env.step() of every world.  auto_reset=True: finished worlds restart inside the same launch
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
@@ -378,14 +394,7 @@ class BatchedCollisionAvoidanceEnv(object):
                                "communicated plans) is not implemented for this attach; attach_%s(episodic=True), or step "
                                "without auto-reset and reset() yourself" % (k, k))
         self._records_contract(auto_reset, "step")
-        a = None
-        if actions is not None:
-            a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
-        a = self._internal_actions(a)
-        fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
-        rc = fn(self.h, None if a is None else a.data_ptr(), C.byref(self._out), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_step")
-        self._ig_boundary(self.team_reward, self.game_over if auto_reset else None)
+        self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None)
         if self._rec is not None:
             self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
@@ -403,8 +412,7 @@ class BatchedCollisionAvoidanceEnv(object):
         rollout(auto_reset=False) are refused while attached.  Attaching again clears the table.  Needs a scenario pool."""
         if keep not in _lib.EPREC_KEEP:
             raise ValueError("attach_episode_records: keep must be 'first' or 'last', got %r" % (keep,))
-        rc = self.L.cagym_episode_records_init(self.h, _lib.EPREC_KEEP[keep], self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_episode_records_init")
+        _lib.call(self.L, self.h, "cagym_episode_records_init", _lib.EPREC_KEEP[keep], self._stream())
         self._rec = keep
         return self
 
@@ -419,9 +427,9 @@ class BatchedCollisionAvoidanceEnv(object):
                                "detach_episode_records() first" % what)
 
     def _records_update(self, flags, reward, game_over, T):
-        rc = self.L.cagym_episode_records_update(self.h, flags.data_ptr(), reward.data_ptr(), game_over.data_ptr(), int(T),
-                                                 self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_episode_records_update")
+        rc = self._records_fn(self.h, flags.data_ptr(), reward.data_ptr(), game_over.data_ptr(), int(T), self._stream())
+        if rc:
+            _lib.check(self.L, self.h, rc, "cagym_episode_records_update")
 
     def _records_out(self, out, n_steps):
         """reward / flags / game_over slices for the recorder: the caller's, or private ones where `out` has none."""
@@ -441,11 +449,8 @@ class BatchedCollisionAvoidanceEnv(object):
 
     def restart_episode_records(self, world_mask=None, clear_table=False):
         """The masked worlds (None = all) forget the episode in progress; clear_table also empties the table and desync."""
-        m = None
-        if world_mask is not None:
-            m = torch.as_tensor(world_mask, device=self.device).to(torch.uint8).contiguous()
-        rc = self.L.cagym_episode_records_restart(self.h, None if m is None else m.data_ptr(), int(bool(clear_table)), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_episode_records_restart")
+        m = self._mask(world_mask)
+        _lib.call(self.L, self.h, "cagym_episode_records_restart", _lib.ptr(m), int(bool(clear_table)), self._stream())
 
     def episode_records(self, check=True):
         """Zero-copy device views of the recorder: the table t / extra_t [S, M] f64, flags [S, M] u8, ret [S] f64, steps /
@@ -454,7 +459,7 @@ class BatchedCollisionAvoidanceEnv(object):
         n_agents [S] rides along for stats.suite_statistics."""
         if self._rec_views is None:
             rp = _lib.CagymEpisodeRecordPtrs()
-            _lib.check(self.L, self.h, self.L.cagym_episode_records_get(self.h, C.byref(rp)), "cagym_episode_records_get")
+            _lib.call(self.L, self.h, "cagym_episode_records_get", C.byref(rp))
             dims = {"S": (self.S,), "SM": (self.S, self.M), "N": (self.N,), "NM": (self.N, self.M), "1": (1,)}
             v = {}
             for name, ts, shape in _lib.EPREC_FIELDS:
@@ -470,13 +475,6 @@ class BatchedCollisionAvoidanceEnv(object):
                                    "again to clear" % d)
         return dict(self._rec_views)
 
-    def _ig_boundary(self, team_reward, game_over):
-        """The episodic IG team's end of a step: the running return, and the restart of the worlds the step just finished."""
-        g = self._igm
-        if g is not None and g.episodic:
-            from .ig import EPISODE_FOLD
-            g.ig.episode_boundary(g.planner.P, g.planner.workspace, team_reward, game_over, EPISODE_FOLD)
-
     # ---- the split step: env.step() in two launches (include/cagym.h: cagym_step_begin / cagym_step_finish) ------------------
     def step_begin(self, stream=None):
         """First half of step(): the internal RVO policies' half-planes and linear programs on the current state (they do not
@@ -485,7 +483,7 @@ class BatchedCollisionAvoidanceEnv(object):
         orders step_finish behind it (step_overlapped does).  Refused while a policy is attached (see step_finish)."""
         self._refuse_split()
         raw = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
-        _lib.check(self.L, self.h, self.L.cagym_step_begin(self.h, raw), "cagym_step_begin")
+        _lib.call(self.L, self.h, "cagym_step_begin", raw)
 
     def _refuse_split(self):
         if self._drives_ga3c() or self._igm is not None:
@@ -497,11 +495,8 @@ class BatchedCollisionAvoidanceEnv(object):
         Takes every action from the caller: refused while attach_ga3c / attach_ig_mcts drive agents inside step()."""
         self._refuse_split()
         self._records_contract(auto_reset, "step_finish")
-        a = None
-        if actions is not None:
-            a = torch.as_tensor(actions, device=self.device).to(torch.float32).reshape(self.N, self.M, 2).contiguous()
-        rc = self.L.cagym_step_finish(self.h, None if a is None else a.data_ptr(), C.byref(self._out), int(bool(auto_reset)), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_step_finish")
+        a = self._actions(actions)
+        _lib.call(self.L, self.h, "cagym_step_finish", _lib.ptr(a), C.byref(self._out), int(bool(auto_reset)), self._stream())
         if self._rec is not None:
             self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
@@ -543,84 +538,63 @@ class BatchedCollisionAvoidanceEnv(object):
         update, team reward into out["team_reward"][t], plan, robot actions, step, episode boundary), no host synchronisation
         either; not under stream capture (the planner's call_base is a kernel argument the host advances per call)."""
         self._records_contract(auto_reset, "rollout")
-        if self._igm is not None and not self._igm.episodic:
-            k = self._igm.kind
+        T, g = int(n_steps), self._igm
+        if g is not None and not g.episodic:
             raise RuntimeError("rollout() with %s attached is not implemented for this attach (the planner needs per-world "
-                               "restarts): attach_%s(episodic=True)" % (k, k))
-        if self._igm is not None:
-            if torch.cuda.is_current_stream_capturing():
-                if self._igm.kind == "ig_greedy":
-                    raise RuntimeError("rollout() with ig_greedy attached cannot be captured in a graph: the chain allocates its "
-                                       "observed-set buffers per step and has not been validated under capture")
-                raise RuntimeError("rollout() with ig_mcts attached cannot be captured in a graph: the planner's call_base is a "
-                                   "by-value kernel argument that the host advances with every planning step")
-            if out is None:
-                out = self.alloc_rollout(n_steps)
-            if out.get("team_reward") is None:
-                out["team_reward"] = torch.empty((int(n_steps), self.N), dtype=torch.float64, device=self.device)
-            caller_out, out = out, self._records_out(out, n_steps)
-            fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
-            keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
-            # the robots' detector reads the OtherAgentsStates table of the step before: slice t - 1, or the env's own table, which
-            # every step writes when the caller asked for no observation slices and which ends up holding the last step's rows
-            sliced = out.get("other_agents_states") is not None
-            for t in range(int(n_steps)):
-                a = self._internal_actions(None, team_reward_out=out["team_reward"][t],
-                                           oas=out["other_agents_states"][t - 1] if sliced and t > 0 else None)
-                o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in keys])
-                if not sliced:
-                    o.obs_oas = self.obs_oas.data_ptr()
-                rc = fn(self.h, a.data_ptr(), C.byref(o), self._stream())
-                _lib.check(self.L, self.h, rc, "cagym_step")
-                self._ig_boundary(out["team_reward"][t], out["game_over"][t] if auto_reset else None)
-            if sliced and int(n_steps) > 0:
-                self.obs_oas.copy_(out["other_agents_states"][int(n_steps) - 1])
-            if self._rec is not None:  # one launch over the chain's T slices, behind its last step
-                self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
-            return caller_out
+                               "restarts): attach_%s(episodic=True)" % (g.kind, g.kind))
+        if g is not None and torch.cuda.is_current_stream_capturing():
+            if g.kind == "ig_greedy":
+                raise RuntimeError("rollout() with ig_greedy attached cannot be captured in a graph: the chain allocates its "
+                                   "observed-set buffers per step and has not been validated under capture")
+            raise RuntimeError("rollout() with ig_mcts attached cannot be captured in a graph: the planner's call_base is a "
+                               "by-value kernel argument that the host advances with every planning step")
         if out is None:
-            out = self.alloc_rollout(n_steps)
-        caller_out, out = out, self._records_out(out, n_steps)
-        if self._drives_ga3c():
-            fn = self.L.cagym_step_autoreset if auto_reset else self.L.cagym_step
-            keys = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")
-            for t in range(int(n_steps)):
-                self._ga3c.act_merge(None, self._act)
-                o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in keys])
-                rc = fn(self.h, self._act.data_ptr(), C.byref(o), self._stream())
-                _lib.check(self.L, self.h, rc, "cagym_step")
-            if self._rec is not None:  # one launch over the chain's T slices, behind its last step
-                self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
-            return caller_out
-        o = self._outputs(out.get("other_agents_states"), out.get("ego"), out.get("laserscan"), out.get("reward"),
-                          out.get("flags"), out.get("game_over"))
-        # (no torch.cuda.device context here and in step(): the library switches to the handle's device itself - DEVGUARD)
-        rc = self.L.cagym_rollout(self.h, int(n_steps), int(bool(auto_reset)), C.byref(o), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_rollout")
-        if self._rec is not None:
-            self._records_update(out["flags"], out["reward"], out["game_over"], n_steps)
+            out = self.alloc_rollout(T)
+        if g is not None and out.get("team_reward") is None:
+            out["team_reward"] = torch.empty((T, self.N), dtype=torch.float64, device=self.device)
+        caller_out, out = out, self._records_out(out, T)
+        if g is None and not self._drives_ga3c():
+            o = self._outputs(*[out.get(k) for k in _OUT_KEYS])
+            rc = self._rollout_fn(self.h, T, int(bool(auto_reset)), C.byref(o), self._stream())
+            if rc:
+                _lib.check(self.L, self.h, rc, "cagym_rollout")
+        else:
+            # an IG team's detector reads the OtherAgentsStates table of the step before: slice t - 1, or the env's own table, which
+            # every step writes when the caller asked for no observation slices and which ends up holding the last step's rows
+            oas = out.get("other_agents_states") if g is not None else None
+            restart = team_reward = prev = None  # what only an IG team needs (the GA3C-only chain stays capturable in a graph)
+            for t in range(T):
+                o = self._outputs(*[None if out.get(k) is None else out[k][t] for k in _OUT_KEYS])
+                if g is not None:
+                    team_reward, restart = out["team_reward"][t], out["game_over"][t] if auto_reset else None
+                    if oas is None:
+                        o.obs_oas = self.obs_oas.data_ptr()
+                    elif t > 0:
+                        prev = oas[t - 1]
+                self._chained_step(None, o, auto_reset, restart, team_reward, prev)
+            if oas is not None and T > 0:
+                self.obs_oas.copy_(oas[T - 1])
+        if self._rec is not None:  # one launch behind the last step, over all T slices
+            self._records_update(out["flags"], out["reward"], out["game_over"], T)
         return caller_out
 
     def kernel_name(self, rollout=True, auto_reset=True):
         """The kernel instantiation the library launches for this handle (as rocprofv3 --kernel-trace names it)."""
         buf = C.create_string_buffer(128)
-        _lib.check(self.L, self.h, self.L.cagym_kernel_name(self.h, int(bool(rollout)), int(bool(auto_reset)), buf, 128),
-                   "cagym_kernel_name")
+        _lib.call(self.L, self.h, "cagym_kernel_name", int(bool(rollout)), int(bool(auto_reset)), buf, 128)
         return buf.value.decode()
 
     def sense_laserscan(self, out=None):
         if out is None:
             out = torch.empty((self.N, self.M, 16), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_laserscan(self.h, out.data_ptr(), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_laserscan")
+        _lib.call(self.L, self.h, "cagym_laserscan", out.data_ptr(), self._stream())
         return out
 
     # ---- zero-copy state views --------------------------------------------------------------------
     def state(self):
         if self._state is None:
             sp = _lib.CagymStatePtrs()
-            _lib.check(self.L, self.h, self.L.cagym_get_state(self.h, C.byref(sp)), "cagym_get_state")
+            _lib.call(self.L, self.h, "cagym_get_state", C.byref(sp))
             N, M = self.N, self.M
             shapes = {"action": (N, M, 2), "n_agents": (N,), "episode": (N,), "stat_return": (N,),
                       "stat_episodes": (N,), "stat_steps": (N,), "stat_outcomes": (N, 3),
@@ -644,9 +618,7 @@ class BatchedCollisionAvoidanceEnv(object):
         """[N, 6] int32 records (stats.py layout) written by ONE kernel on the current stream (cagym_pack_episode_stats)."""
         if out is None:
             out = torch.empty((self.N, 6), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.L.cagym_pack_episode_stats(self.h, out.data_ptr(), self._stream())
-        _lib.check(self.L, self.h, rc, "cagym_pack_episode_stats")
+        _lib.call(self.L, self.h, "cagym_pack_episode_stats", out.data_ptr(), self._stream())
         return out
 
     # ---- parity-test interface (f/u/i accessors used by tests/golden_util.replay) ----------------------------

@@ -28,10 +28,14 @@ uses the global np.random stream, so only statistical agreement with it is possi
 planner is also the executable specification of the device tree (csrc/cagym_dmcts.h, cagym_dmcts_plan): same
 generator keys, same summation orders, same tie rules -- the two make identical decisions (tests/test_dmcts.py).
 """
-import ctypes
+import ctypes as C
 import math
 
 import numpy as np
+import torch
+
+from . import _lib
+from .ig import EPISODE_PLANS_ONLY
 
 _M64 = (1 << 64) - 1
 
@@ -249,11 +253,7 @@ class DecMCTSPlanner(object):
         return actions, paths
 
 
-class DmctsParams(ctypes.Structure):
-    """cagym_dmcts_params (include/cagym.h)."""
-    _fields_ = [(n, ctypes.c_int32) for n in ("n_robots", "Ntree", "Nsims", "horizon", "Ncycles", "comm_n", "xdt", "reset_comms")] + \
-               [("call_base", ctypes.c_uint32), ("parallel_agents", ctypes.c_uint32)] + \
-               [(n, ctypes.c_double) for n in ("c_p", "gamma", "radius", "dt", "fov_rad", "range")] + [("seed", ctypes.c_uint64)]
+DmctsParams = _lib.DmctsParams  # the struct mirrors live beside the prototypes
 
 
 class DeviceDecMCTSPlanner(object):
@@ -265,21 +265,11 @@ class DeviceDecMCTSPlanner(object):
 
     def __init__(self, ig, n_robots, radius=0.5, Ntree=30, Nsims=10, horizon=4, c_p=1.0, gamma=0.95, Ncycles=5, comm_n=5,
                  seed=0, parallelize_agents=False):
-        import ctypes as C
-        import torch
-        from . import _lib
-        self._C, self._torch, self._lib = C, torch, _lib
         self.ig, self.b, self.L = ig, ig.b, ig.L
         self.N, self.R = ig.b.N, int(n_robots)
-
-        Params = DmctsParams  # (include/cagym.h)
-        self.P = Params(self.R, int(Ntree), int(Nsims), int(horizon), int(Ncycles), int(comm_n), ig.xdt, 1, 0,
-                        int(bool(parallelize_agents)), float(c_p), float(gamma), float(radius), ig.dt, ig.fov, ig.range,
-                        int(seed) & _M64)
-        self.L.cagym_dmcts_workspace_bytes.restype = C.c_size_t
-        self.L.cagym_dmcts_workspace_bytes.argtypes = [C.c_int, C.POINTER(Params)]
-        self.L.cagym_dmcts_plan.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        self.P = DmctsParams(self.R, int(Ntree), int(Nsims), int(horizon), int(Ncycles), int(comm_n), ig.xdt, 1, 0,
+                             int(bool(parallelize_agents)), float(c_p), float(gamma), float(radius), ig.dt, ig.fov, ig.range,
+                             int(seed) & _M64)
         nbytes = self.L.cagym_dmcts_workspace_bytes(self.N, C.byref(self.P))
         dev = self.b.device
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -295,9 +285,7 @@ class DeviceDecMCTSPlanner(object):
         if world_mask is None:
             self.P.reset_comms = 1
             return
-        from .ig import EPISODE_PLANS_ONLY
-        m = self._torch.as_tensor(world_mask, device=self.b.device).to(self._torch.uint8).reshape(self.N).contiguous()
-        self.ig.episode_boundary(self.P, self.workspace, None, m, EPISODE_PLANS_ONLY)
+        self.ig.episode_boundary(self.P, self.workspace, None, self.b._mask(world_mask).reshape(self.N), EPISODE_PLANS_ONLY)
 
     @property
     def parallelize_agents(self):
@@ -308,23 +296,19 @@ class DeviceDecMCTSPlanner(object):
         """Switch the mode for the next plan(); the communicated plans are kept.  The sequential workspace is the first
         part of the agent-parallel one, so a workspace that grows keeps its contents."""
         self.P.parallel_agents = int(bool(on))
-        nbytes = self.L.cagym_dmcts_workspace_bytes(self.N, self._C.byref(self.P))
+        nbytes = self.L.cagym_dmcts_workspace_bytes(self.N, C.byref(self.P))
         if nbytes > self.workspace.numel():
-            ws = self._torch.zeros(nbytes, dtype=self._torch.uint8, device=self.workspace.device)
+            ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.workspace.device)
             ws[:self.workspace.numel()].copy_(self.workspace)
             self.workspace = ws
 
     def plan(self, poses):
         """poses [N, R, 3] (torch or numpy).  Returns device tensors (actions [N,R,2], paths [N,R,8] uint8, where
         254 marks an infeasible random draw and 255 the end of the path)."""
-        torch, C = self._torch, self._C
         p = torch.as_tensor(poses, device=self.b.device).to(torch.float64).reshape(self.N, self.R, 3).contiguous()
         self.P.call_base = self.calls & 0xFFFFFFFF
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_dmcts_plan(self.b.h, C.byref(self.P), p.data_ptr(), self.workspace.data_ptr(),
-                                         self.workspace.numel(), self.actions.data_ptr(), self.paths.data_ptr(),
-                                         self.stats.data_ptr(), self.b._stream())
-        self._lib.check(self.L, self.b.h, rc, "cagym_dmcts_plan")
+        _lib.call(self.L, self.b.h, "cagym_dmcts_plan", C.byref(self.P), p.data_ptr(), self.workspace.data_ptr(),
+                  self.workspace.numel(), self.actions.data_ptr(), self.paths.data_ptr(), self.stats.data_ptr(), self.b._stream())
         self.calls += self.R * self.P.Ncycles * self.P.Ntree
         self.P.reset_comms = 0
         return self.actions, self.paths

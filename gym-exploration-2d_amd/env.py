@@ -468,10 +468,8 @@ class CollisionAvoidanceEnv(object):
         robots = [a.policy for a in self.agents if isinstance(a.policy, _IG_POLICIES)]
         if robots and any(type(p) is not type(robots[0]) for p in robots[1:]):
             raise ValueError("ig_mcts and ig_greedy agents cannot share an env: one policy drives the whole team")
-        if robots and isinstance(robots[0], ig_greedy):
-            self._attach_greedy(robots)
-        elif robots:
-            self._attach_planner(robots)
+        if robots:
+            self._attach_ig(robots)
         self.episode_step_number += 1
         self.total_number_of_steps += 1
         _, rew, go, _ = self._benv.step(ext)
@@ -488,38 +486,30 @@ class CollisionAvoidanceEnv(object):
         which = {a.id: bool(a.is_done) for a in self.agents}
         return obs, rewards, game_over, {'which_agents_done': which}
 
-    def _attach_planner(self, robots):
-        """The robots' common set_param values drive one device planner per env (attached again when they change)."""
+    def _attach_ig(self, robots):
+        """The robots' common set_param / init_maps values drive one device planner or one greedy policy per env (attached again
+        when they, the seed or the team change)."""
+        greedy = isinstance(robots[0], ig_greedy)
         if any(p.params is None for p in robots):
-            raise RuntimeError("an ig_mcts agent has no parameters: call policy.set_param(...) after reset() and before step()")
-        params = robots[0].params
-        if any(p.params != params for p in robots[1:]):
-            raise ValueError("all ig_mcts agents of the env must share the same set_param planner parameters "
-                             "(one Dec-MCTS planner plans the whole team)")
-        if params["dt"] != self._sig[5]:
-            raise ValueError("ig_mcts.set_param: dt must equal Config.DT")
-        key = (tuple(sorted(params.items())), self.planner_seed, len(robots))
-        if self._ig_key != key or self._benv._igm is None:
-            p = dict(params)
-            del p["dt"]
-            self._benv.attach_ig_mcts(seed=self.planner_seed, **p)
-            self._ig_key = key
-
-
-    def _attach_greedy(self, robots):
-        """The robots' common init_maps values drive one greedy policy per env (attached again when they change)."""
-        if any(p.params is None for p in robots):
-            raise RuntimeError("an ig_greedy agent has no maps: call policy.init_maps(...) after reset() and before step()")
+            raise RuntimeError("an ig_greedy agent has no maps: call policy.init_maps(...) after reset() and before step()" if greedy else
+                               "an ig_mcts agent has no parameters: call policy.set_param(...) after reset() and before step()")
         params = robots[0].params
         if any(p.params != params for p in robots[1:]):
             raise ValueError("all ig_greedy agents of the env must share the same init_maps values and radius "
-                             "(one launch chooses for the whole team)")
+                             "(one launch chooses for the whole team)" if greedy else
+                             "all ig_mcts agents of the env must share the same set_param planner parameters "
+                             "(one Dec-MCTS planner plans the whole team)")
         if params["dt"] != self._sig[5]:
-            raise ValueError("ig_greedy.init_maps: dt must equal Config.DT")
-        key = ("ig_greedy", tuple(sorted(params.items())), len(robots))
+            raise ValueError("%s: dt must equal Config.DT" % ("ig_greedy.init_maps" if greedy else "ig_mcts.set_param"))
+        key = (("ig_greedy", tuple(sorted(params.items())), len(robots)) if greedy else
+               (tuple(sorted(params.items())), self.planner_seed, len(robots)))
         if self._ig_key != key or self._benv._igm is None:
-            self._benv.attach_ig_greedy(detect_fov=params["detect_fov"], detect_range=params["detect_range"],
-                                        radius=params["radius"])
+            p = dict(params)
+            del p["dt"]
+            if greedy:
+                self._benv.attach_ig_greedy(**p)
+            else:
+                self._benv.attach_ig_mcts(seed=self.planner_seed, **p)
             self._ig_key = key
 
 

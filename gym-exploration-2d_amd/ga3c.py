@@ -7,7 +7,6 @@ agent) by one batched forward over every GA3C agent of every world.  Weights com
 (tools/convert_ga3c_checkpoint.py -> weights/ga3c_cadrl_*.npz), packed in the blob order of include/cagym.h.
 `forward_torch` is a plain-torch restatement kept only as a numerics reference for the tests.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -34,17 +33,7 @@ class GA3CCADRLPolicy(object):
     def __init__(self, benv, checkpoint="iros18", max_observed=None):
         self.b = benv
         self.L = benv.L
-        self.L.cagym_ga3c_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        self.L.cagym_ga3c_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.cagym_ga3c_act_workspace_bytes.argtypes = [C.c_void_p]
-        self.L.cagym_ga3c_act_workspace_bytes.restype = C.c_size_t
-        self.L.cagym_ga3c_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.cagym_ga3c_act.restype = C.c_int
-        self.L.cagym_ga3c_act_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.cagym_ga3c_act_merge.restype = C.c_int
-        self.L.cagym_ga3c_load_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.cagym_ga3c_load_weights.restype = C.c_int
+        self._act_merge = self.L.cagym_ga3c_act_merge  # called once per step of a chain: resolved here
         self._work = None
         path = checkpoint if os.path.exists(checkpoint) else os.path.join(HERE, "weights", "ga3c_cadrl_%s.npz" % checkpoint)
         W = np.load(path)
@@ -66,14 +55,10 @@ class GA3CCADRLPolicy(object):
 
     def load_weights(self):
         """Tell the handle that `self.blob` was rewritten in place (it caches the blob as matrix-core operand fragments by address)."""
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ga3c_load_weights(self.b.h, self.blob.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ga3c_load_weights")
+        _lib.call(self.L, self.b.h, "cagym_ga3c_load_weights", self.blob.data_ptr(), self.b._stream())
 
     def states(self):
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ga3c_state(self.b.h, self.max_observed, self.state.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ga3c_state")
+        _lib.call(self.L, self.b.h, "cagym_ga3c_state", self.max_observed, self.state.data_ptr(), self.b._stream())
         return self.state
 
     def agent_index(self):
@@ -96,11 +81,8 @@ class GA3CCADRLPolicy(object):
         Bn = int(idx.numel())
         act = torch.empty((Bn,), dtype=torch.int32, device=b.device)
         probs = torch.empty((Bn, 11), dtype=torch.float32, device=b.device) if want_probs else None
-        with torch.cuda.device(b.device):
-            rc = self.L.cagym_ga3c_forward(b.h, self.blob.data_ptr(), st.data_ptr(), idx.data_ptr(), Bn,
-                                           None if ext_actions is None else ext_actions.data_ptr(), act.data_ptr(),
-                                           None if probs is None else probs.data_ptr(), b._stream())
-        _lib.check(self.L, b.h, rc, "cagym_ga3c_forward")
+        _lib.call(self.L, b.h, "cagym_ga3c_forward", self.blob.data_ptr(), st.data_ptr(), idx.data_ptr(), Bn, _lib.ptr(ext_actions),
+                  act.data_ptr(), _lib.ptr(probs), b._stream())
         return act, probs
 
     def forward_torch(self, x75):
@@ -140,21 +122,23 @@ class GA3CCADRLPolicy(object):
             self.states()
             self.forward(ext_actions=ext_actions)
             return ext_actions
-        if self._work is None:
-            self._work = torch.empty((int(self.L.cagym_ga3c_act_workspace_bytes(b.h)),), dtype=torch.uint8, device=b.device)
-        with torch.cuda.device(b.device):
-            rc = self.L.cagym_ga3c_act(b.h, self.blob.data_ptr(), self.max_observed, self._work.data_ptr(), ext_actions.data_ptr(), b._stream())
-        _lib.check(self.L, b.h, rc, "cagym_ga3c_act")
+        _lib.call(self.L, b.h, "cagym_ga3c_act", self.blob.data_ptr(), self.max_observed, self._workspace().data_ptr(),
+                  ext_actions.data_ptr(), b._stream())
         return ext_actions
+
+    def _workspace(self):
+        if self._work is None:
+            n = int(self.L.cagym_ga3c_act_workspace_bytes(self.b.h))
+            self._work = torch.empty((n,), dtype=torch.uint8, device=self.b.device)
+        return self._work
 
     def act_merge(self, ext_in, actions):
         """The whole action table in one launch (cagym_ga3c_act_merge): actions [N,M,2] f32 gets this policy's action for every
         active GA3C agent and ext_in's row (or (0, 0) when ext_in is None) for every other slot; ext_in is not written."""
         b = self.b
         assert actions.is_contiguous() and actions.dtype == torch.float32
-        if self._work is None:
-            self._work = torch.empty((int(self.L.cagym_ga3c_act_workspace_bytes(b.h)),), dtype=torch.uint8, device=b.device)
-        rc = self.L.cagym_ga3c_act_merge(b.h, self.blob.data_ptr(), self.max_observed, self._work.data_ptr(),
-                                         None if ext_in is None else ext_in.data_ptr(), actions.data_ptr(), b._stream())
-        _lib.check(self.L, b.h, rc, "cagym_ga3c_act_merge")
+        rc = self._act_merge(b.h, self.blob.data_ptr(), self.max_observed, self._workspace().data_ptr(), _lib.ptr(ext_in),
+                             actions.data_ptr(), b._stream())
+        if rc:
+            _lib.check(self.L, b.h, rc, "cagym_ga3c_act_merge")
         return actions

@@ -18,10 +18,7 @@ PRIMITIVES = np.array([[v, w] for v in (0.0, 2.0, 4.0) for w in (-0.5 * np.pi, 0
 GREEDY_V, GREEDY_W = (0.0, 2.0, 4.0), (-np.pi, 0.0, np.pi)  # ig_greedy.py:65-66: candidate c = 3 a + b is (v[a], w[b])
 
 
-class GreedyParams(C.Structure):
-    """cagym_ig_greedy_params (include/cagym.h)."""
-    _fields_ = [("n_robots", C.c_int32), ("coordinate", C.c_int32)] + \
-               [(n, C.c_double) for n in ("dt", "radius", "fov_rad", "range")] + [("v", C.c_double * 3), ("w", C.c_double * 3)]
+GreedyParams = _lib.GreedyParams  # the struct mirrors live beside the prototypes
 
 
 class InfoGain(object):
@@ -29,30 +26,15 @@ class InfoGain(object):
         self.b = benv
         self.L = benv.L
         self.fov, self.range, self.xdt, self.dt = float(fov_rad), float(sens_range), int(xdt), float(dt)
-        L = self.L
         vp = C.c_void_p
-        L.cagym_ig_init.argtypes = [vp, vp]
-        L.cagym_ig_reset_belief.argtypes = [vp, vp, vp]
-        L.cagym_ig_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-        L.cagym_ig_visible_cells.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp]
-        L.cagym_ig_update_belief.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
-        L.cagym_ig_mi_reward.argtypes = [vp, vp, vp, C.c_int, vp, vp]
-        L.cagym_ig_next_pose.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
-        L.cagym_ig_rollouts.argtypes = [vp] * 7 + [C.c_int] * 4 + [C.c_double] * 3 + [C.c_uint64, vp, vp, vp, vp, vp]
-        L.cagym_ig_robot_inputs.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
-        L.cagym_ig_robot_actions.argtypes = [vp, C.c_int, vp, vp, vp]
-        L.cagym_ig_get_episode_stats.argtypes = [vp] + [C.POINTER(vp)] * 4
-        L.cagym_ig_episode_boundary.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, vp]
-        L.cagym_ig_greedy_plan.argtypes = [vp, C.POINTER(GreedyParams), vp, vp, vp, vp, vp, vp]
-        with torch.cuda.device(benv.device):
-            _lib.check(L, benv.h, L.cagym_ig_init(benv.h, benv._stream()), "cagym_ig_init")
+        _lib.call(self.L, self.b.h, "cagym_ig_init", benv._stream())
         d2, bel = vp(), vp()
-        _lib.check(L, benv.h, L.cagym_ig_get(benv.h, C.byref(d2), C.byref(bel)), "cagym_ig_get")
+        _lib.call(self.L, self.b.h, "cagym_ig_get", C.byref(d2), C.byref(bel))
         from .batched_env import _DevArray
         self.edf_d2 = torch.as_tensor(_DevArray(d2.value, (benv.S, 300, 300), "i4"), device=benv.device)
         self.belief = torch.as_tensor(_DevArray(bel.value, (benv.N, 60, 60), "f8"), device=benv.device)
         acc = [vp() for _ in range(4)]
-        _lib.check(L, benv.h, L.cagym_ig_get_episode_stats(benv.h, *[C.byref(a) for a in acc]), "cagym_ig_get_episode_stats")
+        _lib.call(self.L, self.b.h, "cagym_ig_get_episode_stats", *[C.byref(a) for a in acc])
         # the team reward's per-world episode accumulators (cagym_ig_episode_boundary); zeroed by cagym_ig_init
         self.episode_stats = {k: torch.as_tensor(_DevArray(a.value, (benv.N,), ts), device=benv.device)
                               for k, a, ts in zip(("running", "sum", "last", "episodes"), acc, ("f8", "f8", "f8", "i4"))}
@@ -66,24 +48,20 @@ class InfoGain(object):
     def robot_inputs(self, n_robots, detect_range, obs_oas, poses, detections, n_det):
         """cagym_ig_robot_inputs: the R robots' poses [N,R,3] and detections [N,R,M-1,2] / n_det [N,R] (the detector emulation of
         find_targets_in_obs on their rows of obs_oas), written into the given device tensors."""
-        rc = self.L.cagym_ig_robot_inputs(self.b.h, int(n_robots), float(detect_range), obs_oas.data_ptr(), poses.data_ptr(),
-                                          detections.data_ptr(), n_det.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_robot_inputs")
+        _lib.call(self.L, self.b.h, "cagym_ig_robot_inputs", int(n_robots), float(detect_range), obs_oas.data_ptr(), poses.data_ptr(),
+                  detections.data_ptr(), n_det.data_ptr(), self.b._stream())
 
     def robot_actions(self, n_robots, planner_actions, actions):
         """cagym_ig_robot_actions: the planner's (v, omega) [N,R,2] f64 into the robots' rows of actions [N,M,2] f32."""
-        rc = self.L.cagym_ig_robot_actions(self.b.h, int(n_robots), planner_actions.data_ptr(), actions.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_robot_actions")
+        _lib.call(self.L, self.b.h, "cagym_ig_robot_actions", int(n_robots), planner_actions.data_ptr(), actions.data_ptr(), self.b._stream())
 
     def edf(self):
         """[S,300,300] f64 Euclidean distance field in metres (edfMap.map)."""
         return self.edf_d2.double().sqrt() * 0.1
 
     def reset_belief(self, world_mask=None):
-        m = None if world_mask is None else self._t(world_mask, torch.uint8)
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_reset_belief(self.b.h, None if m is None else m.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_reset_belief")
+        m = self.b._mask(world_mask)
+        _lib.call(self.L, self.b.h, "cagym_ig_reset_belief", _lib.ptr(m), self.b._stream())
 
     def episode_boundary(self, params, workspace, team_reward=None, restart_mask=None, flags=0):
         """cagym_ig_episode_boundary on the current stream: running += team_reward [N] f64; the worlds of the DEVICE mask
@@ -93,20 +71,16 @@ class InfoGain(object):
             restart_mask = self._t(restart_mask, torch.uint8, (self.b.N,))
         if team_reward is not None and (team_reward.dtype != torch.float64 or not team_reward.is_contiguous()):
             team_reward = self._t(team_reward, torch.float64, (self.b.N,))
-        rc = self.L.cagym_ig_episode_boundary(self.b.h, C.byref(params), None if team_reward is None else team_reward.data_ptr(),
-                                              None if restart_mask is None else restart_mask.data_ptr(), int(flags),
-                                              workspace.data_ptr(), workspace.numel(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_episode_boundary")
+        _lib.call(self.L, self.b.h, "cagym_ig_episode_boundary", C.byref(params), _lib.ptr(team_reward), _lib.ptr(restart_mask), int(flags),
+                  workspace.data_ptr(), workspace.numel(), self.b._stream())
 
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
         world = self._t(world, torch.int32, (-1,))
         Q = poses.shape[0]
         masks = torch.empty((Q, 60), dtype=torch.int64, device=self.b.device)
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_visible_cells(self.b.h, poses.data_ptr(), world.data_ptr(), Q, self.fov, self.range,
-                                               masks.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_visible_cells")
+        _lib.call(self.L, self.b.h, "cagym_ig_visible_cells", poses.data_ptr(), world.data_ptr(), Q, self.fov, self.range, masks.data_ptr(),
+                  self.b._stream())
         return masks
 
     def update_belief(self, poses, detections, n_det, n_poses=None):
@@ -119,11 +93,8 @@ class InfoGain(object):
         nd = self._t(n_det, torch.int32, (N, P))
         npz = None if n_poses is None else self._t(n_poses, torch.int32, (N,))
         obs = torch.empty((N, 60), dtype=torch.int64, device=self.b.device)
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_update_belief(self.b.h, poses.data_ptr(), None if npz is None else npz.data_ptr(),
-                                               det.data_ptr(), nd.data_ptr(), P, Dmax, self.fov, self.range,
-                                               obs.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_update_belief")
+        _lib.call(self.L, self.b.h, "cagym_ig_update_belief", poses.data_ptr(), _lib.ptr(npz), det.data_ptr(), nd.data_ptr(), P, Dmax, self.fov,
+                  self.range, obs.data_ptr(), self.b._stream())
         return obs
 
     def mi_reward(self, masks, world, out=None):
@@ -132,10 +103,7 @@ class InfoGain(object):
         world = self._t(world, torch.int32, (-1,))
         if out is None:
             out = torch.empty((masks.shape[0],), dtype=torch.float64, device=self.b.device)
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_mi_reward(self.b.h, masks.data_ptr(), world.data_ptr(), masks.shape[0],
-                                           out.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_mi_reward")
+        _lib.call(self.L, self.b.h, "cagym_ig_mi_reward", masks.data_ptr(), world.data_ptr(), masks.shape[0], out.data_ptr(), self.b._stream())
         return out
 
     def next_pose(self, poses, actions, world, radius):
@@ -146,11 +114,8 @@ class InfoGain(object):
         Q = poses.shape[0]
         nxt = torch.empty((Q, 3), dtype=torch.float64, device=self.b.device)
         ok = torch.empty((Q,), dtype=torch.uint8, device=self.b.device)
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_next_pose(self.b.h, poses.data_ptr(), actions.data_ptr(), world.data_ptr(),
-                                           radius.data_ptr(), Q, self.xdt, self.dt, nxt.data_ptr(), ok.data_ptr(),
-                                           self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_next_pose")
+        _lib.call(self.L, self.b.h, "cagym_ig_next_pose", poses.data_ptr(), actions.data_ptr(), world.data_ptr(), radius.data_ptr(), Q, self.xdt,
+                  self.dt, nxt.data_ptr(), ok.data_ptr(), self.b._stream())
         return nxt, ok
 
     def greedy_plan(self, poses, coordinate=False, radius=0.5, v=GREEDY_V, w=GREEDY_W, out=None):
@@ -166,16 +131,13 @@ class InfoGain(object):
         R = poses.shape[1]
         if out is None:
             out = {"actions": torch.empty((N, R, 2), dtype=torch.float64, device=dev),
-                   "choice": torch.empty((N, R), dtype=torch.uint8, device=dev),
-                   "mi": torch.empty((N, R, 9), dtype=torch.float64, device=dev),
-                   "claimed": torch.empty((N, 60), dtype=torch.int64, device=dev)}
+                  "choice": torch.empty((N, R), dtype=torch.uint8, device=dev),
+                  "mi": torch.empty((N, R, 9), dtype=torch.float64, device=dev),
+                  "claimed": torch.empty((N, 60), dtype=torch.int64, device=dev)}
         P = GreedyParams(R, int(bool(coordinate)), self.dt, float(radius), self.fov, self.range,
                          (C.c_double * 3)(*[float(x) for x in v]), (C.c_double * 3)(*[float(x) for x in w]))
-        ptr = lambda k: None if out.get(k) is None else out[k].data_ptr()
-        with torch.cuda.device(dev):
-            rc = self.L.cagym_ig_greedy_plan(self.b.h, C.byref(P), poses.data_ptr(), ptr("actions"), ptr("choice"), ptr("mi"),
-                                             ptr("claimed"), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_greedy_plan")
+        _lib.call(self.L, self.b.h, "cagym_ig_greedy_plan", C.byref(P), poses.data_ptr(),
+                  *[_lib.ptr(out.get(k)) for k in ("actions", "choice", "mi", "claimed")], self.b._stream())
         return out
 
     def rollouts(self, pose0, observed0, exclude, world, n_steps, radius, nsims, seed, max_steps=None,
@@ -194,13 +156,9 @@ class InfoGain(object):
         acts = torch.full((Q, nsims, max(H, 1)), 255, dtype=torch.uint8, device=self.b.device)
         fin = torch.empty((Q, nsims, 3), dtype=torch.float64, device=self.b.device)
         obs_out = torch.empty((Q, nsims, 60), dtype=torch.int64, device=self.b.device) if want_observed else None
-        with torch.cuda.device(self.b.device):
-            rc = self.L.cagym_ig_rollouts(self.b.h, pose0.data_ptr(), observed0.data_ptr(), exclude.data_ptr(),
-                                          world.data_ptr(), n_steps.data_ptr(), radius.data_ptr(), Q, int(nsims),
-                                          max(H, 1), self.xdt, self.dt, self.fov, self.range, int(seed),
-                                          rew.data_ptr(), acts.data_ptr(), fin.data_ptr(),
-                                          None if obs_out is None else obs_out.data_ptr(), self.b._stream())
-        _lib.check(self.L, self.b.h, rc, "cagym_ig_rollouts")
+        _lib.call(self.L, self.b.h, "cagym_ig_rollouts", pose0.data_ptr(), observed0.data_ptr(), exclude.data_ptr(), world.data_ptr(),
+                  n_steps.data_ptr(), radius.data_ptr(), Q, int(nsims), max(H, 1), self.xdt, self.dt, self.fov, self.range,
+                  int(seed), rew.data_ptr(), acts.data_ptr(), fin.data_ptr(), _lib.ptr(obs_out), self.b._stream())
         return (rew, acts, fin, obs_out) if want_observed else (rew, acts, fin)
 
 
@@ -211,12 +169,9 @@ class GreedyPlanner(object):
     there solely so that cagym_ig_episode_boundary finds publications to clear when it restarts a world."""
 
     def __init__(self, ig, n_robots, radius=0.5, coordinate=False):
-        from .dmcts import DmctsParams
         self.ig, self.R = ig, int(n_robots)
         self.radius, self.coordinate = float(radius), bool(coordinate)
-        self.P = DmctsParams(self.R, 1, 1, 1, 1, 1, ig.xdt, 1, 0, 0, 1.0, 1.0, self.radius, ig.dt, ig.fov, ig.range, 0)
-        ig.L.cagym_dmcts_workspace_bytes.restype = C.c_size_t
-        ig.L.cagym_dmcts_workspace_bytes.argtypes = [C.c_int, C.POINTER(DmctsParams)]
+        self.P = _lib.DmctsParams(self.R, 1, 1, 1, 1, 1, ig.xdt, 1, 0, 0, 1.0, 1.0, self.radius, ig.dt, ig.fov, ig.range, 0)
         self.workspace = torch.zeros(ig.L.cagym_dmcts_workspace_bytes(ig.b.N, C.byref(self.P)), dtype=torch.uint8, device=ig.b.device)
         self._out = None
         self.actions = self.choice = self.mi = self.claimed = None

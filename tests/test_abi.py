@@ -1,9 +1,12 @@
 """CPU-side checks: the C-ABI library loads, exports every symbol include/*.h declares, refuses to run
-without a GPU (no CPU fallback), and the product never imports the oracle."""
+without a GPU (no CPU fallback), the ctypes prototypes and struct mirrors of _lib.py agree with include/cagym.h, and the
+product never imports the oracle."""
 import ctypes
 import glob
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -33,6 +36,92 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(L, s), "libcagym_hip.so does not export %s" % s
     assert L.cagym_version() == 112
+
+
+def _header_source():
+    src = open(os.path.join(ROOT, "include", "cagym.h")).read()
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared_parameter_counts():
+    """cagym_* function -> number of parameters, from the header text: the commas of the top-level parameter list."""
+    counts = {}
+    for name, params in re.findall(r"\b(cagym_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_source()):
+        params = params.strip()
+        counts[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return counts
+
+
+def test_every_declared_function_has_its_prototype_after_load_alone():
+    """_lib.load() alone - no env, no policy object - declares argtypes (as many as the header's parameters) for every function
+    of include/cagym.h, and the restype of those that do not return int."""
+    L = _lib()
+    counts = _declared_parameter_counts()
+    syms = _declared_symbols()
+    assert sorted(counts) == syms
+    assert counts["cagym_version"] == 0 and counts["cagym_ig_rollouts"] == 20 and counts["cagym_set_scenarios"] == 10
+    for name in syms:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, "%s has no argtypes" % name
+        assert len(fn.argtypes) == counts[name], (name, len(fn.argtypes), counts[name])
+    assert L.cagym_ga3c_act_workspace_bytes.restype is ctypes.c_size_t
+    assert L.cagym_dmcts_workspace_bytes.restype is ctypes.c_size_t
+    assert L.cagym_last_error.restype is ctypes.c_char_p
+
+
+def _c_compiler():
+    for c in ("cc", "gcc", "clang", os.environ.get("HIPCC", "hipcc")):  # (hipcc: the compiler the build itself needs)
+        if shutil.which(c):
+            return c
+    raise RuntimeError("no C compiler")
+
+
+def _header_struct_fields():
+    """struct name -> field names in order, from the header's typedefs (`double *a, *b;` and `double v[3], w[3];` included)."""
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct(?:\s+\w+)?\s*\{(.*?)\}\s*(\w+)\s*;", _header_source(), flags=re.S):
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if decl:
+                fields += [re.sub(r"\[.*?\]", "", d).replace("*", " ").split()[-1] for d in decl.split(",")]
+        out[name] = fields
+    return out
+
+
+def test_struct_mirrors_match_the_header_layout(tmp_path):
+    """sizeof and every field's name and offsetof, as the host C compiler lays out include/cagym.h, against the ctypes mirrors."""
+    lib = __import__("importlib").import_module("gym-exploration-2d_amd._lib")
+    mirrors = {"cagym_config": lib.CagymConfig, "cagym_outputs": lib.CagymOutputs, "cagym_state_ptrs": lib.CagymStatePtrs,
+               "cagym_scenario_ptrs": lib.CagymScenarioPtrs, "cagym_gen_params": lib.CagymGenParams,
+               "cagym_gen2_params": lib.CagymGen2Params, "cagym_dmcts_params": lib.DmctsParams,
+               "cagym_ig_greedy_params": lib.GreedyParams, "cagym_episode_record_ptrs": lib.CagymEpisodeRecordPtrs}
+    header = _header_struct_fields()
+    assert sorted(header) == sorted(mirrors)  # the package mirrors every struct the header defines
+    lines = []
+    for name, fields in header.items():
+        lines.append('printf("%s %%d\\n", (int)sizeof(%s));' % (name, name))
+        lines += ['printf("%s.%s %%d\\n", (int)offsetof(%s, %s));' % (name, f, name, f) for f in fields]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cagym.h"\nint main(void) {\n%s\nreturn 0; }\n' % "\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run([_c_compiler(), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    for name, S in mirrors.items():
+        assert [f[0] for f in S._fields_] == header[name], name
+        assert ctypes.sizeof(S) == int(got[name]), name
+        for f in header[name]:
+            assert getattr(S, f).offset == int(got["%s.%s" % (name, f)]), (name, f)
+    assert len(got) == sum(1 + len(f) for f in header.values())
+
+
+def test_prototypes_are_declared_in_one_place():
+    """No module of the package but _lib.py sets a ctypes prototype."""
+    pkg = os.path.join(ROOT, "gym-exploration-2d_amd")
+    for f in sorted(glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)):
+        if os.path.basename(f) != "_lib.py":
+            src = open(f).read()
+            assert ".argtypes" not in src and ".restype" not in src, os.path.relpath(f, ROOT)
 
 
 def test_no_cpu_fallback():

@@ -147,8 +147,6 @@ def test_workspace_bytes_by_mode():
     b = importlib.import_module("gym-exploration-2d_amd.build")
     b.build()
     L = importlib.import_module("gym-exploration-2d_amd._lib").load()
-    L.cagym_dmcts_workspace_bytes.restype = ctypes.c_size_t
-    L.cagym_dmcts_workspace_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(dm.DmctsParams)]
     P = dm.DmctsParams(3, 30, 10, 4, 5, 5, 5, 1, 0, 0, 1.0, 0.95, 0.5, 0.1, 0.5, 5.0, 0)
     N, trees = 16, 48
     al = lambda x: (x + 255) // 256 * 256

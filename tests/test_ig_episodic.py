@@ -463,7 +463,6 @@ def test_episodic_refusals_and_abi_checks():
     a.close()
     # before cagym_ig_init: CAGYM_E_STATE
     e = _env()
-    e.L.cagym_ig_episode_boundary.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     assert e.L.cagym_ig_episode_boundary(e.h, ctypes.byref(pa.P), None, None, 1, ws.data_ptr(), ws.numel(), e._stream()) == -5
     e.close()
 

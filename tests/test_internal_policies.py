@@ -560,6 +560,66 @@ def test_run_episode_shape_with_a_ga3c_agent_and_the_example():
     assert "cumulative team reward" in r.stdout
 
 
+# ---- GPU: GA3C and an episodic IG team attached together ------------------------------------------------------------
+def _ga3c_ig_env(B, N=4, M=4, S=8):
+    """Per scenario one GA3C agent (slot 0), two IG robots, one Static target in the robots' range, one rectangle.  The GA3C agent
+    of an even scenario starts 0.8 m from its goal: 3 * (0.8 - 0.75) / pref_speed = 0.15 s to reach it (agent.py:59-63), so it is
+    at its goal or out of time after two steps and the world (game_over_mode agent0) restarts on scenario w + N, even again."""
+    a6 = np.zeros((S, M, 6))
+    obst = np.zeros((S, 1, 4))
+    for s in range(S):
+        x0 = 0.5 * s - 8.0
+        a6[s, 0] = [x0, -8, x0 + (0.8 if s % 2 == 0 else 6.0), -8, 1.0, 0.5]
+        a6[s, 1] = [-5, -3 + 0.25 * s, 16, 0, 1.0, 0.5]
+        a6[s, 2] = [-2, -6, 16, 0, 1.0, 0.5]
+        a6[s, 3] = [-3, -2.5, 0, 0, 1.0, 0.2]
+        obst[s, 0] = [2 + 0.25 * s, 2, 8, 8]
+    pol = np.tile(np.array([scen.POLICY_GA3C, scen.POLICY_IGMCTS, scen.POLICY_IGMCTS, scen.POLICY_STATIC], dtype=np.int32), (S, 1))
+    dyn = np.tile(np.array([scen.DYN_UNICYCLE] + [scen.DYN_FIRSTORDER] * 3, dtype=np.int32), (S, 1))
+    env = B(N, M, n_scenarios=S, max_obstacles=1, game_over_mode="agent0")
+    env.set_scenarios(a6, pol, dyn, heading0=np.zeros((S, M)), obstacles=obst, n_obst=[1] * S)
+    env.reset()
+    env.attach_ga3c()
+    env.attach_ig_greedy(episodic=True)
+    return env
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("obs", [True, False])
+def test_ga3c_and_episodic_ig_rollout_equals_steps(obs):
+    """GA3C and an episodic IG team on one handle: rollout(4, auto_reset=True) == 4 x step(None, auto_reset=True), byte for byte,
+    with observation slices in `out` and without (the detector then reads the env's own OtherAgentsStates table)."""
+    import torch
+    B = _B()
+    T = 4
+    a, b = _ga3c_ig_env(B), _ga3c_ig_env(B)
+    out = a.rollout(T, auto_reset=True, out=a.alloc_rollout(T, obs=obs))
+    torch.cuda.synchronize()
+    assert ("other_agents_states" in out) == obs
+    for t in range(T):
+        b.step(None, auto_reset=True)
+        torch.cuda.synchronize()
+        pairs = [("reward", b.reward), ("flags", b.flags), ("game_over", b.game_over), ("team_reward", b.team_reward)]
+        if obs:
+            pairs += [("other_agents_states", b.obs_oas), ("ego", b.obs_ego)]
+        for k, src in pairs:
+            assert torch.equal(out[k][t], src), (k, t)
+    assert out["game_over"].any() and (out["team_reward"] > 0).any()  # worlds did restart, the robots did observe
+    assert torch.equal(a.obs_oas, b.obs_oas)  # the env's own table ends up holding the last step's rows either way
+    assert torch.equal(a.team_reward, b.team_reward)
+    assert torch.equal(a._act, b._act)
+    assert torch.equal(a._igm.ig.belief, b._igm.ig.belief)
+    sa, sb = a.ig_episode_stats(), b.ig_episode_stats()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    assert int(sa["episodes"].sum()) == int(out["game_over"].sum())
+    sa, sb = a.state(), b.state()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    a.close()
+    b.close()
+
+
 @pytest.mark.gpu
 def test_refusals():
     B = _B()

@@ -1,5 +1,6 @@
 """Host-side cost of one bracketed launch (what bench.py's wall clock adds to the kernel time of a 20-step block): micro-timings
-of the pieces of BatchedCollisionAvoidanceEnv.rollout and of the bracket itself, on a tiny handle."""
+of the pieces of BatchedCollisionAvoidanceEnv.rollout and of the bracket itself, and the host time of one step() call with nothing
+and with GA3C attached, on a tiny handle."""
 import ctypes as C
 import importlib
 import os
@@ -63,4 +64,27 @@ def bracket(with_events):
 for we in (False, True):
     r = sorted(bracket(we) for _ in range(500))
     print("bracketed 20-step rollout of 64 worlds, events %-5s: wall median %7.2f us, HIP events %7.2f us" % (we, r[250][0], sorted(x[1] for x in r)[250]))
+
+
+def host_us_per_step(e, ext, calls=20, blocks=500):
+    """Median host wall time of one e.step(ext, auto_reset=True) call: blocks of `calls` calls enqueued on an idle device."""
+    r = []
+    for _ in range(blocks):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            e.step(ext, auto_reset=True)
+        r.append((time.perf_counter() - t0) / calls * 1e6)
+    torch.cuda.synchronize(dev)
+    return sorted(r)[blocks // 2]
+
+
+ext = torch.zeros((N, M, 2), dtype=torch.float32, device=dev)
+print("env.step(ext, auto_reset=True), nothing attached: host wall median %7.2f us per call" % host_us_per_step(env, ext))
+pol = np.full((N, M), scen.POLICY_RVO, dtype=np.int32)
+pol[:, 0] = scen.POLICY_GA3C
+env.set_scenarios(scen.random_worlds_fast(N, M, seed=1), pol, scen.DYN_UNICYCLE, coop=np.full((N, M), 0.5))
+env.reset()
+env.attach_ga3c()
+print("env.step(ext, auto_reset=True), attach_ga3c, one GA3C agent per world: host wall median %7.2f us per call" % host_us_per_step(env, ext))
 env.close()
