@@ -81,6 +81,16 @@ class GreedyParams(C.Structure):
                [(n, C.c_double) for n in ("dt", "radius", "fov_rad", "range")] + [("v", C.c_double * 3), ("w", C.c_double * 3)]
 
 
+SNAP_MAGIC, SNAP_VERSION, SNAP_CORE, SNAP_IG = 0x43475331, 1, 1, 2  # CAGYM_SNAP_*
+
+
+class CagymSnapshotLayout(C.Structure):
+    """cagym_snapshot_layout (include/cagym.h)."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("n_worlds", C.c_int32), ("max_agents", C.c_int32),
+                ("n_scenarios", C.c_int32), ("max_obstacles", C.c_int32), ("fields", C.c_uint32), ("reserved", C.c_uint32),
+                ("row_bytes", C.c_uint64)]
+
+
 # ---- the prototypes of include/cagym.h: name -> argtypes; every function returns int except those of _RESTYPES ----------------
 _vp, _int, _dbl, _P = C.c_void_p, C.c_int, C.c_double, C.POINTER
 _OUT = _P(CagymOutputs)
@@ -132,6 +142,10 @@ _ARGTYPES = {
     "cagym_episode_records_update": [_vp, _vp, _vp, _vp, _int, _vp],
     "cagym_episode_records_restart": [_vp, _vp, _int, _vp],
     "cagym_episode_records_get": [_vp, _P(CagymEpisodeRecordPtrs)],
+    "cagym_snapshot_layout_of": [_vp, _P(CagymSnapshotLayout)],
+    "cagym_snapshot": [_vp, _vp, _int, _vp, _vp],
+    "cagym_restore": [_vp, _P(CagymSnapshotLayout), _vp, _vp, _int, _vp],
+    "cagym_fork": [_vp, _vp, _vp, _int, _vp],
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],

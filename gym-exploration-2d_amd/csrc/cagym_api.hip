@@ -27,6 +27,7 @@
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
 #include "cagym_episode_records.h"
+#include "cagym_snapshot.h"
 
 namespace {
 
@@ -263,6 +264,76 @@ inline int eprec_restart(Env* e, const uint8_t* world_mask, bool clear_table, hi
     const size_t rows = (size_t)std::max(e->cfg.n_worlds, clear_table ? e->cfg.n_scenarios : 0) * e->cfg.max_agents;
     const unsigned grid = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
     hipLaunchKernelGGL(k_episode_records_restart, dim3(grid), dim3(256), 0, st, e->D, e->rec, world_mask, clear_table ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- the field tables of csrc/cagym_snapshot.h ----------------------------------------------------------------------------------------
+// A blob row: the header, then every per-world field alloc_state allocates except lp_vel (the split step's hand-over: restore and
+// fork void a pending begin), each at the next multiple of 16; after cagym_ig_init also the belief, its MI cache and the team
+// reward's accumulators.  fork_only: the table of cagym_fork's world -> world copy, which leaves dst its episode index and stat_*.
+inline SnapTable snap_state_table(const Env* e, int mode, bool fork_only = false) {
+    const CagymDev& D = e->D;
+    const uint32_t M = (uint32_t)e->cfg.max_agents;
+    SnapTable T{};
+    T.mode = mode; T.N = e->cfg.n_worlds; T.S = e->cfg.n_scenarios; T.episode = D.episode;
+    uint64_t off = SNAP_HEADER_BYTES;
+    auto add = [&](void* base, size_t bytes, bool in_fork = true) {
+        if (fork_only && !in_fork) return;  // (no blob in a fork: the fields it copies are packed without the gaps)
+        T.f[T.n_fields++] = {reinterpret_cast<unsigned char*>(base), (uint32_t)bytes, (uint32_t)off};
+        off += (bytes + 15) & ~(size_t)15;
+    };
+    double* const f64[] = {D.px, D.py, D.vx, D.vy, D.heading, D.heading_ego, D.dist_goal, D.time_rem, D.t,
+                           D.gx, D.gy, D.radius, D.pref, D.speed, D.dhead, D.aux0, D.aux1, D.coop};
+    for (double* p : f64) add(p, M * sizeof(double));
+    add(D.action, M * 2 * sizeof(float)); add(D.status, M * sizeof(uint32_t)); add(D.step_num, M * sizeof(int32_t));
+    add(D.n_observed, M * sizeof(int32_t));
+    add(D.n_agents, sizeof(int32_t)); add(D.episode, sizeof(int32_t), false); add(D.ep_len, sizeof(int32_t)); add(D.ep_return, sizeof(float));
+    add(D.stat_return, sizeof(float), false); add(D.stat_episodes, sizeof(int32_t), false); add(D.stat_steps, sizeof(int32_t), false);
+    add(D.stat_outcomes, 3 * sizeof(int32_t), false);
+    if (e->ig_ready) {
+        add(e->G.belief, (size_t)IG_BEL * IG_BEL * sizeof(double)); add(e->G.mi, (size_t)IG_BEL * IG_BEL * sizeof(double));
+        add(e->ig_ep.running, sizeof(double)); add(e->ig_ep.sum, sizeof(double)); add(e->ig_ep.last, sizeof(double));
+        add(e->ig_ep.episodes, sizeof(int32_t));
+    }
+    T.row_bytes = off;
+    return T;
+}
+static_assert(18 + 4 + 8 + 6 <= SNAP_MAX_FIELDS, "SnapTable holds every field of a row");
+
+// the pool rows of one scenario slot (cagym_fork copies src's current slot over dst's)
+inline SnapTable snap_pool_table(const Env* e) {
+    const CagymDev& D = e->D;
+    const size_t M = (size_t)e->cfg.max_agents, K = (size_t)e->cfg.max_obstacles;
+    SnapTable T{};
+    T.mode = SNAP_POOL; T.N = e->cfg.n_worlds; T.S = e->cfg.n_scenarios; T.episode = D.episode;
+    uint64_t off = SNAP_HEADER_BYTES;  // no blob here: the offsets only spread the lanes over the fields
+    auto add = [&](const void* base, size_t bytes) {
+        T.f[T.n_fields++] = {reinterpret_cast<unsigned char*>(const_cast<void*>(base)), (uint32_t)bytes, (uint32_t)off};
+        off += (bytes + 15) & ~(size_t)15;
+    };
+    add(D.sc_agents6, M * 6 * sizeof(double)); add(e->sc_heading_buf, M * sizeof(double)); add(D.sc_coop, M * sizeof(double));
+    add(D.sc_policy, M * sizeof(int32_t)); add(D.sc_dyn, M * sizeof(int32_t)); add(D.sc_nagents, sizeof(int32_t)); add(D.sc_nobst, sizeof(int32_t));
+    if (has_map(e)) {
+        add(D.map_bits, (size_t)CAGYM_MAPD * CAGYM_MAPW * sizeof(uint32_t)); add(e->sc_obst, K * 4 * sizeof(double));
+        add(e->sc_obst_prep, K * 4 * sizeof(float4));
+    }
+    T.row_bytes = off;
+    return T;
+}
+
+inline cagym_snapshot_layout snap_layout(const Env* e) {
+    cagym_snapshot_layout L{};
+    L.magic = CAGYM_SNAP_MAGIC; L.version = CAGYM_SNAP_VERSION;
+    L.n_worlds = e->cfg.n_worlds; L.max_agents = e->cfg.max_agents; L.n_scenarios = e->cfg.n_scenarios; L.max_obstacles = e->cfg.max_obstacles;
+    L.fields = CAGYM_SNAP_CORE | (e->ig_ready ? CAGYM_SNAP_IG : 0u);
+    L.row_bytes = snap_state_table(e, SNAP_GATHER).row_bytes;
+    return L;
+}
+
+inline int snap_launch(Env* e, const SnapTable& T, const int32_t* ids, const int32_t* ids2, void* blob, int n, hipStream_t st) {
+    if (n == 0) return CAGYM_OK;
+    hipLaunchKernelGGL(k_snapshot_copy, dim3((unsigned)n), dim3(SNAP_NT), 0, st, T, ids, ids2, reinterpret_cast<unsigned char*>(blob));
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
@@ -1390,6 +1461,63 @@ int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out) {
     out->count = R.count; out->t_run = R.t_run; out->ret_run = R.ret_run; out->steps_run = R.steps_run; out->atgoal_run = R.atgoal_run;
     out->cursor = R.cursor; out->desync = R.desync;
     return CAGYM_OK;
+}
+
+// ---- per-world snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------------
+int cagym_snapshot_layout_of(void* env, cagym_snapshot_layout* out) {
+    ENTRY(e, env);
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    *out = snap_layout(e);
+    return CAGYM_OK;
+}
+
+// the argument checks the three calls share
+static int snap_check_blob(Env* e, const char* what, const void* blob, int n) {
+    if (n < 0 || n > e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, std::string(what) + ": n must be in [0, n_worlds]");
+    if (!blob || (reinterpret_cast<uintptr_t>(blob) & 15)) return fail(e, CAGYM_E_INVALID, std::string(what) + ": the blob must be a 16-byte aligned device buffer");
+    return CAGYM_OK;
+}
+
+int cagym_snapshot(void* env, const int32_t* worlds, int n, void* blob, void* stream) {
+    ENTRY_POOL(e, env, "cagym_snapshot");
+    if (int rc = snap_check_blob(e, "cagym_snapshot", blob, n)) return rc;
+    if (!worlds && n != e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, "cagym_snapshot: NULL worlds means every world, n must be n_worlds");
+    ON_DEVICE(e);  // a pending cagym_step_begin stays valid: nothing moves
+    return snap_launch(e, snap_state_table(e, SNAP_GATHER), worlds, nullptr, blob, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* blob, const int32_t* rows, int n, void* stream) {
+    ENTRY_POOL(e, env, "cagym_restore");
+    if (int rc = snap_check_blob(e, "cagym_restore", blob, n)) return rc;
+    if (!layout) return fail(e, CAGYM_E_INVALID, "cagym_restore: null layout");
+    const cagym_snapshot_layout own = snap_layout(e);
+    if (layout->magic != own.magic || layout->version != own.version || layout->n_worlds != own.n_worlds || layout->max_agents != own.max_agents ||
+        layout->n_scenarios != own.n_scenarios || layout->max_obstacles != own.max_obstacles || layout->fields != own.fields ||
+        layout->reserved != own.reserved || layout->row_bytes != own.row_bytes)
+        return fail(e, CAGYM_E_INVALID, "cagym_restore: the blob's layout is not this handle's (n_worlds, max_agents, n_scenarios, max_obstacles, "
+                                        "cagym_ig_init done or not, magic and version must all match)");
+    if (e->rec_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_restore with episode records initialised: their running rows would describe another timeline; "
+                                      "detach the records first");
+    ON_DEVICE_VOIDS_BEGUN(e);
+    return snap_launch(e, snap_state_table(e, SNAP_SCATTER), rows, nullptr, const_cast<void*>(blob), n, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* stream) {
+    ENTRY_POOL(e, env, "cagym_fork");
+    if (n < 0 || n > e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, "cagym_fork: n must be in [0, n_worlds]");
+    if (n > 0 && (!src || !dst)) return fail(e, CAGYM_E_INVALID, "cagym_fork: null src / dst");
+    if (e->rec_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_fork with episode records initialised: their running rows would describe another timeline; "
+                                      "detach the records first");
+    if (e->cfg.n_scenarios % e->cfg.n_worlds != 0)
+        return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork needs n_scenarios to be a multiple of n_worlds: otherwise two worlds can share a scenario "
+                                            "slot and the copy of src's slot over dst's could hit a third world");
+    if (e->ig_ready) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork after cagym_ig_init: the per-slot distance field is not copied");
+    ON_DEVICE_VOIDS_BEGUN(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = snap_launch(e, snap_state_table(e, SNAP_FORK, true), src, dst, nullptr, n, st)) return rc;
+    return snap_launch(e, snap_pool_table(e), src, dst, nullptr, n, st);
 }
 
 }  // extern "C"

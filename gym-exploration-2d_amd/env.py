@@ -332,6 +332,7 @@ class CollisionAvoidanceEnv(object):
         return "agent0" if Config.TRAIN_SINGLE_AGENT else "learning"
 
     def _snapshot(self):
+        # (a host cache of the state views for the Agent properties; unrelated to BatchedCollisionAvoidanceEnv.snapshot())
         if self._snap is None:
             import torch
             torch.cuda.synchronize()

@@ -519,6 +519,57 @@ int cagym_episode_records_update(void* env, const uint8_t* flags, const float* r
 int cagym_episode_records_restart(void* env, const uint8_t* world_mask, int clear_table, void* stream);
 int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out);
 
+/* ---- Per-world state snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------
+ * The env can be put back where it was (checkpoint / resume, rewind) and a world can continue as a copy of another one (look-ahead:
+ * "try these K actions from this state").  One copy kernel beside the step kernels; no step, reset or roll-out kernel knows of it.
+ * A blob is [n, row_bytes] caller-owned DEVICE bytes, 16-byte aligned.  A row holds everything the handle keeps per world except
+ * the split step's hand-over: a 16-byte header {origin world id, CAGYM_SNAP_MAGIC, 0, 0}, then (CAGYM_SNAP_CORE) the 18 fp64
+ * per-agent arrays (the cagym_state_ptrs ones and coop), action, status, step_num, n_observed, and per world n_agents, episode,
+ * the running episode length and return, stat_return, stat_episodes, stat_steps, stat_outcomes; after cagym_ig_init also
+ * (CAGYM_SNAP_IG) the world's belief grid, its MI cache and the four cagym_ig_get_episode_stats accumulators.  Every field starts at
+ * a multiple of 16 inside the row and row_bytes is a multiple of 16.  The scenario pool is NOT part of a blob: a world's scenario is
+ * computed, (world + episode * N) % S, so putting `episode` back puts the scenario back - into the pool the handle holds THEN
+ * (resume in a fresh handle: install the same pool first).  The caller's output buffers are not part of it either.
+ * cagym_snapshot_layout_of: the handle's layout (host only, no launch).  It changes when cagym_ig_init runs.
+ * cagym_snapshot: row r of the blob <- world worlds[r] (DEVICE [n] i32; NULL: worlds 0..N-1, and n must be N).
+ * cagym_restore: blob row rows[r] (DEVICE [n] i32; NULL: rows 0..n-1) -> the origin world its header names; there is no destination
+ *   argument.  `layout` is the one the blob was taken with; it must equal the handle's own in every field (same N, M, S,
+ *   max_obstacles, IG-ness), which lets a blob restore into a fresh handle of the same shape.
+ * cagym_fork: world dst[r] continues as a copy of world src[r] (DEVICE [n] i32 each): every field of a row except dst's own episode
+ *   index and stat_* (the running episode length and return ARE copied), and the pool rows of src's current scenario slot over
+ *   dst's current slot (start / goal / speed / radius rows, the heading buffer whether or not headings are in use, coop, policy,
+ *   dynamics, n_agents, n_obst and, with rectangles, the raster, the rectangles and their prepared form) - so dst steps against
+ *   src's rectangles and a later cagym_reset of dst re-initialises it from the forked scenario.  No kernel needs an indirection.
+ * All work is enqueued on `stream`; no call allocates or synchronises the host, so all three can be captured in a graph.
+ * cagym_restore and cagym_fork void a pending cagym_step_begin; cagym_snapshot does not.
+ * Every id read from a list, and the origin id of a blob row, is checked on the device: an id outside [0, N) (or a row without
+ * the magic) makes that row's workgroup return without touching memory.
+ * PRECONDITIONS the library cannot check without reading device memory: the dst ids of one cagym_fork are distinct and none is
+ * also a src of the same call; the rows of one cagym_restore name distinct origin worlds and are smaller than the number of rows the
+ * blob holds.  Violating the first three gives an unspecified mix of the candidates, never a fault; a row id in [n of the blob, N)
+ * reads past the caller's blob (the library does not know its size; BatchedCollisionAvoidanceEnv.restore masks such ids).
+ * Errors, in this order: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before cagym_set_scenarios; CAGYM_E_INVALID for n < 0 or
+ * n > N, a NULL blob or one that is not 16-byte aligned, NULL worlds with n != N, NULL src / dst with n > 0, a NULL layout or one
+ * that differs from the handle's own in any field; CAGYM_E_STATE for restore / fork while episode records are initialised (their
+ * running rows would describe another timeline: detach the records first); CAGYM_E_UNSUPPORTED for fork on a handle whose
+ * n_scenarios is not a multiple of n_worlds (two worlds can share a slot, the overwrite could hit a third) or after cagym_ig_init
+ * (the per-slot distance field is not copied); CAGYM_E_DEVICE as every launching entry. */
+#define CAGYM_SNAP_MAGIC 0x43475331u /* "CGS1" */
+#define CAGYM_SNAP_VERSION 1
+enum { CAGYM_SNAP_CORE = 1, CAGYM_SNAP_IG = 2 };
+struct cagym_snapshot_layout {
+    uint32_t magic, version;
+    int32_t n_worlds, max_agents, n_scenarios, max_obstacles;
+    uint32_t fields;    /* CAGYM_SNAP_CORE | CAGYM_SNAP_IG */
+    uint32_t reserved;  /* 0 */
+    uint64_t row_bytes;
+};
+typedef struct cagym_snapshot_layout cagym_snapshot_layout;
+int cagym_snapshot_layout_of(void* env, cagym_snapshot_layout* out);
+int cagym_snapshot(void* env, const int32_t* worlds, int n, void* blob, void* stream);
+int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* blob, const int32_t* rows, int n, void* stream);
+int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
