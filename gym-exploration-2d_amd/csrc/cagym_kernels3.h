@@ -15,6 +15,10 @@
 //             pair lane also ranks its two half-planes into nearest-first order (the LP groups start from sorted lines)
 //   (rare)    a world was reset in S2: keys, distances, preferred velocities and half-planes are rebuilt in two extra phases
 //
+// The step's top holds nothing but the busy list: each output slice is computed by its consumer (the row workers take the observation
+// pointers of step t-1, S2 indexes reward / flags / game_over of step t) and the issue priority of step t+1 (W.flag[4]) is read
+// behind barrier B together with the restart flag.
+//
 // Wave 0 waits for the other LP waves on an LDS counter (release/acquire at workgroup scope), not on a barrier, so the
 // row workers never stop between C and D.  Arithmetic is shared with generation 1 (cagym_gen1.h) through cagym_device.h and cagym_orca.h:
 // both produce bit-identical results (tests/test_hip_parity.py); generation 2 (phase-split, one barrier-separated phase after
@@ -1008,6 +1012,15 @@ __device__ __forceinline__ void observation_chunks3(const CagymDev& D, const Lds
     if (OBST && o.laserscan) laser_scan3<BATCH>(D, W, o.laserscan, M, wpw, AS, inv_m, ko);
 }
 
+// the observation pointers of step t alone (what the row workers of a roll-out write; the S2 outputs are indexed in S2)
+__device__ __forceinline__ CagymOut out_rows_slice3(const CagymOut& out, int t, size_t NM, int M) {
+    CagymOut o;
+    o.obs_oas = out.obs_oas ? out.obs_oas + (size_t)t * NM * (M - 1) * 10 : nullptr;
+    o.obs_ego = out.obs_ego ? out.obs_ego + (size_t)t * NM * CAGYM_EGO_WIDTH : nullptr;
+    o.laserscan = out.laserscan ? out.laserscan + (size_t)t * NM * 16 : nullptr;
+    o.reward = nullptr; o.flags = nullptr; o.game_over = nullptr;
+    return o;
+}
 __device__ __forceinline__ CagymOut out_slice3(const CagymOut& out, int t, size_t N, size_t NM, int M) {
     CagymOut o;
     o.obs_oas = out.obs_oas ? out.obs_oas + (size_t)t * NM * (M - 1) * 10 : nullptr;
@@ -1117,6 +1130,7 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         __syncthreads();
     }
     WGTRACE(1);
+    bool lagging = false;  // some ego needed linearProgram3 in the previous step (W.flag[4]; 0 behind the prologue)
 #pragma nounroll
     for (int t = 0; t < n_steps; t++) {
         int tid = threadIdx.x;
@@ -1130,9 +1144,9 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         int aidx32 = C.world * M + C.slot;
         asm volatile("" : "+v"(aidx32));
         const size_t aidx = (size_t)(unsigned)aidx32;
-        const CagymOut o_prev = out_slice3(out, t > 0 ? t - 1 : 0, (size_t)D.N, NM, M);  // rows of step t-1 (used when t > 0)
-        const CagymOut o = out_slice3(out, t, (size_t)D.N, NM, M);
-        const bool lagging = __builtin_amdgcn_readfirstlane(W.flag[4]) != 0;  // some ego needed linearProgram3 in the previous step
+        // (the output slices of the step are computed where they are consumed - the rows' by the row workers, S2's in S2 - and
+        // `lagging` came with the previous step's last LDS read: nothing but the busy list stands between the loop head and wave 0's
+        // first linear program)
         prio_chain3(lagging);
         WAVETRACE(t, 0);
         PMARK("C_begin");
@@ -1264,11 +1278,14 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         } else if (t > 0) {
             prio_rows3();
             PMARK("D_rows_begin");
+            const CagymOut o_prev = out_rows_slice3(out, t - 1, NM, M);  // rows of step t-1
             observation_chunks3<OBST, (ONE ? 8 : CAGYM_LASER_BATCH_ROLLOUT)>(D, W, o_prev, npairs, M, MP, K, C.wpw, C.worlds_valid, inv_m, ko, AS);
             prio_chain3(lagging);
             WAVETRACE(t, 4);
         }
         PMARK("D_end_barrierX");
+        // (the other waves are long here when wave 0 arrives: the barrier releases it at once.  An arrival count that only wave 0 waits
+        // for is slower - DESIGN.md section 4, "measured, not kept")
         __syncthreads();  // rows of step t-1 are out: the moved state may replace the old one
         WGTRACE1(25);
         WAVETRACE(t, 5);
@@ -1366,10 +1383,12 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
                 else if (D.go_mode == CAGYM_GO_LEARNING) go = (b_learn & wm) == wm;
                 else go = C.n > 0 ? ((b_done >> C.base) & 1ull) : true;
                 if (C.valid) {
-                    if (o.reward) o.reward[aidx] = reward;
-                    if (o.flags) o.flags[aidx] = (uint8_t)(S.st & 0xffu);
+                    // the step's slice of the three S2 outputs (t * N * M < 2^31: cagym_create bounds the trajectory's rows)
+                    const size_t ot = (size_t)t * NM;
+                    if (out.reward) out.reward[ot + aidx] = reward;
+                    if (out.flags) out.flags[ot + aidx] = (uint8_t)(S.st & 0xffu);
                     if (C.slot == 0) {
-                        if (o.game_over) o.game_over[C.world] = go ? 1 : 0;
+                        if (out.game_over) out.game_over[(size_t)t * (size_t)D.N + C.world] = go ? 1 : 0;
                         ep_ret += reward;
                         ep_len += 1;
                     }
@@ -1427,12 +1446,12 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
             PMARK("B_hp_begin");
             for (int p = tid - CAGYM_WAVE; p < lim; p += NT - CAGYM_WAVE) half_planes3<MT>(D, W, p, M, MP, AS, ko);
         }
-        if (OBST && ONE && o.laserscan) {
+        if (OBST && ONE && out.laserscan) {  // (ONE: t == 0, the outputs are not sliced)
             // the one-step launch (every step of the VecEnv path; the roll-out kernels sit at their register limit and keep the scan
             // of their last step in the epilogue): no half-planes to build, waves 1.. would idle beside S2.  The
             // LaserScan only reads what S1 published (pose, radius, the world's rectangles), so it runs here - it was the longest part
             // of the epilogue (wave 0 joins behind S2); a world restarted by S2 is scanned again in the epilogue (W.flag[0]).
-            laser_scan3<8>(D, W, o.laserscan, M, C.wpw, AS, inv_m, ko);
+            laser_scan3<8>(D, W, out.laserscan, M, C.wpw, AS, inv_m, ko);
         }
         PMARK("B_end");
         WAVETRACE(t, 10);
@@ -1442,7 +1461,11 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         WAVETRACE(t, 11);
         PMARK("R_begin");
         // ---- rare: a world restarted on its next scenario -> everything derived from the old episode is rebuilt -------------
-        if (AUTO_RESET && W.flag[0]) {
+        // W.flag[0] (a world restarted) and W.flag[4] (the next step's `lagging`, set between barriers X and Y): two LDS reads issued
+        // back to back under one wait, so that the next step's top has none
+        const int f_reset = W.flag[0], f_lag = W.flag[4];
+        lagging = __builtin_amdgcn_readfirstlane(f_lag) != 0;
+        if (AUTO_RESET && f_reset) {
             if (OBST && tid == 0) { W.flag[7] = 0; W.flag[8] = 0; W.flag[9] = 0; W.flag[10] = 0; }  // the epilogue scans again (barriers below)
             if (OBST && ko > 0) {  // the restarted worlds' rectangles (also behind the last step: the epilogue's scan uses them)
                 stage_rects3(D, W, C.wpw, C.worlds_valid);
