@@ -91,6 +91,11 @@ class CagymSnapshotLayout(C.Structure):
                 ("row_bytes", C.c_uint64)]
 
 
+class CagymStreamPtrs(C.Structure):
+    """cagym_stream_ptrs (include/cagym.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("next_episode", "generated", "n_failed", "n_lapped")]
+
+
 # ---- the prototypes of include/cagym.h: name -> argtypes; every function returns int except those of _RESTYPES ----------------
 _vp, _int, _dbl, _P = C.c_void_p, C.c_int, C.c_double, C.POINTER
 _OUT = _P(CagymOutputs)
@@ -146,6 +151,11 @@ _ARGTYPES = {
     "cagym_snapshot": [_vp, _vp, _int, _vp, _vp],
     "cagym_restore": [_vp, _P(CagymSnapshotLayout), _vp, _vp, _int, _vp],
     "cagym_fork": [_vp, _vp, _vp, _int, _vp],
+    "cagym_stream_scenarios": [_vp, _P(CagymGen2Params), _P(C.c_int32), _vp],
+    "cagym_stream_refill": [_vp, _vp],
+    "cagym_stream_set_params": [_vp, _P(CagymGen2Params)],
+    "cagym_stream_get": [_vp, _P(CagymStreamPtrs)],
+    "cagym_stream_stop": [_vp],
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],

@@ -94,6 +94,7 @@ class BatchedCollisionAvoidanceEnv(object):
         # the calls inside per-step loops, resolved once
         self._step_fn = (self.L.cagym_step, self.L.cagym_step_autoreset)
         self._rollout_fn, self._records_fn = self.L.cagym_rollout, self.L.cagym_episode_records_update
+        self._refill_fn = self.L.cagym_stream_refill
         N, M, K = self.N, self.M, self.K
         dev = self.device
         self.obs_oas = torch.zeros((N, M, K, 10), dtype=torch.float32, device=dev)
@@ -115,6 +116,8 @@ class BatchedCollisionAvoidanceEnv(object):
         self._rec = None          # keep mode of attach_episode_records, None while detached
         self._rec_views = None
         self._rec_priv = {}       # rollout buffers of a caller whose `out` lacks reward / flags / game_over
+        self._streaming = False   # stream_reference_scenarios: one cagym_stream_refill behind every episode-advancing call
+        self._stream_views = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
@@ -171,6 +174,7 @@ class BatchedCollisionAvoidanceEnv(object):
             no = np.ascontiguousarray(np.asarray(n_obst, dtype=np.int32).reshape(S))
         p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
         _lib.call(self.L, self.h, "cagym_set_scenarios", p(a6), p(h0), p(pol), p(dyn), p(na), p(co), p(ob), p(no), self._stream())
+        self._streaming = False  # as the library: a new pool ends the stream
         live = np.arange(M)[None, :] < (na if na is not None else np.full(S, M))[:, None]
         self._pool_policies = set(np.unique(pol[live]).tolist())
         counts = ((pol == sc.POLICY_IGMCTS) & live).sum(axis=1)
@@ -204,6 +208,7 @@ class BatchedCollisionAvoidanceEnv(object):
                                 float(pref_speed), float(coop))
         nf = C.c_int32(0)
         _lib.call(self.L, self.h, "cagym_generate_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
+        self._streaming = False
         self._pool_policies = {int(ego_policy), int(other_policies[0]), int(other_policies[1])}
         self._n_ig = None
         self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
@@ -224,6 +229,19 @@ class BatchedCollisionAvoidanceEnv(object):
         and a world that leaves no room for an agent (ten agents among ten stage-2 rectangles can) spins its lane to the bound -
         1000 keeps a pool of 8192 stage-2 worlds near 10 ms, 100000 takes about 0.3 s.  Returns the number of agents and
         rectangles whose rejection loop hit max_tries (they keep their last draw) when check=True."""
+        P, pols = self._gen2_params(kinds, seed, number_of_agents, fixed_count, ego_policy, ego_dynamics, other_policies, p_b,
+                                    other_dynamics, n_obst, max_tries)
+        nf = C.c_int32(0)
+        _lib.call(self.L, self.h, "cagym_generate_reference_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
+        self._streaming = False
+        self._pool_policies = pols
+        self._n_ig = None
+        self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
+        return int(nf.value) if check else None
+
+    def _gen2_params(self, kinds, seed, number_of_agents, fixed_count, ego_policy, ego_dynamics, other_policies, p_b,
+                     other_dynamics, n_obst, max_tries):
+        """generate_reference_scenarios' arguments as (cagym_gen2_params, the policies the scenarios may hold)."""
         ks = [kinds] if isinstance(kinds, (str, int, np.integer)) else list(kinds)
         mask = 0
         for k in ks:
@@ -242,8 +260,6 @@ class BatchedCollisionAvoidanceEnv(object):
         lo, hi = (-1, -1) if n_obst is None else (n_obst, n_obst) if np.isscalar(n_obst) else n_obst
         P = _lib.CagymGen2Params(int(seed), mask, int(number_of_agents), int(bool(fixed_count)), int(ego_policy),
                                  int(ego_dynamics), int(own), pa, pb, int(other_dynamics), int(lo), int(hi), int(max_tries), pp)
-        nf = C.c_int32(0)
-        _lib.call(self.L, self.h, "cagym_generate_reference_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
         # the policies the pool may hold
         pols = {int(ego_policy)}
         for k in {sc.sampler_kind(k) for k in ks}:
@@ -252,10 +268,69 @@ class BatchedCollisionAvoidanceEnv(object):
                 pols |= {pb} if pp > 0.0 else set()
             else:
                 pols |= {sc.POLICY_RVO} if k >= sc.GEN_STAGE_1 else {sc.POLICY_RVO, sc.POLICY_NONCOOP}
+        return P, pols
+
+    # ---- streamed scenarios (include/cagym.h: cagym_stream_*) -------------------------------------------------------------------
+    def stream_reference_scenarios(self, kinds, seed, number_of_agents=None, fixed_count=False, ego_policy=5, ego_dynamics=4,
+                                   other_policies=None, p_b=None, other_dynamics=0, n_obst=None, max_tries=1000, check=True):
+        """generate_reference_scenarios (same arguments, same pool), and from now on the pool is a ring of depth
+        k = n_scenarios / n_worlds per world that is refilled behind the stepping calls: world w's episode e runs on the scenario
+        the samplers draw for key w + e * N - row w + e * N of a plain pool generated with the same arguments, however large e
+        gets - instead of replaying the pool after k episodes (the reference draws a fresh world at every reset()).  One
+        cagym_stream_refill launch is enqueued on the current stream behind every call that can advance an episode counter:
+        step / step_finish / step_overlapped with auto_reset=True, rollout(auto_reset=True) (once, behind its last step) and
+        reset(advance_episode=True); CagymVecEnv inherits it through step().  A world that finished nothing costs the launch two
+        loads.  Needs n_scenarios to be a multiple of n_worlds and >= 2 * n_worlds; refused on handles with information-gain
+        state, for IG_MCTS agents and while episode records are attached.  While streaming, restore(), fork() and
+        attach_episode_records() raise.  set_scenarios / generate_* / stop_streaming() end it.  Returns n_failed as
+        generate_reference_scenarios does when check=True."""
+        P, pols = self._gen2_params(kinds, seed, number_of_agents, fixed_count, ego_policy, ego_dynamics, other_policies, p_b,
+                                    other_dynamics, n_obst, max_tries)
+        nf = C.c_int32(0)
+        _lib.call(self.L, self.h, "cagym_stream_scenarios", C.byref(P), C.byref(nf) if check else None, self._stream())
+        self._streaming = True
         self._pool_policies = pols
         self._n_ig = None
-        self.detach_ig_mcts()  # the generated pool's robot count is not known on the host
+        self.detach_ig_mcts()
         return int(nf.value) if check else None
+
+    def set_stream_params(self, kinds, seed, number_of_agents=None, fixed_count=False, ego_policy=5, ego_dynamics=4,
+                          other_policies=None, p_b=None, other_dynamics=0, n_obst=None, max_tries=1000):
+        """The reference's curriculum switch (collision_avoidance_env.py:419-438) on a streaming env: the slots that later refills
+        generate come from this sampler set (scenarios.reference_curriculum gives the set of a training step); the seed may change
+        too.  Scenarios already in the ring stay, so a world meets the new set n_scenarios / n_worlds - 1 episodes later."""
+        P, pols = self._gen2_params(kinds, seed, number_of_agents, fixed_count, ego_policy, ego_dynamics, other_policies, p_b,
+                                    other_dynamics, n_obst, max_tries)
+        _lib.call(self.L, self.h, "cagym_stream_set_params", C.byref(P))
+        self._pool_policies = self._pool_policies | pols
+
+    def stop_streaming(self):
+        """End the stream: the pool stays as it is and is replayed from here on, as a fixed pool is."""
+        _lib.call(self.L, self.h, "cagym_stream_stop")
+        self._streaming = False
+
+    def stream_stats(self):
+        """Host integers of the stream (this synchronises): generated (slots generated since stream_reference_scenarios, its first
+        fill included), n_failed (rejection loops that hit max_tries), n_lapped (times a world started an episode on a slot that
+        had not been refilled: only a rollout in which a world finishes more than depth - 1 episodes does that), depth."""
+        if self._stream_views is None:
+            sp = _lib.CagymStreamPtrs()
+            _lib.call(self.L, self.h, "cagym_stream_get", C.byref(sp))
+            spec = {"next_episode": ((self.N,), "i4"), "generated": ((1,), "i8"), "n_failed": ((1,), "i4"), "n_lapped": ((1,), "i4")}
+            self._stream_views = {k: torch.as_tensor(_DevArray(getattr(sp, k), shp, ts), device=self.device) for k, (shp, ts) in spec.items()}
+        v = self._stream_views
+        return {"generated": int(v["generated"].item()), "n_failed": int(v["n_failed"].item()), "n_lapped": int(v["n_lapped"].item()),
+                "depth": self.S // self.N}
+
+    def stream_next_episode(self):
+        """Zero-copy device view of next_episode [N] i32: the first episode of each world whose slot has not been generated."""
+        self.stream_stats()
+        return self._stream_views["next_episode"]
+
+    def _refill(self):
+        rc = self._refill_fn(self.h, self._stream())
+        if rc:
+            _lib.check(self.L, self.h, rc, "cagym_stream_refill")
 
     def obstacles(self):
         """Zero-copy device views of the pool's rectangles: obstacles [S, max_obstacles, 4] (xl, yl, xu, yu), n_obst [S]."""
@@ -286,6 +361,8 @@ class BatchedCollisionAvoidanceEnv(object):
     def reset(self, world_mask=None, advance_episode=False):
         m = self._mask(world_mask)
         _lib.call(self.L, self.h, "cagym_reset", _lib.ptr(m), int(bool(advance_episode)), C.byref(self._out), self._stream())
+        if self._streaming and advance_episode:
+            self._refill()
         g = self._igm
         if g is not None and g.episodic and m is not None:
             # a manual restart of the masked worlds only: prior belief, no communicated plans, running team return zeroed; it is
@@ -428,6 +505,8 @@ class BatchedCollisionAvoidanceEnv(object):
                                "without auto-reset and reset() yourself" % (k, k))
         self._records_contract(auto_reset, "step")
         self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None)
+        if self._streaming and auto_reset:
+            self._refill()
         if self._rec is not None:
             self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
@@ -445,6 +524,7 @@ class BatchedCollisionAvoidanceEnv(object):
         rollout(auto_reset=False) are refused while attached.  Attaching again clears the table.  Needs a scenario pool."""
         if keep not in _lib.EPREC_KEEP:
             raise ValueError("attach_episode_records: keep must be 'first' or 'last', got %r" % (keep,))
+        self._refuse_streaming("attach_episode_records", "the records table has one row per pool slot, and a streamed pool reuses its slots")
         _lib.call(self.L, self.h, "cagym_episode_records_init", _lib.EPREC_KEEP[keep], self._stream())
         self._rec = keep
         return self
@@ -530,6 +610,8 @@ class BatchedCollisionAvoidanceEnv(object):
         self._records_contract(auto_reset, "step_finish")
         a = self._actions(actions)
         _lib.call(self.L, self.h, "cagym_step_finish", _lib.ptr(a), C.byref(self._out), int(bool(auto_reset)), self._stream())
+        if self._streaming and auto_reset:
+            self._refill()
         if self._rec is not None:
             self._records_update(self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
@@ -569,7 +651,11 @@ class BatchedCollisionAvoidanceEnv(object):
         GA3C agents in the pool: T x (cagym_ga3c_act_merge, step), each step writing slice t of the buffers - no host
         synchronisation, so the chain can be captured in a graph.  With an episodic attach_ig_mcts: T x (robot inputs, belief
         update, team reward into out["team_reward"][t], plan, robot actions, step, episode boundary), no host synchronisation
-        either; not under stream capture (the planner's call_base is a kernel argument the host advances per call)."""
+        either; not under stream capture (the planner's call_base is a kernel argument the host advances per call).
+        On a streaming env (stream_reference_scenarios) the ring is refilled ONCE, behind the last step: a world may finish at
+        most n_scenarios / n_worlds - 1 episodes per launch.  A world that finishes more starts an episode on a slot that was not
+        refilled (it replays an older scenario); nothing faults, and stream_stats()["n_lapped"] counts it - that is how a caller
+        finds out, and the remedy is a shorter rollout or a deeper ring."""
         self._records_contract(auto_reset, "rollout")
         T, g = int(n_steps), self._igm
         if g is not None and not g.episodic:
@@ -607,6 +693,8 @@ class BatchedCollisionAvoidanceEnv(object):
                 self._chained_step(None, o, auto_reset, restart, team_reward, prev)
             if oas is not None and T > 0:
                 self.obs_oas.copy_(oas[T - 1])
+        if self._streaming and auto_reset:  # one refill behind the last step, whichever chain ran
+            self._refill()
         if self._rec is not None:  # one launch behind the last step, over all T slices
             self._records_update(out["flags"], out["reward"], out["game_over"], T)
         return caller_out
@@ -690,6 +778,10 @@ class BatchedCollisionAvoidanceEnv(object):
         pick = ids.long() if host is not None else ids.long().clamp(0, self.N - 1)
         return EnvSnapshot(L, blob, ids, {k: v.index_select(0, pick) for k, v in self._outs().items()}, False, host is not None)
 
+    def _refuse_streaming(self, what, why):
+        if self._streaming:
+            raise RuntimeError("%s() on a streaming env: %s; stop_streaming() first" % (what, why))
+
     def _refuse_with_planner(self, what):
         if self._igm is not None:
             raise RuntimeError("%s() with %s attached: the planner's workspace, its published plans and the host-side call counter are "
@@ -699,8 +791,11 @@ class BatchedCollisionAvoidanceEnv(object):
         """Put the rows of an EnvSnapshot (default: all; else distinct row indices into it) back, each into its origin world:
         ONE cagym_restore launch, then the same worlds' output rows.  A pending step_begin is void afterwards.  The snapshot
         may come from another handle of the same shape (resume): install the same scenario pool first.  Refused while an
-        ig_mcts / ig_greedy planner is attached, and by the library while episode records are initialised."""
+        ig_mcts / ig_greedy planner is attached, while the env streams scenarios, and by the library while episode records are
+        initialised."""
         self._refuse_with_planner("restore")
+        self._refuse_streaming("restore", "the ring of scenario slots is not part of a snapshot (a restored episode index would meet "
+                               "other scenarios)")
         valid = None
         if rows is None and snap.all_worlds:  # whole tensors, and nothing allocated: the form a graph capture takes
             _lib.call(self.L, self.h, "cagym_restore", C.byref(snap.layout), snap.blob.data_ptr(), None, snap.n, self._stream())
@@ -729,9 +824,11 @@ class BatchedCollisionAvoidanceEnv(object):
     def fork(self, src, dst, check=True):
         """World dst[r] continues as a copy of world src[r]: cagym_fork (state rows except dst's own episode index and stat_*, and
         the pool rows of src's current scenario slot over dst's), then the same copy of the output rows.  dst ids are distinct
-        and none is also a src.  Needs n_scenarios % n_worlds == 0; refused while a planner is attached, on handles with
-        information-gain state and while episode records are initialised.  A pending step_begin is void afterwards."""
+        and none is also a src.  Needs n_scenarios % n_worlds == 0; refused while a planner is attached, while the env streams
+        scenarios, on handles with information-gain state and while episode records are initialised.  A pending step_begin is void
+        afterwards."""
         self._refuse_with_planner("fork")
+        self._refuse_streaming("fork", "the ring of scenario slots is not part of a snapshot, and a refill would overwrite the forked slot")
         s, hs = self._id_list(src, "fork(src)", check, self.N, distinct=False)
         d, hd = self._id_list(dst, "fork(dst)", check, self.N)
         if s.numel() != d.numel():

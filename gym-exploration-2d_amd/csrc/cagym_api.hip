@@ -28,6 +28,7 @@
 #include "cagym_ig_greedy.h"
 #include "cagym_episode_records.h"
 #include "cagym_snapshot.h"
+#include "cagym_stream.h"
 
 namespace {
 
@@ -62,6 +63,9 @@ struct Env {
     bool rec_ready = false;
     int n_ig = 0;        // IG robots (active CAGYM_POL_IGMCTS slots) of every scenario of the pool; N_IG_UNEQUAL when the scenarios
                          // differ, N_IG_RANDOM when cagym_generate_scenarios may have drawn some (cagym_ig_robot_inputs / _actions)
+    bool streaming = false;          // cagym_stream_scenarios started the ring and no pool setter or cagym_stream_stop ended it
+    StreamDev stream{};              // its device words (allocated by the first cagym_stream_scenarios; csrc/cagym_stream.h)
+    cagym_gen2_params stream_P{};    // the parameter set cagym_stream_refill generates with (cagym_stream_set_params replaces it)
 };
 enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
@@ -640,6 +644,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->obst_rvo = new_obst_rvo;
     e->D.ko = new_ko;
     e->scenarios_set = true;
+    e->streaming = false;  // the pool is the caller's again
     e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
     return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
 }
@@ -698,12 +703,18 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     }
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     e->scenarios_set = true;
+    e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
     return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
 }
 
-int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
-    ENTRY(e, env);
+// what a parameter set of the reference samplers implies for the handle (gen2_validate)
+struct Gen2Flags {
+    bool any_rvo = false, any_ig = false, obst_rvo = false;
+};
+
+// the argument checks of cagym_generate_reference_scenarios, shared with cagym_stream_scenarios / cagym_stream_set_params
+static int gen2_validate(Env* e, const cagym_gen2_params* params, Gen2Flags& F) {
     if (!params) return fail(e, CAGYM_E_INVALID, "null params");
     const cagym_gen2_params& P = *params;
     const int M = e->cfg.max_agents, K = e->cfg.max_obstacles;
@@ -726,11 +737,10 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
         const double p_b = own ? P.p_b : (kind >= CAGYM_GEN_STAGE_1 ? 0.0 : 0.5);
         return (pa == pol && p_b < 1.0) || (pb == pol && p_b > 0.0);
     };
-    bool any_rvo = false, any_ig = false, obst_rvo = false;
     for (int kind = 0; kind < CAGYM_GEN_NKINDS; kind++) {
         if (!((P.kinds_mask >> kind) & 1u)) continue;
-        any_rvo |= may(CAGYM_POL_RVO, kind);
-        any_ig |= may(CAGYM_POL_IGMCTS, kind);
+        F.any_rvo |= may(CAGYM_POL_RVO, kind);
+        F.any_ig |= may(CAGYM_POL_IGMCTS, kind);
         if (kind == CAGYM_GEN_STAGE_1 || kind == CAGYM_GEN_STAGE_2) {
             // the reference's randint range (tc.py:2377, 2482) narrowed by the caller's bounds, as the kernel narrows it
             const int rlo = kind == CAGYM_GEN_STAGE_1 ? 0 : 2, rhi = kind == CAGYM_GEN_STAGE_1 ? 4 : 10;
@@ -743,25 +753,32 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
             if (lo > hi)
                 return fail(e, CAGYM_E_INVALID, "the n_obst bounds leave " + name + " no rectangle count (its range is " +
                                                     std::to_string(rlo) + ".." + std::to_string(rhi) + ")");
-            obst_rvo |= hi > 0 && may(CAGYM_POL_RVO, kind);
+            F.obst_rvo |= hi > 0 && may(CAGYM_POL_RVO, kind);
         }
     }
     // the counts are drawn on the device: the handle's max_obstacles decides, as cagym_set_scenarios decides it for a pool with a full world
-    if (obst_rvo) {
+    if (F.obst_rvo) {
         const int rc = check_obst_rvo_capacity(e);
         if (rc != CAGYM_OK) return rc;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ON_DEVICE(e);
-    CagymDev& D = e->D;
+    return CAGYM_OK;
+}
+
+static Gen2Dev gen2_dev(const Env* e) {
     Gen2Dev G;
     G.G = gen_dev(e);
     G.obst = e->sc_obst;
     G.prep = reinterpret_cast<float*>(e->sc_obst_prep);
-    G.K = K;
-    if (int rc = gen_failed_word(e)) return rc;
-    int32_t* d_failed = e->gen_failed;
-    HIPCHK(e, hipMemsetAsync(d_failed, 0, sizeof(int32_t), st));
+    G.K = e->cfg.max_obstacles;
+    return G;
+}
+
+// every slot of the pool from the samplers (slot r from stream key r), its rasters, and the handle state a new pool commits;
+// d_failed: the device word the rejection loops report into (zeroed by the caller)
+static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int32_t* d_failed, int32_t* n_failed_host, hipStream_t st) {
+    CagymDev& D = e->D;
+    const int K = e->cfg.max_obstacles;
+    const Gen2Dev G = gen2_dev(e);
     hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
     HIPCHK(e, hipGetLastError());
     if (K > 0) {
@@ -775,13 +792,109 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
         HIPCHK(e, hipStreamSynchronize(st));
     }
     D.sc_heading0 = nullptr;  // toward the goal (agent.py:29-31)
-    e->any_rvo = any_rvo ? 1 : 0;
-    e->n_ig = any_ig ? N_IG_RANDOM : 0;
-    e->obst_rvo = obst_rvo ? 1 : 0;
-    e->D.ko = obst_rvo ? 2 * K : 0;
+    e->any_rvo = F.any_rvo ? 1 : 0;
+    e->n_ig = F.any_ig ? N_IG_RANDOM : 0;
+    e->obst_rvo = F.obst_rvo ? 1 : 0;
+    e->D.ko = F.obst_rvo ? 2 * K : 0;
     e->scenarios_set = true;
+    e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
     return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
+}
+
+int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
+    ENTRY(e, env);
+    Gen2Flags F;
+    if (int rc = gen2_validate(e, params, F)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(e);
+    if (int rc = gen_failed_word(e)) return rc;
+    HIPCHK(e, hipMemsetAsync(e->gen_failed, 0, sizeof(int32_t), st));
+    return gen2_fill(e, *params, F, e->gen_failed, n_failed_host, st);
+}
+
+// ---- streamed scenarios (csrc/cagym_stream.h) -------------------------------------------------------------------------------------------
+// what cagym_stream_scenarios and cagym_stream_set_params refuse beyond the generator's own checks
+static int stream_check(Env* e, const char* what, const cagym_gen2_params* params, Gen2Flags& F) {
+    if (int rc = gen2_validate(e, params, F)) return rc;
+    const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
+    if (S % N != 0 || S < 2 * N)
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": n_scenarios must be a multiple of n_worlds and at least 2 * n_worlds (a ring of depth >= 2 per world)");
+    if (e->ig_ready) return fail(e, CAGYM_E_UNSUPPORTED, std::string(what) + " after cagym_ig_init: the per-slot distance field is not rebuilt");
+    if (F.any_ig) return fail(e, CAGYM_E_UNSUPPORTED, std::string(what) + ": the parameter set can place CAGYM_POL_IGMCTS agents");
+    if (e->rec_ready)
+        return fail(e, CAGYM_E_STATE, std::string(what) + " with episode records initialised: their table has one row per pool slot, "
+                                                          "which a streamed pool reuses");
+    return CAGYM_OK;
+}
+
+int cagym_stream_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
+    ENTRY(e, env);
+    Gen2Flags F;
+    if (int rc = stream_check(e, "cagym_stream_scenarios", params, F)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(e);
+    const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
+    if (!e->stream.next_episode) {  // {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
+        unsigned char* buf = nullptr;
+        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
+        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
+        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
+        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
+        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
+    }
+    StreamDev& T = e->stream;
+    T.episode = e->D.episode;
+    T.map_bits = const_cast<uint32_t*>(e->D.map_bits);
+    T.N = N;
+    T.depth = S / N;
+    // the first fill counts: generated = S, n_failed = its failures
+    HIPCHK(e, hipMemsetAsync(T.generated, 0, 16, st));
+    HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.generated), S, 1, st));
+    HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.next_episode), T.depth, (size_t)N, st));
+    if (int rc = gen2_fill(e, *params, F, T.n_failed, n_failed_host, st)) return rc;
+    e->stream_P = *params;
+    e->streaming = true;
+    return CAGYM_OK;
+}
+
+int cagym_stream_set_params(void* env, const cagym_gen2_params* params) {
+    ENTRY_IF(e, env, e->streaming, "cagym_stream_set_params on a handle that is not streaming");
+    Gen2Flags F;
+    if (int rc = stream_check(e, "cagym_stream_set_params", params, F)) return rc;
+    // slots of both parameter sets are in the ring from now on: the handle's flags cover both
+    const int any_rvo = (e->any_rvo || F.any_rvo) ? 1 : 0, obst_rvo = (e->obst_rvo || F.obst_rvo) ? 1 : 0;
+    if (any_rvo != e->any_rvo || obst_rvo != e->obst_rvo) e->begun = false;  // a pending cagym_step_begin solved for the old flags
+    e->any_rvo = any_rvo;
+    e->obst_rvo = obst_rvo;
+    e->D.ko = obst_rvo ? 2 * e->cfg.max_obstacles : 0;
+    e->stream_P = *params;
+    return CAGYM_OK;
+}
+
+int cagym_stream_refill(void* env, void* stream) {
+    ENTRY_IF(e, env, e->streaming, "cagym_stream_refill on a handle that is not streaming");
+    ON_DEVICE(e);
+    const unsigned grid = (unsigned)((e->cfg.n_worlds + CAGYM_WAVE - 1) / CAGYM_WAVE);
+    hipLaunchKernelGGL(k_stream_refill, dim3(grid), dim3(CAGYM_WAVE), 0, reinterpret_cast<hipStream_t>(stream), gen2_dev(e), e->stream_P, e->stream);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_stream_get(void* env, cagym_stream_ptrs* out) {
+    ENTRY_IF(e, env, e->stream.next_episode != nullptr, "cagym_stream_get before cagym_stream_scenarios");
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    out->next_episode = e->stream.next_episode;
+    out->generated = reinterpret_cast<const uint64_t*>(e->stream.generated);
+    out->n_failed = e->stream.n_failed;
+    out->n_lapped = e->stream.n_lapped;
+    return CAGYM_OK;
+}
+
+int cagym_stream_stop(void* env) {
+    ENTRY(e, env);
+    e->streaming = false;
+    return CAGYM_OK;
 }
 
 int cagym_get_obstacles(void* env, const double** obst, const int32_t** n_obst) {
@@ -1126,6 +1239,7 @@ int cagym_ga3c_forward(void* env, const float* weights, const float* state, cons
 // ---- information-gain primitives -----------------------------------------------------------------
 int cagym_ig_init(void* env, void* stream) {
     ENTRY_POOL(e, env, "cagym_ig_init");
+    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_ig_init on a streaming handle: the per-slot distance field is not rebuilt by cagym_stream_refill");
     if (e->cfg.max_obstacles <= 0 || !e->D.map_bits)
         return fail(e, CAGYM_E_UNSUPPORTED, "information-gain primitives need obstacle rasters (max_obstacles > 0)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1408,6 +1522,8 @@ int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const 
 // ---- per-scenario episode records (csrc/cagym_episode_records.h) --------------------------------------------------------------------
 int cagym_episode_records_init(void* env, int keep, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_records_init");
+    if (e->streaming)
+        return fail(e, CAGYM_E_STATE, "cagym_episode_records_init on a streaming handle: the table has one row per pool slot, which a streamed pool reuses");
     if (keep != CAGYM_EPREC_KEEP_FIRST && keep != CAGYM_EPREC_KEEP_LAST) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_init: unknown keep mode");
     ON_DEVICE(e);
     if (!e->rec.t) {
@@ -1496,6 +1612,7 @@ int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* bl
         layout->reserved != own.reserved || layout->row_bytes != own.row_bytes)
         return fail(e, CAGYM_E_INVALID, "cagym_restore: the blob's layout is not this handle's (n_worlds, max_agents, n_scenarios, max_obstacles, "
                                         "cagym_ig_init done or not, magic and version must all match)");
+    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_restore on a streaming handle: the ring of scenario slots is not part of a snapshot");
     if (e->rec_ready)
         return fail(e, CAGYM_E_STATE, "cagym_restore with episode records initialised: their running rows would describe another timeline; "
                                       "detach the records first");
@@ -1507,6 +1624,7 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
     ENTRY_POOL(e, env, "cagym_fork");
     if (n < 0 || n > e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, "cagym_fork: n must be in [0, n_worlds]");
     if (n > 0 && (!src || !dst)) return fail(e, CAGYM_E_INVALID, "cagym_fork: null src / dst");
+    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork on a streaming handle: the ring of scenario slots is not part of a snapshot");
     if (e->rec_ready)
         return fail(e, CAGYM_E_STATE, "cagym_fork with episode records initialised: their running rows would describe another timeline; "
                                       "detach the records first");

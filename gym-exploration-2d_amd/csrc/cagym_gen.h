@@ -20,18 +20,19 @@ __device__ __forceinline__ uint64_t gen_mix64(uint64_t z) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-// U[0,1) with 53 random bits, draw k of scenario s
+// U[0,1) with 53 random bits, draw k of stream key s
 __device__ __forceinline__ double gen_u01(uint64_t seed, uint32_t s, uint32_t k) {
     const uint64_t h = gen_mix64(seed ^ gen_mix64(((uint64_t)s << 32) | (uint64_t)k));
     return (double)(h >> 11) * 0x1.0p-53;
 }
 
-// scenario s by the rule of train_agents_random_positions; returns the agents whose rejection loop hit max_tries.  Shared by
-// k_generate_scenarios and cagym_gen2.h's RANDOM_POSITIONS kind, which therefore agree bit for bit.
-__device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym_gen_params& P, int s) {
+// one scenario by the rule of train_agents_random_positions, drawn from stream key v and stored in pool row s (the pool
+// generators pass v == s; csrc/cagym_stream.h keys a ring slot by its world's episode); returns the agents whose rejection loop hit
+// max_tries.  Shared by k_generate_scenarios and cagym_gen2.h's RANDOM_POSITIONS kind, which therefore agree bit for bit.
+__device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym_gen_params& P, uint32_t v, int s) {
     const int M = G.M;
     uint32_t k = 0;
-    int n = P.n_min + (int)(gen_u01(P.seed, s, k++) * (double)(P.n_max - P.n_min + 1));
+    int n = P.n_min + (int)(gen_u01(P.seed, v, k++) * (double)(P.n_max - P.n_min + 1));
     n = n < P.n_min ? P.n_min : (n > P.n_max ? P.n_max : n);
     double* A = G.agents6 + (size_t)s * M * 6;
     int failed = 0;
@@ -42,10 +43,10 @@ __device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym
             double x0 = 0, y0 = 0, gx = 0, gy = 0;
             bool ok = false;
             for (int tries = 0; tries < P.max_tries && !ok; tries++) {  // every lane leaves after max_tries
-                x0 = -P.side + (2.0 * P.side) * gen_u01(P.seed, s, k++);  // np.random.uniform(low, high): low + (high-low)*u
-                y0 = -P.side + (2.0 * P.side) * gen_u01(P.seed, s, k++);
-                gx = -P.side + (2.0 * P.side) * gen_u01(P.seed, s, k++);
-                gy = -P.side + (2.0 * P.side) * gen_u01(P.seed, s, k++);
+                x0 = -P.side + (2.0 * P.side) * gen_u01(P.seed, v, k++);  // np.random.uniform(low, high): low + (high-low)*u
+                y0 = -P.side + (2.0 * P.side) * gen_u01(P.seed, v, k++);
+                gx = -P.side + (2.0 * P.side) * gen_u01(P.seed, v, k++);
+                gy = -P.side + (2.0 * P.side) * gen_u01(P.seed, v, k++);
                 ok = !(norm2(gx - x0, gy - y0) < P.min_travel);
                 for (int j = 0; j < i && ok; j++) {
                     const double* b = A + j * 6;
@@ -59,7 +60,7 @@ __device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym
                 pol = P.ego_policy;
                 dyn = P.ego_dynamics;
             } else {
-                pol = gen_u01(P.seed, s, k++) < P.p_b ? P.policy_b : P.policy_a;
+                pol = gen_u01(P.seed, v, k++) < P.p_b ? P.policy_b : P.policy_a;
                 dyn = P.other_dynamics;
             }
         } else {
@@ -79,6 +80,6 @@ __device__ __forceinline__ int gen_random_positions(const GenDev& G, const cagym
 __global__ void __launch_bounds__(64) k_generate_scenarios(GenDev G, cagym_gen_params P, int32_t* n_failed) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= G.S) return;
-    const int failed = gen_random_positions(G, P, s);
+    const int failed = gen_random_positions(G, P, (uint32_t)s, s);
     if (failed) atomicAdd(n_failed, failed);
 }

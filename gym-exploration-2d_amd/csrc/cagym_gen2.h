@@ -47,7 +47,7 @@ __device__ __forceinline__ void gen2_row(double* a, double sx, double sy, double
 }
 
 // policies of slots 1..n-1 (slot order), dynamics, coop; slot 0 = the ego; empty slots as cagym_generate_scenarios leaves them
-__device__ __forceinline__ void gen2_assign(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t s, uint32_t& k, int n,
+__device__ __forceinline__ void gen2_assign(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t v, uint32_t s, uint32_t& k, int n,
                                             int pol_a, int pol_b, double p_b, int ego_dyn, double coop_ego, double coop_other) {
     const int M = D.G.M;
     for (int i = 0; i < M; i++) {
@@ -58,7 +58,7 @@ __device__ __forceinline__ void gen2_assign(const Gen2Dev& D, const cagym_gen2_p
             dyn = ego_dyn;
             coop = coop_ego;
         } else if (i < n) {
-            pol = gen_u01(P.seed, s, k++) < p_b ? pol_b : pol_a;
+            pol = gen_u01(P.seed, v, k++) < p_b ? pol_b : pol_a;
             dyn = P.other_dynamics;
         } else {
             gen2_row(D.G.agents6 + ((size_t)s * M + i) * 6, 0.0, 0.0, 0.0, 0.0);
@@ -71,11 +71,11 @@ __device__ __forceinline__ void gen2_assign(const Gen2Dev& D, const cagym_gen2_p
 }
 
 // train_agents_swap_circle (tc.py:1192-1282)
-__device__ int gen2_swap_circle(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t s, int nmax, int pa, int pb, double p_b,
+__device__ int gen2_swap_circle(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t v, uint32_t s, int nmax, int pa, int pb, double p_b,
                                 int ego_dyn) {
     double* A = D.G.agents6 + (size_t)s * D.G.M * 6;
     uint32_t k = 0;
-    const int c = gen2_count(P.seed, s, k, 2, nmax);
+    const int c = gen2_count(P.seed, v, k, 2, nmax);
     const int n = P.fixed_count ? nmax : c;
     const int na = 2 * (n / 2);
     int failed = 0;
@@ -83,8 +83,8 @@ __device__ int gen2_swap_circle(const Gen2Dev& D, const cagym_gen2_params& P, ui
         double x = 0, y = 0;
         bool ok = false;
         for (int tries = 0; tries < P.max_tries && !ok; tries++) {
-            const double d = gen2_uniform(P.seed, s, k, 4.0, 8.0);
-            const double ang = gen2_uniform(P.seed, s, k, -M_PI, M_PI);
+            const double d = gen2_uniform(P.seed, v, k, 4.0, 8.0);
+            const double ang = gen2_uniform(P.seed, v, k, -M_PI, M_PI);
             x = d * cos(ang);
             y = d * sin(ang);
             ok = true;
@@ -97,24 +97,24 @@ __device__ int gen2_swap_circle(const Gen2Dev& D, const cagym_gen2_params& P, ui
         gen2_row(A + 6 * (2 * p), -x, -y, x, y);
         gen2_row(A + 6 * (2 * p + 1), x, y, -x, -y);
     }
-    gen2_assign(D, P, s, k, na, pa, pb, p_b, ego_dyn, 1.0, 0.5);
+    gen2_assign(D, P, v, s, k, na, pa, pb, p_b, ego_dyn, 1.0, 0.5);
     return failed;
 }
 
 // train_agents_pairwise_swap (tc.py:1283-1364); the drawn positions wait in the start columns of slots 0..n-1
-__device__ int gen2_pairwise_swap(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t s, int nmax, int pa, int pb, double p_b,
+__device__ int gen2_pairwise_swap(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t v, uint32_t s, int nmax, int pa, int pb, double p_b,
                                   int ego_dyn) {
     double* A = D.G.agents6 + (size_t)s * D.G.M * 6;
     uint32_t k = 0;
-    const int c = gen2_count(P.seed, s, k, 2, nmax);
+    const int c = gen2_count(P.seed, v, k, 2, nmax);
     const int n = P.fixed_count ? nmax : c;
     int failed = 0;
     for (int i = 0; i < n; i++) {
         double x = 0, y = 0;
         bool ok = false;
         for (int tries = 0; tries < P.max_tries && !ok; tries++) {
-            x = gen2_uniform(P.seed, s, k, -7.5, 7.5);
-            y = gen2_uniform(P.seed, s, k, -7.5, 7.5);
+            x = gen2_uniform(P.seed, v, k, -7.5, 7.5);
+            y = gen2_uniform(P.seed, v, k, -7.5, 7.5);
             ok = true;
             for (int j = 0; j < i && ok; j++)
                 if (gen2_near(x, y, A[6 * j], A[6 * j + 1], 2.0)) ok = false;
@@ -124,7 +124,7 @@ __device__ int gen2_pairwise_swap(const Gen2Dev& D, const cagym_gen2_params& P, 
         A[6 * i + 1] = y;
     }
     for (int i = n - 1; i >= 1; i--) {  // random.shuffle
-        int j = (int)(gen_u01(P.seed, s, k++) * (double)(i + 1));
+        int j = (int)(gen_u01(P.seed, v, k++) * (double)(i + 1));
         j = j > i ? i : j;
         const double tx = A[6 * i], ty = A[6 * i + 1];
         A[6 * i] = A[6 * j];
@@ -138,12 +138,12 @@ __device__ int gen2_pairwise_swap(const Gen2Dev& D, const cagym_gen2_params& P, 
         gen2_row(A + 6 * (2 * p), x0, y0, x1, y1);
         gen2_row(A + 6 * (2 * p + 1), x1, y1, x0, y0);
     }
-    gen2_assign(D, P, s, k, na, pa, pb, p_b, ego_dyn, 1.0, 0.5);
+    gen2_assign(D, P, v, s, k, na, pa, pb, p_b, ego_dyn, 1.0, 0.5);
     return failed;
 }
 
 // train_stage_1 / train_stage_2 (tc.py:2359-2572)
-__device__ int gen2_stage(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t s, const Gen2Kind& C, int nmax, int pa, int pb,
+__device__ int gen2_stage(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t v, uint32_t s, const Gen2Kind& C, int nmax, int pa, int pb,
                           double p_b) {
     double* A = D.G.agents6 + (size_t)s * D.G.M * 6;
     double* ob = D.obst + (size_t)s * D.K * 4;
@@ -151,21 +151,21 @@ __device__ int gen2_stage(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t
     // the reference's range narrowed by the caller's bounds (< 0: none); cagym_generate_reference_scenarios refuses an empty one
     const int nob_min = P.n_obst_min < 0 ? C.nob_min : max(C.nob_min, P.n_obst_min);
     const int nob_max = P.n_obst_max < 0 ? C.nob_max : min(C.nob_max, P.n_obst_max);
-    const int nob = gen2_count(P.seed, s, k, nob_min, nob_max);
+    const int nob = gen2_count(P.seed, v, k, nob_min, nob_max);
     int failed = 0;
     for (int r = 0; r < nob; r++) {
         double sx, sy;
-        if (gen_u01(P.seed, s, k++) < 0.5) {  // np.random.choice(['square', 'rectangle'])
-            sx = sy = gen2_uniform(P.seed, s, k, C.sq_lo, C.sq_hi);
+        if (gen_u01(P.seed, v, k++) < 0.5) {  // np.random.choice(['square', 'rectangle'])
+            sx = sy = gen2_uniform(P.seed, v, k, C.sq_lo, C.sq_hi);
         } else {
-            sx = gen2_uniform(P.seed, s, k, 1.0, 4.0);
-            sy = sx > 2.0 ? gen2_uniform(P.seed, s, k, 1.0, 2.0) : gen2_uniform(P.seed, s, k, 3.0, 4.0);
+            sx = gen2_uniform(P.seed, v, k, 1.0, 4.0);
+            sy = sx > 2.0 ? gen2_uniform(P.seed, v, k, 1.0, 2.0) : gen2_uniform(P.seed, v, k, 3.0, 4.0);
         }
         double xl = 0, yl = 0, xu = 0, yu = 0;
         bool ok = false;
         for (int tries = 0; tries < P.max_tries && !ok; tries++) {
-            xu = gen2_uniform(P.seed, s, k, C.c_lo, C.c_hi);
-            yu = gen2_uniform(P.seed, s, k, C.c_lo, C.c_hi);
+            xu = gen2_uniform(P.seed, v, k, C.c_lo, C.c_hi);
+            yu = gen2_uniform(P.seed, v, k, C.c_lo, C.c_hi);
             xl = xu - sx;
             yl = yu - sy;
             ok = true;
@@ -183,15 +183,15 @@ __device__ int gen2_stage(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t
     for (int i = 0; i < nmax; i++) {
         if (i == 1) {  // others = random.randint(1, max(number_of_agents - 1, 1)), drawn after the ego is placed
             const int hi = nmax - 1;
-            const int c = gen2_count(P.seed, s, k, 1, hi);
+            const int c = gen2_count(P.seed, v, k, 1, hi);
             n = 1 + (P.fixed_count ? hi : c);
         }
         if (i >= n) break;
         double x = 0, y = 0;
         bool ok = false;
         for (int tries = 0; tries < P.max_tries && !ok; tries++) {
-            const double d = gen2_uniform(P.seed, s, k, C.d_lo, C.d_hi);
-            const double ang = gen2_uniform(P.seed, s, k, -M_PI, M_PI);
+            const double d = gen2_uniform(P.seed, v, k, C.d_lo, C.d_hi);
+            const double ang = gen2_uniform(P.seed, v, k, -M_PI, M_PI);
             x = d * cos(ang);
             y = d * sin(ang);
             ok = gen2_clear(ob, nob, x, y) && gen2_clear(ob, nob, -x, -y);
@@ -205,7 +205,7 @@ __device__ int gen2_stage(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t
         if (!ok) failed++;
         gen2_row(A + 6 * i, x, y, -x, -y);
     }
-    gen2_assign(D, P, s, k, n, pa, pb, p_b, P.ego_dynamics, 1.0, 1.0);
+    gen2_assign(D, P, v, s, k, n, pa, pb, p_b, P.ego_dynamics, 1.0, 1.0);
     return failed;
 }
 
@@ -240,15 +240,17 @@ __device__ void gen2_prep(const Gen2Dev& D, uint32_t s) {
     }
 }
 
-__global__ void __launch_bounds__(64) k_generate_reference_scenarios(Gen2Dev D, cagym_gen2_params P, int32_t* n_failed) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= D.G.S) return;
+// One scenario of the mixture P, drawn from stream key v and stored in pool row s: the kind pick, the kind's sampler, empty rectangle
+// rows for a free-space kind and the RVO prep rows.  Returns the agents and rectangles whose rejection loop hit max_tries.  Every
+// draw is keyed by v alone, so a row's bits depend on (P, v) and not on where it is stored (k_generate_reference_scenarios passes
+// v == s; k_stream_refill, csrc/cagym_stream.h, keys a ring slot by its world's episode).
+__device__ int gen2_scenario(const Gen2Dev& D, const cagym_gen2_params& P, uint32_t v, uint32_t s) {
     int kind = 0;
     {
         const int nk = __popc(P.kinds_mask);
         int pick = 0;
         if (nk > 1) {  // _init_agents' np.random.randint over the kinds, from the scenario's second stream
-            pick = (int)(gen_u01(P.seed ^ 0xD1B54A32D192ED03ull, s, 0) * (double)nk);
+            pick = (int)(gen_u01(P.seed ^ 0xD1B54A32D192ED03ull, v, 0) * (double)nk);
             pick = pick >= nk ? nk - 1 : pick;
         }
         for (int b = 0, seen = 0; b < CAGYM_GEN_NKINDS; b++)
@@ -264,8 +266,8 @@ __global__ void __launch_bounds__(64) k_generate_reference_scenarios(Gen2Dev D, 
     if (kind == CAGYM_GEN_SWAP_CIRCLE || kind == CAGYM_GEN_PAIRWISE_SWAP) {
         const int pa = own ? P.policy_a : CAGYM_POL_RVO, pb = own ? P.policy_b : CAGYM_POL_NONCOOP;
         const double p_b = own ? P.p_b : 0.2;
-        failed = kind == CAGYM_GEN_SWAP_CIRCLE ? gen2_swap_circle(D, P, s, nmax, pa, pb, p_b, ego_dyn)
-                                               : gen2_pairwise_swap(D, P, s, nmax, pa, pb, p_b, ego_dyn);
+        failed = kind == CAGYM_GEN_SWAP_CIRCLE ? gen2_swap_circle(D, P, v, s, nmax, pa, pb, p_b, ego_dyn)
+                                               : gen2_pairwise_swap(D, P, v, s, nmax, pa, pb, p_b, ego_dyn);
     } else if (kind == CAGYM_GEN_RANDOM_POSITIONS) {
         cagym_gen_params Q;
         Q.seed = P.seed;
@@ -279,11 +281,11 @@ __global__ void __launch_bounds__(64) k_generate_reference_scenarios(Gen2Dev D, 
         Q.max_tries = P.max_tries;
         Q.p_b = own ? P.p_b : 0.5;
         Q.side = 7.5; Q.min_travel = 4.0; Q.min_sep = 1.5; Q.radius = 0.5; Q.pref_speed = 1.0; Q.coop = 0.5;
-        failed = gen_random_positions(D.G, Q, s);
+        failed = gen_random_positions(D.G, Q, v, (int)s);
     } else {
         const Gen2Kind C = kind == CAGYM_GEN_STAGE_1 ? Gen2Kind{1.0, 3.0, -4.0, 6.0, 6.0, 8.0, 0, 4}
                                                      : Gen2Kind{1.0, 2.0, -8.0, 10.0, 8.0, 10.0, 2, 10};
-        failed = gen2_stage(D, P, s, C, nmax, own ? P.policy_a : CAGYM_POL_RVO, own ? P.policy_b : CAGYM_POL_RVO, own ? P.p_b : 0.0);
+        failed = gen2_stage(D, P, v, s, C, nmax, own ? P.policy_a : CAGYM_POL_RVO, own ? P.policy_b : CAGYM_POL_RVO, own ? P.p_b : 0.0);
     }
     if (kind != CAGYM_GEN_STAGE_1 && kind != CAGYM_GEN_STAGE_2) {  // free space
         D.G.nobst[s] = 0;
@@ -293,5 +295,12 @@ __global__ void __launch_bounds__(64) k_generate_reference_scenarios(Gen2Dev D, 
         }
     }
     if (D.K > 0) gen2_prep(D, s);
+    return failed;
+}
+
+__global__ void __launch_bounds__(64) k_generate_reference_scenarios(Gen2Dev D, cagym_gen2_params P, int32_t* n_failed) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= D.G.S) return;
+    const int failed = gen2_scenario(D, P, (uint32_t)s, (uint32_t)s);
     if (failed) atomicAdd(n_failed, failed);
 }

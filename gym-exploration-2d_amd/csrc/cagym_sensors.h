@@ -117,9 +117,9 @@ __global__ void __launch_bounds__(256) k_occupancy_grid(CagymDev D, uint8_t* out
     }
 }
 
-// Map.get_occupancy_grid (Map.py:107-123): one workgroup per scenario, bit-packed output.
-__global__ void __launch_bounds__(256) k_rasterize(const double* obst, const int32_t* nobst, int Kobs, uint32_t* map_bits) {
-    const int s = blockIdx.x;
+// Map.get_occupancy_grid (Map.py:107-123) of pool row s, bit-packed output, by the whole workgroup: every lane of it makes the call
+// (it holds workgroup barriers).  The rectangle rows must be visible to the workgroup on entry.
+__device__ __forceinline__ void rasterize_scenario(const double* obst, const int32_t* nobst, int Kobs, uint32_t* map_bits, int s) {
     uint32_t* map = map_bits + (size_t)s * CAGYM_MAPD * CAGYM_MAPW;
     for (int q = threadIdx.x; q < CAGYM_MAPD * CAGYM_MAPW; q += blockDim.x) map[q] = 0u;
     __syncthreads();
@@ -143,4 +143,9 @@ __global__ void __launch_bounds__(256) k_rasterize(const double* obst, const int
         }
         __syncthreads();
     }
+}
+
+// one workgroup per scenario of the pool (k_stream_refill, csrc/cagym_stream.h, rasterises the slots it refills itself)
+__global__ void __launch_bounds__(256) k_rasterize(const double* obst, const int32_t* nobst, int Kobs, uint32_t* map_bits) {
+    rasterize_scenario(obst, nobst, Kobs, map_bits, blockIdx.x);
 }

@@ -570,6 +570,57 @@ int cagym_snapshot(void* env, const int32_t* worlds, int n, void* blob, void* st
 int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* blob, const int32_t* rows, int n, void* stream);
 int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* stream);
 
+/* ---- Fresh scenarios streamed into the pool under auto-reset (csrc/cagym_stream.h) ---------------------------------------------------
+ * The reference draws a new random world at every reset() (_init_agents, collision_avoidance_env.py:403-442, with the curriculum of
+ * :419-438 changing the sampler set as training goes on).  A fixed pool replays its scenarios after S / N episodes; streaming turns
+ * the pool into a ring of depth k = S / N per world instead: world w owns slots w, w + N, ..., w + (k - 1) N, and slot
+ * (w + e * N) % S holds the scenario of its episode e - the one cagym_generate_reference_scenarios' samplers draw for the stream key
+ * v = (uint32_t)(w + e * N), which takes the place of the scenario index in every u(k), the kind-pick stream included.  With constant
+ * parameters the scenario of (w, e) is a pure function of (params, w, e): row v of a plain pool of more than v slots generated with
+ * the same arguments, bit for bit (agents, policies, dynamics, counts, coop, rectangles, RVO prep rows, raster).  Keys wrap at 2^32:
+ * once w + e * N passes 2^32 the stream repeats the scenarios of the keys it started with.
+ * No step, reset or roll-out kernel knows of the stream: they keep deriving the slot from episode[w].
+ * cagym_stream_scenarios: validates exactly as cagym_generate_reference_scenarios (same codes and messages, the obstacle-capacity check
+ *   included) and refuses besides: n_scenarios % n_worlds != 0 or n_scenarios < 2 * n_worlds (CAGYM_E_INVALID); a handle with
+ *   information-gain state (cagym_ig_init done) or a parameter set that can place CAGYM_POL_IGMCTS agents (CAGYM_E_UNSUPPORTED: the
+ *   per-slot distance field would need a rebuild); initialised episode records (CAGYM_E_STATE: their table is per pool slot).  Fills
+ *   all S slots, slot r from key r - the pool is what cagym_generate_reference_scenarios writes - commits the handle state as that call
+ *   does, sets next_episode[w] = k and restarts the counters (generated = S, n_failed = the fill's count, also copied to
+ *   *n_failed_host when that is not NULL, which synchronises `stream`; n_lapped = 0).  A refused call leaves the handle as it was.
+ *   The first call allocates the words of cagym_stream_get.
+ * cagym_stream_refill: ONE launch on `stream`, no host synchronisation, no allocation; enqueue it behind every call that can advance
+ *   an episode counter (cagym_step_autoreset, cagym_step_finish with auto_reset, cagym_rollout with auto_reset - once behind the
+ *   launch -, cagym_reset with advance_episode) and before the next such call.  CAGYM_E_STATE on a handle that is not streaming.
+ *   Per world it reads episode[w] and next_episode[w].  next_episode[w] <= episode[w]: the world has lapped - it started an episode on
+ *   a slot that was never refilled (more than k - 1 episodes finished between two refills, which only a roll-out can do); it is
+ *   counted once in n_lapped and its current slot is left alone.  It generates the episodes max(next_episode, episode + 1) ..
+ *   episode + k - 1 into their slots, sets next_episode[w] = episode[w] + k and adds to generated and n_failed.  The slot of a world's
+ *   current episode is never written, and S % N == 0 gives every slot one writer.  A world that finished nothing costs two loads.
+ *   The parameter set is a by-value kernel argument: a graph that captured the call keeps the set it was captured with.
+ * cagym_stream_set_params: the reference's curriculum switch.  Same validation and refusals; takes effect for the slots later refills
+ *   generate (the seed may change too); scenarios already in the ring stay, so a world meets the new set k - 1 episodes later.  While
+ *   the stream runs, the handle's flags (RVO agents present, RVO agents among rectangles) are the union of what both sets imply; a
+ *   change of them voids a pending cagym_step_begin.  CAGYM_E_STATE on a handle that is not streaming.
+ * cagym_stream_get: zero-copy DEVICE views, owned by the handle: next_episode [N] i32, generated u64, n_failed i32, n_lapped i32.
+ *   CAGYM_E_STATE before the first cagym_stream_scenarios; they stay readable after the stream stopped.
+ * cagym_stream_stop: ends the stream (the pool stays as it is); a successful cagym_set_scenarios, cagym_generate_scenarios or
+ *   cagym_generate_reference_scenarios does the same.
+ * While streaming: cagym_restore and cagym_fork return CAGYM_E_UNSUPPORTED (the ring is not part of a snapshot; cagym_snapshot stays
+ * allowed), cagym_ig_init CAGYM_E_UNSUPPORTED and cagym_episode_records_init CAGYM_E_STATE.
+ * Not streamed: cagym_generate_scenarios' own parameter struct (the RANDOM_POSITIONS kind covers its rule). */
+struct cagym_stream_ptrs {
+    const int32_t* next_episode; /* [N] first episode of world w whose slot has not been generated */
+    const uint64_t* generated;   /* slots generated since cagym_stream_scenarios, its fill included */
+    const int32_t* n_failed;     /* agents and rectangles whose rejection loop hit max_tries, since then */
+    const int32_t* n_lapped;     /* times a world started an episode on a slot that had not been refilled */
+};
+typedef struct cagym_stream_ptrs cagym_stream_ptrs;
+int cagym_stream_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream);
+int cagym_stream_refill(void* env, void* stream);
+int cagym_stream_set_params(void* env, const cagym_gen2_params* params);
+int cagym_stream_get(void* env, cagym_stream_ptrs* out);
+int cagym_stream_stop(void* env);
+
 #ifdef __cplusplus
 }
 #endif
