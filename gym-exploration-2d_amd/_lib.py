@@ -68,6 +68,17 @@ class CagymEpisodeRecordPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in EPREC_FIELDS]
 
 
+# cagym_episode_log_ptrs: (field, typestr, shape in terms of L / N / M); the int32 capacity closes the struct
+EPLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
+                ("ret", "f8", "L"), ("outcome", "i4", "L"), ("n_agents", "i4", "L"), ("n_obst", "i4", "L"), ("t", "f8", "LM"),
+                ("extra_t", "f8", "LM"), ("flags", "u1", "LM"), ("t_run", "f8", "NM"), ("ret_run", "f8", "N"),
+                ("steps_run", "i4", "N"), ("atgoal_run", "u4", "N"), ("cursor", "i4", "N"), ("head", "u8", "1"), ("desync", "i4", "1")]
+
+
+class CagymEpisodeLogPtrs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _, _ in EPLOG_FIELDS] + [("capacity", C.c_int32)]
+
+
 class DmctsParams(C.Structure):
     """cagym_dmcts_params (include/cagym.h)."""
     _fields_ = [(n, C.c_int32) for n in ("n_robots", "Ntree", "Nsims", "horizon", "Ncycles", "comm_n", "xdt", "reset_comms")] + \
@@ -147,6 +158,10 @@ _ARGTYPES = {
     "cagym_episode_records_update": [_vp, _vp, _vp, _vp, _int, _vp],
     "cagym_episode_records_restart": [_vp, _vp, _int, _vp],
     "cagym_episode_records_get": [_vp, _P(CagymEpisodeRecordPtrs)],
+    "cagym_episode_log_init": [_vp, _int, _vp],
+    "cagym_episode_log_update": [_vp, _vp, _vp, _vp, _int, _vp],
+    "cagym_episode_log_restart": [_vp, _vp, _int, _vp],
+    "cagym_episode_log_get": [_vp, _P(CagymEpisodeLogPtrs)],
     "cagym_snapshot_layout_of": [_vp, _P(CagymSnapshotLayout)],
     "cagym_snapshot": [_vp, _vp, _int, _vp, _vp],
     "cagym_restore": [_vp, _P(CagymSnapshotLayout), _vp, _vp, _int, _vp],

@@ -94,7 +94,7 @@ class BatchedCollisionAvoidanceEnv(object):
         # the calls inside per-step loops, resolved once
         self._step_fn = (self.L.cagym_step, self.L.cagym_step_autoreset)
         self._rollout_fn, self._records_fn = self.L.cagym_rollout, self.L.cagym_episode_records_update
-        self._refill_fn = self.L.cagym_stream_refill
+        self._refill_fn, self._log_fn = self.L.cagym_stream_refill, self.L.cagym_episode_log_update
         N, M, K = self.N, self.M, self.K
         dev = self.device
         self.obs_oas = torch.zeros((N, M, K, 10), dtype=torch.float32, device=dev)
@@ -116,6 +116,8 @@ class BatchedCollisionAvoidanceEnv(object):
         self._rec = None          # keep mode of attach_episode_records, None while detached
         self._rec_views = None
         self._rec_priv = {}       # rollout buffers of a caller whose `out` lacks reward / flags / game_over
+        self._log = None          # capacity of attach_episode_log, None while detached
+        self._log_views = None
         self._streaming = False   # stream_reference_scenarios: one cagym_stream_refill behind every episode-advancing call
         self._stream_views = None
 
@@ -505,10 +507,7 @@ class BatchedCollisionAvoidanceEnv(object):
                                "without auto-reset and reset() yourself" % (k, k))
         self._records_contract(auto_reset, "step")
         self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None)
-        if self._streaming and auto_reset:
-            self._refill()
-        if self._rec is not None:
-            self._records_update(self.flags, self.reward, self.game_over, 1)
+        self._after_steps(auto_reset, self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
 
     # ---- per-scenario episode records (include/cagym.h: cagym_episode_records_*) ---------------------------------------------
@@ -533,7 +532,23 @@ class BatchedCollisionAvoidanceEnv(object):
         """Stop feeding the recorder (its table stays readable through the C ABI; attach again to clear and resume)."""
         self._rec = None
 
+    def _after_steps(self, auto_reset, flags, reward, game_over, T):
+        """What follows the step launch(es) of one call on the stream, in this order: the episode log's update (it reads the pool
+        slot of the episode that ended, which the refill regenerates next), the stream's refill, the records' update."""
+        if self._log is not None:
+            rc = self._log_fn(self.h, flags.data_ptr(), reward.data_ptr(), game_over.data_ptr(), int(T), self._stream())
+            if rc:
+                _lib.check(self.L, self.h, rc, "cagym_episode_log_update")
+        if self._streaming and auto_reset:
+            self._refill()
+        if self._rec is not None:
+            self._records_update(flags, reward, game_over, T)
+
     def _records_contract(self, auto_reset, what):
+        if self._log is not None and not auto_reset:
+            raise RuntimeError("%s(auto_reset=False) with an episode log attached: cagym_episode_log_update takes the outputs "
+                               "of auto-reset stepping only, every step exactly once and in order (include/cagym.h); "
+                               "detach_episode_log() first" % what)
         if self._rec is not None and not auto_reset:
             raise RuntimeError("%s(auto_reset=False) with episode records attached: cagym_episode_records_update takes the outputs "
                                "of auto-reset stepping only, every step exactly once and in order (include/cagym.h); "
@@ -546,7 +561,7 @@ class BatchedCollisionAvoidanceEnv(object):
 
     def _records_out(self, out, n_steps):
         """reward / flags / game_over slices for the recorder: the caller's, or private ones where `out` has none."""
-        if self._rec is None:
+        if self._rec is None and self._log is None:
             return out
         T = int(n_steps)
         shapes = {"reward": ((T, self.N, self.M), torch.float32), "flags": ((T, self.N, self.M), torch.uint8),
@@ -588,6 +603,80 @@ class BatchedCollisionAvoidanceEnv(object):
                                    "again to clear" % d)
         return dict(self._rec_views)
 
+    # ---- append-only episode log (include/cagym.h: cagym_episode_log_*) --------------------------------------------------------
+    def attach_episode_log(self, capacity=65536):
+        """From now on every auto-resetting step / rollout is followed, on the same stream, by one cagym_episode_log_update: ONE ROW
+        PER FINISHED EPISODE in a device ring of `capacity` rows (the newest overwrite the oldest).  Unlike the per-scenario
+        records it is not keyed by pool slot, so it works on any pool and under stream_reference_scenarios: a row names its
+        episode by key = (uint32)(world + episode * N), the stream key its scenario was drawn for, and carries world, episode,
+        slice, steps, ret, outcome, n_agents, n_obst, t / extra_t / flags [M].  The same paths feed it as the records (step,
+        step_finish, step_overlapped, rollout in its three forms, CagymVecEnv.step), in the order step(s), log update, stream
+        refill, records update; step(auto_reset=False) and rollout(auto_reset=False) are refused while attached, and so are
+        restore() and fork() (snapshot() is not).  Records and log may be attached together on a fixed pool.  A world that lapped
+        its ring inside a rollout logs the scenario that actually ran under the key of the one it should have met:
+        stream_stats()["n_lapped"] tells.  Attaching again clears the log and may change the capacity.  Needs a scenario pool."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("attach_episode_log: capacity must be >= 1, got %d" % capacity)
+        _lib.call(self.L, self.h, "cagym_episode_log_init", capacity, self._stream())
+        self._log, self._log_views = capacity, None
+        return self
+
+    def detach_episode_log(self):
+        """Stop feeding the log (the library keeps it, and keeps refusing restore / fork; attach again to clear and resume)."""
+        self._log = None
+
+    def clear_episode_log(self):
+        """Empty the log: every row, head, the slice counter and desync; every world forgets the episode in progress."""
+        self._refuse_without_log("clear_episode_log")
+        _lib.call(self.L, self.h, "cagym_episode_log_restart", None, 1, self._stream())
+
+    def _refuse_without_log(self, what):
+        if self._log is None:
+            raise RuntimeError("%s() without an episode log: attach_episode_log() first" % what)
+
+    def episode_log_views(self):
+        """Zero-copy device views of the ring and its words, no synchronisation: key (u32 bits as int32), world, episode, steps,
+        outcome, n_agents, n_obst [L] i32, slice [L] i64, ret [L] f64, t / extra_t [L, M] f64, flags [L, M] u8, the running t_run
+        [N, M], ret_run, steps_run, atgoal_run, cursor [N], head [1] i64 (rows ever appended; row i lives at index i % L) and
+        desync [1]."""
+        self._refuse_without_log("episode_log_views")
+        if self._log_views is None:
+            lp = _lib.CagymEpisodeLogPtrs()
+            _lib.call(self.L, self.h, "cagym_episode_log_get", C.byref(lp))
+            L = int(lp.capacity)
+            dims = {"L": (L,), "LM": (L, self.M), "N": (self.N,), "NM": (self.N, self.M), "1": (1,)}
+            v = {}
+            for name, ts, shape in _lib.EPLOG_FIELDS:
+                ts = {"u4": "i4", "u8": "i8"}.get(ts, ts)  # the bits, in the signed types torch computes with
+                v[name] = torch.as_tensor(_DevArray(getattr(lp, name), dims[shape], ts), device=self.device)
+            self._log_views = v
+        return dict(self._log_views)
+
+    def episode_log(self, last=None, sort=False, check=True):
+        """The valid rows in append order, oldest first, as device tensors (copies): the columns of episode_log_views() with key
+        as int64 in [0, 2^32), plus count (int32 ones) so that stats.suite_statistics(env.episode_log(last=K)) works on a window.
+        One synchronisation, to read head.  last=K: the newest K rows only; sort=True: ordered by (slice, world) instead;
+        check: raise RuntimeError when the log saw a skipped, doubled or non-auto-reset step (desync != 0)."""
+        v = self.episode_log_views()
+        L = self._log
+        head, d = torch.cat([v["head"], v["desync"].to(torch.int64)]).tolist()
+        if check and d:
+            raise RuntimeError("the episode log is out of step with the env in %d world-launches (desync): the recorder was "
+                               "fed a step twice, skipped one, or saw a step without auto-reset; attach_episode_log() "
+                               "again to clear" % d)
+        n = min(head, L)
+        if last is not None:
+            n = min(n, max(int(last), 0))
+        idx = (torch.arange(head - n, head, dtype=torch.int64, device=self.device) % L)
+        rows = {k: v[k].index_select(0, idx) for k, _, shape in _lib.EPLOG_FIELDS if shape in ("L", "LM")}
+        rows["key"] = rows["key"].to(torch.int64) & 0xFFFFFFFF
+        if sort and n:
+            order = torch.argsort(rows["slice"] * self.N + rows["world"].to(torch.int64), stable=True)
+            rows = {k: t.index_select(0, order) for k, t in rows.items()}
+        rows["count"] = torch.ones((n,), dtype=torch.int32, device=self.device)
+        return rows
+
     # ---- the split step: env.step() in two launches (include/cagym.h: cagym_step_begin / cagym_step_finish) ------------------
     def step_begin(self, stream=None):
         """First half of step(): the internal RVO policies' half-planes and linear programs on the current state (they do not
@@ -610,10 +699,7 @@ class BatchedCollisionAvoidanceEnv(object):
         self._records_contract(auto_reset, "step_finish")
         a = self._actions(actions)
         _lib.call(self.L, self.h, "cagym_step_finish", _lib.ptr(a), C.byref(self._out), int(bool(auto_reset)), self._stream())
-        if self._streaming and auto_reset:
-            self._refill()
-        if self._rec is not None:
-            self._records_update(self.flags, self.reward, self.game_over, 1)
+        self._after_steps(auto_reset, self.flags, self.reward, self.game_over, 1)
         return self._obs(), self.reward, self.game_over, {"flags": self.flags}
 
     def step_overlapped(self, policy, actions, auto_reset=False):
@@ -693,10 +779,8 @@ class BatchedCollisionAvoidanceEnv(object):
                 self._chained_step(None, o, auto_reset, restart, team_reward, prev)
             if oas is not None and T > 0:
                 self.obs_oas.copy_(oas[T - 1])
-        if self._streaming and auto_reset:  # one refill behind the last step, whichever chain ran
-            self._refill()
-        if self._rec is not None:  # one launch behind the last step, over all T slices
-            self._records_update(out["flags"], out["reward"], out["game_over"], T)
+        # one log update, one refill and one records update behind the last step, over all T slices, whichever chain ran
+        self._after_steps(auto_reset, out.get("flags"), out.get("reward"), out.get("game_over"), T)
         return caller_out
 
     def kernel_name(self, rollout=True, auto_reset=True):
@@ -782,6 +866,11 @@ class BatchedCollisionAvoidanceEnv(object):
         if self._streaming:
             raise RuntimeError("%s() on a streaming env: %s; stop_streaming() first" % (what, why))
 
+    def _refuse_with_log(self, what):
+        if self._log is not None:
+            raise RuntimeError("%s() with an episode log attached: its running rows would describe another timeline (the library "
+                               "refuses as long as the log is initialised)" % what)
+
     def _refuse_with_planner(self, what):
         if self._igm is not None:
             raise RuntimeError("%s() with %s attached: the planner's workspace, its published plans and the host-side call counter are "
@@ -794,6 +883,7 @@ class BatchedCollisionAvoidanceEnv(object):
         ig_mcts / ig_greedy planner is attached, while the env streams scenarios, and by the library while episode records are
         initialised."""
         self._refuse_with_planner("restore")
+        self._refuse_with_log("restore")
         self._refuse_streaming("restore", "the ring of scenario slots is not part of a snapshot (a restored episode index would meet "
                                "other scenarios)")
         valid = None
@@ -828,6 +918,7 @@ class BatchedCollisionAvoidanceEnv(object):
         scenarios, on handles with information-gain state and while episode records are initialised.  A pending step_begin is void
         afterwards."""
         self._refuse_with_planner("fork")
+        self._refuse_with_log("fork")
         self._refuse_streaming("fork", "the ring of scenario slots is not part of a snapshot, and a refill would overwrite the forked slot")
         s, hs = self._id_list(src, "fork(src)", check, self.N, distinct=False)
         d, hd = self._id_list(dst, "fork(dst)", check, self.N)

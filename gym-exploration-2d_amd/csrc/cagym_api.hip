@@ -27,6 +27,7 @@
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
 #include "cagym_episode_records.h"
+#include "cagym_episode_log.h"
 #include "cagym_snapshot.h"
 #include "cagym_stream.h"
 
@@ -61,6 +62,9 @@ struct Env {
     bool begun = false;  // cagym_step_begin was enqueued and no cagym_step_finish has consumed its velocities yet
     EpRec rec{};         // per-scenario episode records (cagym_episode_records_init allocates them)
     bool rec_ready = false;
+    EpLog elog{};        // append-only episode log (cagym_episode_log_init allocates it: the running block once, the ring per capacity)
+    bool log_ready = false;
+    void* elog_ring = nullptr;  // the ring's one allocation (EpLog's row columns are carved from it)
     int n_ig = 0;        // IG robots (active CAGYM_POL_IGMCTS slots) of every scenario of the pool; N_IG_UNEQUAL when the scenarios
                          // differ, N_IG_RANDOM when cagym_generate_scenarios may have drawn some (cagym_ig_robot_inputs / _actions)
     bool streaming = false;          // cagym_stream_scenarios started the ring and no pool setter or cagym_stream_stop ended it
@@ -270,6 +274,21 @@ inline int eprec_restart(Env* e, const uint8_t* world_mask, bool clear_table, hi
     hipLaunchKernelGGL(k_episode_records_restart, dim3(grid), dim3(256), 0, st, e->D, e->rec, world_mask, clear_table ? 1 : 0);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
+}
+
+// the episode log's restart / clear launch (csrc/cagym_episode_log.h); a no-op for handles that never initialised it
+inline int eplog_restart(Env* e, const uint8_t* world_mask, bool clear_rows, hipStream_t st) {
+    if (!e->log_ready) return CAGYM_OK;
+    const size_t rows = (size_t)std::max(e->cfg.n_worlds, clear_rows ? e->elog.capacity : 0) * e->cfg.max_agents;
+    const unsigned grid = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_episode_log_restart, dim3(grid), dim3(256), 0, st, e->D, e->elog, world_mask, clear_rows ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+// what a new pool means to both: the records describe the pool (cleared); the log is history (its rows stay, the running values go)
+inline int episodes_new_pool(Env* e, hipStream_t st) {
+    if (int rc = eprec_restart(e, nullptr, true, st)) return rc;
+    return eplog_restart(e, nullptr, false, st);
 }
 
 // ---- the field tables of csrc/cagym_snapshot.h ----------------------------------------------------------------------------------------
@@ -646,7 +665,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->scenarios_set = true;
     e->streaming = false;  // the pool is the caller's again
     e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
-    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
+    return episodes_new_pool(e, st);
 }
 
 // the handle's scenario pool as the generator kernels write it
@@ -705,7 +724,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     e->scenarios_set = true;
     e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
+    return episodes_new_pool(e, st);
 }
 
 // what a parameter set of the reference samplers implies for the handle (gen2_validate)
@@ -799,7 +818,7 @@ static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int
     e->scenarios_set = true;
     e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return eprec_restart(e, nullptr, true, st);  // the episode records describe the pool
+    return episodes_new_pool(e, st);
 }
 
 int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
@@ -925,6 +944,7 @@ int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const
                        advance_episode, o);
     HIPCHK(e, hipGetLastError());
     if (int rc = eprec_restart(e, world_mask, false, st)) return rc;  // an abandoned episode leaves no record
+    if (int rc = eplog_restart(e, world_mask, false, st)) return rc;  // ... and no row
     if (e->cfg.laserscan && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);
     return CAGYM_OK;
 }
@@ -1579,6 +1599,93 @@ int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out) {
     return CAGYM_OK;
 }
 
+// ---- append-only episode log (csrc/cagym_episode_log.h) -------------------------------------------------------------------------------
+int cagym_episode_log_init(void* env, int capacity, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_log_init");
+    if (capacity < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_init: capacity must be >= 1");
+    ON_DEVICE(e);
+    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
+    EpLog G = e->elog;
+    if (!G.t_run) {  // the running block: once per handle
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, 8 * (N * M + 2 * N + 2) + 4 * (4 * N + 2))) return rc;
+        G.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
+        G.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
+        G.pos = reinterpret_cast<unsigned long long*>(b); b += 8 * N;
+        G.seq = reinterpret_cast<unsigned long long*>(b); b += 8;
+        G.head = reinterpret_cast<unsigned long long*>(b); b += 8;
+        G.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
+        G.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.cnt = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.desync = reinterpret_cast<int32_t*>(b);
+        e->elog = G;  // kept whatever becomes of the ring's allocation
+    }
+    if (!e->elog_ring || G.capacity != capacity) {  // the ring: once per capacity (8-byte columns first, then 4-byte ones, then bytes)
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, L * (8 * (2 + 2 * M) + 4 * 7 + M))) return rc;
+        if (e->elog_ring) {  // the old ring: no launch may still use it
+            HIPCHK(e, hipDeviceSynchronize());
+            e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->elog_ring));
+            HIPCHK(e, hipFree(e->elog_ring));
+        }
+        e->elog_ring = b;
+        G.slice = reinterpret_cast<long long*>(b); b += 8 * L;
+        G.ret = reinterpret_cast<double*>(b); b += 8 * L;
+        G.t = reinterpret_cast<double*>(b); b += 8 * L * M;
+        G.extra_t = reinterpret_cast<double*>(b); b += 8 * L * M;
+        G.key = reinterpret_cast<uint32_t*>(b); b += 4 * L;
+        G.world = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.episode = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.steps = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.outcome = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.n_agents = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.n_obst = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.flags = b;
+        G.capacity = capacity;
+    }
+    e->elog = G;
+    e->log_ready = true;
+    return eplog_restart(e, nullptr, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_episode_log_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_log_update");
+    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_update before cagym_episode_log_init");
+    if (!flags || !reward || !game_over) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_update: flags, reward and game_over are required");
+    if (T < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_update: T must be >= 1");
+    ON_DEVICE(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int N = e->cfg.n_worlds, waves_per_wg = EPREC_NT / CAGYM_WAVE;
+    if (T > 1)  // (a one-slice update's counts are its game_over bytes: the scan reads them)
+        hipLaunchKernelGGL(k_episode_log_count, dim3((unsigned)((N + CAGYM_WAVE - 1) / CAGYM_WAVE)), dim3(CAGYM_WAVE * EPLOG_CNT_WAVES), 0, st, e->elog, N,
+                           game_over, T);
+    hipLaunchKernelGGL(k_episode_log_scan, dim3(1), dim3(EPLOG_NT_SCAN), 0, st, e->elog, N, T, T > 1 ? nullptr : game_over);
+    hipLaunchKernelGGL(k_episode_log_write, dim3((unsigned)((n_waves(e) + waves_per_wg - 1) / waves_per_wg)), dim3(EPREC_NT), 0, st, e->D, e->elog,
+                       flags, reward, game_over, T);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream) {
+    ENTRY_POOL(e, env, "cagym_episode_log_restart");
+    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_restart before cagym_episode_log_init");
+    ON_DEVICE(e);
+    return eplog_restart(e, world_mask, clear_rows != 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_episode_log_get(void* env, cagym_episode_log_ptrs* out) {
+    ENTRY_POOL(e, env, "cagym_episode_log_get");
+    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_get before cagym_episode_log_init");
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    const EpLog& G = e->elog;
+    out->key = G.key; out->world = G.world; out->episode = G.episode; out->slice = reinterpret_cast<const int64_t*>(G.slice); out->steps = G.steps;
+    out->ret = G.ret; out->outcome = G.outcome; out->n_agents = G.n_agents; out->n_obst = G.n_obst; out->t = G.t; out->extra_t = G.extra_t;
+    out->flags = G.flags; out->t_run = G.t_run; out->ret_run = G.ret_run; out->steps_run = G.steps_run; out->atgoal_run = G.atgoal_run;
+    out->cursor = G.cursor; out->head = reinterpret_cast<const uint64_t*>(G.head); out->desync = G.desync; out->capacity = G.capacity;
+    return CAGYM_OK;
+}
+
 // ---- per-world snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------------
 int cagym_snapshot_layout_of(void* env, cagym_snapshot_layout* out) {
     ENTRY(e, env);
@@ -1616,6 +1723,8 @@ int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* bl
     if (e->rec_ready)
         return fail(e, CAGYM_E_STATE, "cagym_restore with episode records initialised: their running rows would describe another timeline; "
                                       "detach the records first");
+    if (e->log_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_restore with an episode log initialised: its running rows would describe another timeline");
     ON_DEVICE_VOIDS_BEGUN(e);
     return snap_launch(e, snap_state_table(e, SNAP_SCATTER), rows, nullptr, const_cast<void*>(blob), n, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1628,6 +1737,8 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
     if (e->rec_ready)
         return fail(e, CAGYM_E_STATE, "cagym_fork with episode records initialised: their running rows would describe another timeline; "
                                       "detach the records first");
+    if (e->log_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_fork with an episode log initialised: its running rows would describe another timeline");
     if (e->cfg.n_scenarios % e->cfg.n_worlds != 0)
         return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork needs n_scenarios to be a multiple of n_worlds: otherwise two worlds can share a scenario "
                                             "slot and the copy of src's slot over dst's could hit a third world");

@@ -104,45 +104,62 @@ __device__ __forceinline__ int eprec_scenario(const CagymDev& D, int world, int 
     return (int)(((long long)world + (long long)cursor * D.N) % D.S);
 }
 
-// The end of an episode, called by EVERY lane of a wave in which some world's game_over fired (go: this lane's world did).
-// write: this episode owns the row (decided by the caller for the lanes with go).  Zeroes the running values, cursor += 1.
-__device__ __forceinline__ void eprec_finish(const CagymDev& D, const EpRec& E, const EpLane& L, EpRun& R, bool go, bool write, uint32_t f) {
-    const int M = D.M;
-    int s = 0, n = 0;
+// A finished episode's row as the lanes of its world hold it: the pool slot and its agent count, the outcome bits (every lane of
+// the world), and this lane's t / extra_t / flags byte (zeros at or above n).  Computing it and storing it are separate so that the
+// per-slot table here and the append-only log (cagym_episode_log.h) hold the same doubles.
+struct EpRow {
+    int s, n, outcome;
+    double t, extra;
+    uint8_t fb;
+};
+// Called by EVERY lane of a wave in which some world's game_over fired (go: this lane's world did).  full: this lane's t / extra_t
+// are wanted (the row will be stored); otherwise only s, n and the outcome bits are computed.
+__device__ __forceinline__ EpRow eprec_row(const CagymDev& D, const EpLane& L, const EpRun& R, bool go, bool full, uint32_t f) {
+    EpRow W{};
     if (go) {
-        s = eprec_scenario(D, L.world, R.cursor);
-        n = D.sc_nagents[s];
+        W.s = eprec_scenario(D, L.world, R.cursor);
+        W.n = D.sc_nagents[W.s];
     }
-    const bool active = go && L.slot < n;
+    const bool active = go && L.slot < W.n;
     const bool coll = (f & CAGYM_FLAG_IN_COLLISION) != 0, goal = (f & CAGYM_FLAG_AT_GOAL) != 0;
     const uint64_t b_coll = __ballot(active && coll) & L.wm;
     const uint64_t b_notgoal = __ballot(active && !goal) & L.wm;
     const uint64_t b_neither = __ballot(active && !coll && !goal) & L.wm;
-    if (!go) return;
-    if (write) {
-        const size_t k = (size_t)s * M + L.slot;
-        double t = 0.0, extra = 0.0;
-        uint8_t fb = 0;
-        if (active) {
-            const double* s6 = D.sc_agents6 + k * 6;
-            t = R.t;
-            extra = t - (norm2(s6[0] - s6[2], s6[1] - s6[3]) - 0.75) / s6[4];  // agent.py:59, as init_agent states it
-            fb = (uint8_t)f;
-        }
-        E.t[k] = t;
-        E.extra_t[k] = extra;
-        E.flags[k] = fb;
-        if (L.slot == 0) {
-            E.ret[s] = R.ret;
-            E.steps[s] = R.steps;
-            E.outcome[s] = (b_coll ? 1 : 0) | (b_notgoal ? 0 : 2) | (b_neither ? 4 : 0);
-        }
+    W.outcome = (b_coll ? 1 : 0) | (b_notgoal ? 0 : 2) | (b_neither ? 4 : 0);
+    if (active && full) {
+        const double* s6 = D.sc_agents6 + ((size_t)W.s * D.M + L.slot) * 6;
+        W.t = R.t;
+        W.extra = W.t - (norm2(s6[0] - s6[2], s6[1] - s6[3]) - 0.75) / s6[4];  // agent.py:59, as init_agent states it
+        W.fb = (uint8_t)f;
     }
+    return W;
+}
+// the running values of a world whose episode ended: zeroes, cursor += 1
+__device__ __forceinline__ void eprec_next(EpRun& R) {
     R.t = 0.0;
     R.ret = 0.0;
     R.steps = 0;
     R.atgoal = false;
     R.cursor += 1;
+}
+
+// The end of an episode, called by EVERY lane of a wave in which some world's game_over fired (go: this lane's world did).
+// write: this episode owns the row (decided by the caller for the lanes with go).  Zeroes the running values, cursor += 1.
+__device__ __forceinline__ void eprec_finish(const CagymDev& D, const EpRec& E, const EpLane& L, EpRun& R, bool go, bool write, uint32_t f) {
+    const EpRow W = eprec_row(D, L, R, go, write, f);
+    if (!go) return;
+    if (write) {
+        const size_t k = (size_t)W.s * D.M + L.slot;
+        E.t[k] = W.t;
+        E.extra_t[k] = W.extra;
+        E.flags[k] = W.fb;
+        if (L.slot == 0) {
+            E.ret[W.s] = R.ret;
+            E.steps[W.s] = R.steps;
+            E.outcome[W.s] = W.outcome;
+        }
+    }
+    eprec_next(R);
 }
 
 // After the last slice: the recorder's episode index and step count against the ones the step kernels keep.  A skipped, doubled

@@ -90,7 +90,9 @@ def suite_statistics(records, first=0, count=None, include=None):
       extra_time_pctls: the 50 / 75 / 90th percentiles (np.percentile's default, linear interpolation) of the per-case mean of
         extra_t over the case's active agents (slots < n_agents; every slot when the records carry no n_agents), taken over the
         rows of `include` (a [n_cases] bool mask, e.g. the intersection of several policies' clean rows; default: this
-        table's clean rows).  NaN when no row is included."""
+        table's clean rows).  NaN when no row is included.
+    A window of the append-only episode log works unchanged: BatchedCollisionAvoidanceEnv.episode_log(last=K) carries count (ones)
+    and n_agents per row, so every row is a case that ran (collision rate over the last K episodes)."""
     cnt = records["count"]
     S = int(cnt.shape[0])
     first = int(first)

@@ -96,7 +96,7 @@ class CagymVecEnv(object):
     def step_wait(self):
         b = self.b
         # DummyVecEnv auto-reset inside the launch; an attached GA3C policy or (episodic) ig_mcts team fills its agents' rows and
-        # restarts with its worlds (BatchedCollisionAvoidanceEnv.step)
+        # restarts with its worlds (BatchedCollisionAvoidanceEnv.step); attached episode records and the episode log are fed there too
         _, rew, go, info = b.step(self._external(self._actions), auto_reset=True)
         rews = rew[:, 0] if self.single_agent else rew
         infos = {"flags": info["flags"]}

@@ -519,6 +519,70 @@ int cagym_episode_records_update(void* env, const uint8_t* flags, const float* r
 int cagym_episode_records_restart(void* env, const uint8_t* world_mask, int clear_table, void* stream);
 int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out);
 
+/* ---- Append-only episode log under auto-reset, streamed pools included (csrc/cagym_episode_log.h) -----------------------------------
+ * The records table above has one row per pool slot, which a streamed pool reuses (cagym_stream_*): a streaming handle refuses it.
+ * The log is not keyed by slot: a device ring of `capacity` rows, ONE ROW PER FINISHED EPISODE, rebuilt from the same step outputs by
+ * launches of its own behind the auto-resetting step(s).  No step, reset, roll-out or refill kernel knows of it.
+ * Row columns (structure of arrays, L = capacity rows):
+ *   key [L] u32 = (uint32_t)(w + e * N), the stream key of the episode that ended (world w, episode index e); world, episode [L] i32;
+ *   slice [L] i64, the index of the slice that ended the episode counted over all update calls since init / clear;
+ *   steps [L] i32; ret [L] f64 (sum of agent 0's reward in step order); outcome [L] i32 (the records' bits: 1 any collision, 2 all at
+ *   goal, 4 any neither); n_agents, n_obst [L] i32 from the pool row of the episode's slot (w + e * N) % S (n_obst 0 without
+ *   rectangles); t, extra_t [L,M] f64 and flags [L,M] u8 as the records define them, zeros at slots >= n_agents.
+ *   t, extra_t, ret, steps, outcome and the masking are computed by the recorder's own device functions: log and table hold the same
+ *   doubles.  With constant stream parameters the scenario of (w, e) is a pure function of (params, w, e) (see cagym_stream_*), so a
+ *   logged episode is reproducible: generate a plain pool of more than `key` slots with the same arguments and read row `key`.
+ * Running, per world and the log's own (records and log may both be initialised on a fixed pool; they share no state): t_run [N,M]
+ *   f64, ret_run [N] f64, steps_run [N] i32, atgoal_run [N] u32, cursor [N] i32; desync, one i32 word with the recorder's meaning;
+ *   head, one u64 word: the number of rows ever appended since init / clear.
+ * ORDER (deterministic): the rows of one update are appended world-major - ascending world, inside a world ascending slice -;
+ *   updates append in call order; row number i (0-based, i < head) lives at ring index i % capacity.  An update that finishes
+ *   n > capacity episodes writes only its last `capacity` rows in that order, the others are skipped; head still grows by n.
+ *   Valid rows: the min(head, capacity) newest, oldest first from ring index head % capacity when head > capacity, else from 0.
+ * cagym_episode_log_init: allocate (the running values once, the ring once per capacity) and clear; a second call clears again and
+ *   may change the capacity (that synchronises the device and frees the old ring).
+ * cagym_episode_log_update: at most three launches (count per world, one exclusive scan over the N counts, write), chained by stream
+ *   order only.  Inputs and CONTRACT as cagym_episode_records_update: the outputs of auto-reset stepping only, every step exactly once
+ *   and in order, behind the step(s) that wrote them and before the next stepping call.  WHILE STREAMING ALSO BEFORE
+ *   cagym_stream_refill: the update reads the pool row of the slot of the episode that ended, and the next refill regenerates that
+ *   slot (it is the slot of episode e + n_scenarios / n_worlds).  For a world that lapped its ring inside a roll-out the row describes
+ *   the scenario that actually ran - the slot's content - while its key is still w + e * N; cagym_stream_get's n_lapped tells a caller
+ *   that this happened.  No argument advances on the host: the call can be captured in a graph with the steps.  desync as the
+ *   recorder's: after the last slice cursor / steps_run are compared with the handle's episode index and length.
+ * cagym_episode_log_restart: the masked worlds (DEVICE [N] u8, NULL = all) forget the episode in progress and take the handle's
+ *   episode index; clear_rows != 0 also zeroes every row, head, the slice counter and desync.
+ * cagym_episode_log_get: zero-copy DEVICE views, owned by the handle (the ring's views change when init changes the capacity).
+ * Once initialised: a successful cagym_reset enqueues the restart for its mask (an abandoned episode leaves no row); a successful
+ * cagym_set_scenarios / cagym_generate_scenarios / cagym_generate_reference_scenarios / cagym_stream_scenarios clears the running
+ * values and takes the handle's episode indices - the rows, head, the slice counter and desync stay: a log is history and every row is
+ * self-contained.  cagym_stream_scenarios and cagym_stream_set_params do not refuse a handle with a log.  cagym_restore and cagym_fork
+ * return CAGYM_E_STATE while a log is initialised (its running rows would describe another timeline, as the records' would);
+ * cagym_snapshot stays allowed.  Handles that never called init behave as before.
+ * Errors: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before a pool is installed, and for update / restart / get before init;
+ * CAGYM_E_INVALID for a NULL flags / reward / game_over / out, T < 1 or capacity < 1; CAGYM_E_DEVICE as every launching entry. */
+struct cagym_episode_log_ptrs {
+    const uint32_t* key;
+    const int32_t *world, *episode;
+    const int64_t* slice;
+    const int32_t* steps;
+    const double* ret;
+    const int32_t *outcome, *n_agents, *n_obst;
+    const double *t, *extra_t;
+    const uint8_t* flags;
+    const double *t_run, *ret_run;
+    const int32_t* steps_run;
+    const uint32_t* atgoal_run;
+    const int32_t* cursor;
+    const uint64_t* head;
+    const int32_t* desync;
+    int32_t capacity;
+};
+typedef struct cagym_episode_log_ptrs cagym_episode_log_ptrs;
+int cagym_episode_log_init(void* env, int capacity, void* stream);
+int cagym_episode_log_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream);
+int cagym_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream);
+int cagym_episode_log_get(void* env, cagym_episode_log_ptrs* out);
+
 /* ---- Per-world state snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------
  * The env can be put back where it was (checkpoint / resume, rewind) and a world can continue as a copy of another one (look-ahead:
  * "try these K actions from this state").  One copy kernel beside the step kernels; no step, reset or roll-out kernel knows of it.
@@ -551,7 +615,8 @@ int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out);
  * Errors, in this order: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before cagym_set_scenarios; CAGYM_E_INVALID for n < 0 or
  * n > N, a NULL blob or one that is not 16-byte aligned, NULL worlds with n != N, NULL src / dst with n > 0, a NULL layout or one
  * that differs from the handle's own in any field; CAGYM_E_STATE for restore / fork while episode records are initialised (their
- * running rows would describe another timeline: detach the records first); CAGYM_E_UNSUPPORTED for fork on a handle whose
+ * running rows would describe another timeline: detach the records first) and, for the same reason, while an episode log
+ * (cagym_episode_log_init) is initialised; CAGYM_E_UNSUPPORTED for fork on a handle whose
  * n_scenarios is not a multiple of n_worlds (two worlds can share a slot, the overwrite could hit a third) or after cagym_ig_init
  * (the per-slot distance field is not copied); CAGYM_E_DEVICE as every launching entry. */
 #define CAGYM_SNAP_MAGIC 0x43475331u /* "CGS1" */
