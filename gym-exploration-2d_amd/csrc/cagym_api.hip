@@ -130,7 +130,7 @@ int device_status(Env* e) {
     const int32_t code = e->status_host ? *reinterpret_cast<volatile int32_t*>(e->status_host) : 0;
     if (code == CAGYM_DEVERR_NONE) return CAGYM_OK;
     return fail(e, CAGYM_E_DEVICE, std::string("a kernel of an earlier launch gave up a bounded wait (") +
-                                       (code == CAGYM_DEVERR_LP_WAIT ? "LP waves" : code == CAGYM_DEVERR_LASER_WAIT ? "LaserScan passes" : "unknown") +
+                                       (code == CAGYM_DEVERR_LP_WAIT ? "LP waves" : code == CAGYM_DEVERR_LASER_WAIT ? "LaserScan passes" : code == CAGYM_DEVERR_PAIR_WAIT ? "pair phase" : "unknown") +
                                        "): results since then are void, destroy the handle");
 }
 

@@ -15,6 +15,14 @@
 //             pair lane also ranks its two half-planes into nearest-first order (the LP groups start from sorted lines)
 //   (rare)    a world was reset in S2: keys, distances, preferred velocities and half-planes are rebuilt in two extra phases
 //
+// The free-space roll-out kernels whose unordered pairs fit the lanes of waves 1.. in one pass (M = 10 with 4 worlds per workgroup,
+// M = 4) run phases A and B as ONE phase without the barrier between them (run_steps3: FUSED; pair_phase3, ego_phase3):
+//
+//   waves 1.. one lane per unordered pair: distances / collisions / keys AND orca_pair from the same registers, the wave arrives on
+//             an LDS counter, waits for the other pair waves' keys and wave 0's LP inputs, ranks and stores its two half-planes
+//   wave 0    preferred velocities + ego frames of all agent slots (one instruction stream), arrives on a second counter, waits
+//             for the pair waves' arrival, S2
+//
 // The step's top holds nothing but the busy list: each output slice is computed by its consumer (the row workers take the observation
 // pointers of step t-1, S2 indexes reward / flags / game_over of step t) and the issue priority of step t+1 (W.flag[4]) is read
 // behind barrier B together with the restart flag.
@@ -140,6 +148,7 @@ struct Lds3 {
     int* flag;     // [16] 0: a world was reset this step   1: OAS row chunks claimed   2: LP waves finished
                    //      3/4: some ego needed linearProgram3 this / the previous step   5/6: obstacle_lines_phase3's work list
                    //      7, 8, 10: LaserScan: slab-test passes claimed / finished, sampling rounds claimed
+                   //      11/12: fused pair phase: pair waves whose keys are stored / wave 0's LP inputs are stored
     float2* lpv;   // [AS] preferred (optimisation) velocity of each ego
     float2* lpc;   // [AS] pref velocity clipped to maxSpeed = LP start; LP result afterwards
     float* lpr;    // [AS] maxSpeed of the ego (LP radius)
@@ -726,6 +735,131 @@ __device__ __forceinline__ void half_planes3(const CagymDev& D, const Lds3& W, i
     }
 }
 
+// Wave 0's share of the fused pair phase for agent slot a: the next step's LP inputs (LP; publish_pref_velocity3's expressions and
+// stores) and Dynamics.update_ego_frame (dynamics/Dynamics.py:14-28) of an agent S1 moved, as ONE instruction stream.  Both start
+// from goal - position and each is a dependent fp64 chain (square root + division; square root, divisions, atan2): in one basic
+// block the scheduler interleaves them.  An agent that did not move computes its ego frame for nothing and keeps the old one.
+template <bool LP>
+__device__ __forceinline__ void ego_phase3(const Lds3& W, int a) {
+    const double px = W.tpx[a], py = W.tpy[a], tgx = W.tgx[a], tgy = W.tgy[a], h = W.th[a];
+    const bool mv = W.tmoved[a] != 0;
+    float ox = 0.f, oy = 0.f, radius = 0.f;
+    if (LP) {
+        const double gx = tgx - px, gy = tgy - py;
+        const double pref = W.tpref[a];
+        const double sc = pref / norm2(gx, gy);
+        ox = (float)(sc * gx); oy = (float)(sc * gy); radius = (float)pref;
+    }
+    Agent E;
+    E.px = px; E.py = py; E.gx = tgx; E.gy = tgy; E.h = h;
+    double prx, pry;
+    update_ego_frame(E, prx, pry);
+    if (LP) {
+        W.lpv[a] = make_float2(ox, oy);
+        W.lpr[a] = radius;
+        float cx = ox, cy = oy;
+        if (ox * ox + oy * oy > radius * radius) {
+            const float inv = 1.0f / sqrtf(ox * ox + oy * oy);
+            cx = ox * inv * radius;
+            cy = oy * inv * radius;
+        }
+        W.lpc[a] = make_float2(cx, cy);
+        W.busy[a] = 0;
+    }
+    if (mv) { W.tdg[a] = E.dg; W.the[a] = E.he; W.tprx[a] = prx; W.tpry[a] = pry; }
+}
+
+// ---- the fused pair phase (free-space roll-out kernels whose unordered pairs fit the lanes of waves 1.. in one pass) -----------
+// Phase A's and phase B's pair lanes are the same lanes here: lane `p` of waves 1.. does pair_distances3<MT, true, true> of its pair
+// and, from the same eight doubles in registers, orca_pair - it needs the moved state alone -, its wave arrives on the counter
+// W.flag[11] ("P"), and only then the lane waits: for every pair wave (a half-plane is ranked in the ego's whole row of
+// W.dsq) and for wave 0's arrival on W.flag[12] ("Q": W.lpc / W.busy of ego_lp_inputs3).  Behind the wait stands what is left of
+// half_planes3.  The expressions are pair_distances3's and half_planes3's (a sum, a difference's square and the pair's distance
+// do not depend on which agent is named first: the lane reads agents a / b once, not lo / hi and a / b).
+// has: the lane holds a pair (p < nup); PLANES: half-planes are wanted (any_rvo && more).  Every lane of the wave calls it - the
+// arrival and the waits are per wave - exactly once per step.
+template <int MT, bool PLANES>
+__device__ __forceinline__ void pair_phase3(const CagymDev& D, const Lds3& W, int p, bool has, int M, int MP, int AS, int pair_waves, int t) {
+    UPair q = {0, 0, 0};
+    int a = 0, b = 0;
+    bool both = false;
+    bool on_a = false, on_b = false;
+    OrcaPair g = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float vax = 0.f, vay = 0.f, vbx = 0.f, vby = 0.f, ca = 0.f, cb = 0.f;
+    if (has) {
+        q = upair_of<MT>(p, M);
+        const int n = W.wn[q.wl];
+        a = q.wl * M + q.i;
+        b = q.wl * M + q.j;
+        both = q.i < n && q.j < n;
+        const int lo = q.i < q.j ? a : b, hi = q.i < q.j ? b : a;
+        double kab = -INFINITY, kba = -INFINITY, gp = INFINITY;
+        float dq = INFINITY;
+        uint8_t ht = 0;
+        if (both) {
+            // everything the lane reads of the moved state in one batch of LDS loads (each dependent round trip is ~130 cycles of
+            // the step's chain): the half-plane part's inputs ride along with the distance part's
+            const double pax = W.tpx[a], pay = W.tpy[a], pbx = W.tpx[b], pby = W.tpy[b];
+            const double ra = W.tr[a], rb = W.tr[b];
+            const uint32_t st_hi = W.tst[hi];
+            double dvax = 0., dvay = 0., dvbx = 0., dvby = 0.;
+            if (PLANES) {
+                dvax = W.tvx[a]; dvay = W.tvy[a]; dvbx = W.tvx[b]; dvby = W.tvy[b];
+                on_a = W.trvo[a] != 0;
+                on_b = W.trvo[b] != 0;
+                ca = W.tcoop[a];
+                cb = W.tcoop[b];
+            }
+            const double dx = pbx - pax, dy = pby - pay;
+            const double d = norm2(dx, dy);
+            const bool skip = ST_POLICY(st_hi) == CAGYM_POL_STATIC && !D.collide_static;  // env.py:643 (Q8)
+            const double cr = ra + rb;
+            ht = (!skip && d <= cr) ? 1 : 0;
+            if (!skip) gp = d - cr;  // lower index only (Q7)
+            kab = d - ra - rb;
+            kba = d - rb - ra;
+            const float rpx = (float)pbx - (float)pax, rpy = (float)pby - (float)pay;
+            dq = rpx * rpx + rpy * rpy;
+            if (PLANES) {
+                // behind the fp64 distance in program order, so that its square root shares a basic block with orca_pair's head.  A
+                // pair without a live RVO ego computes its half-planes for nothing (its wave does anyway) and never stores them.
+                vax = (float)dvax; vay = (float)dvay; vbx = (float)dvbx; vby = (float)dvby;
+                g = orca_pair((float)pax, (float)pay, vax, vay, (float)((1 + 15e-2) * ra), (float)D.dt, pbx, pby, dvbx, dvby, rb);
+            }
+        }
+        W.hit[a * MP + q.j] = ht;
+        W.hit[b * MP + q.i] = ht;
+        if (gp < INFINITY) atomicMin(&W.gmin[lo], gap_key(gp));
+        W.keys[a * MP + q.j] = kab;
+        W.keys[b * MP + q.i] = kba;
+        W.dsq[a * MP + q.j] = make_uint2((uint32_t)q.j, __float_as_uint(dq));
+        W.dsq[b * MP + q.i] = make_uint2((uint32_t)q.i, __float_as_uint(dq));
+    }
+    // the wave's keys, collision bits and gaps are out (LDS operations of one wave complete in order, the release keeps the order)
+    if ((threadIdx.x & (CAGYM_WAVE - 1)) == 0) __hip_atomic_fetch_add(&W.flag[11], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    WAVETRACE(t, 8);
+    if (!PLANES) return;
+    PMARK("hp_pair_done");
+    // every pair wave's keys and wave 0's LP inputs (each arrives exactly once per step; bounded all the same, cagym_spin.h)
+    if (!lds_wait_ge(&W.flag[11], pair_waves) || !lds_wait_ge(&W.flag[12], 1)) *D.dev_status = CAGYM_DEVERR_PAIR_WAIT;
+    WAVETRACE(t, 9);
+    // (one ego after the other: both key rows in flight at once cost the headline kernel 13 VGPRs and 12 bytes of scratch)
+    if (on_a) {
+        const float4 ln = make_float4(vax + ca * g.ux, vay + ca * g.uy, g.zx, g.zy);
+        const float2 s0 = W.lpc[a];
+        if (detf(ln.z, ln.w, ln.x - s0.x, ln.y - s0.y) > 0.0f) W.busy[a] = 1;
+        const int rank = neighbour_rank3<MT>(W, a, q.j, g.d2, MP);
+        if (rank < D.maxnb) W.sorted[rank * AS + a] = ln;
+    }
+    if (on_b) {
+        const float4 ln = make_float4(vbx - cb * g.ux, vby - cb * g.uy, -g.zx, -g.zy);
+        const float2 s0 = W.lpc[b];
+        if (detf(ln.z, ln.w, ln.x - s0.x, ln.y - s0.y) > 0.0f) W.busy[b] = 1;
+        const int rank = neighbour_rank3<MT>(W, b, q.i, g.d2, MP);
+        if (rank < D.maxnb) W.sorted[rank * AS + b] = ln;
+    }
+}
+
 // ---- one 64-row chunk of the OtherAgentsStates table (sensors/OtherAgentsStatesSensor.py:11-77), straight to HBM ----------
 __device__ __forceinline__ void oas_row3(const Lds3& W, float* oas_out, int p, int npairs, int M, int MP, int K, int wpw,
                                          int worlds_valid, uint32_t inv_m) {
@@ -1050,6 +1184,11 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
     const int AS = cagym_as(M, WPWT);
     const int ko = OBST ? D.ko : 0;  // 2 * Kobs: an agent outside a rectangle sees at most 2 of its edges from their right side
     constexpr int LPL = cagym_lpl3(MT, OBST);
+    // the fused pair phase (pair_phase3): free-space roll-out kernels whose unordered pairs fit the lanes of waves 1.. in one pass
+    // (M = 10 with 4 worlds per workgroup: 180 <= 192; M = 4: 96).  Everything else - a second pass or wave 0's tail round
+    // (M = 10 with 5 worlds, M = 20), run-time M, the OBST and the one-step kernels - keeps phases A and B as they are.
+    constexpr int WPWC = WPWT ? WPWT : (MT > 0 ? CAGYM_WAVE / MT : 0);
+    constexpr bool FUSED = !OBST && !ONE && !POST && MT > 0 && NT > CAGYM_WAVE && WPWC * (MT * (MT - 1) / 2) <= NT - CAGYM_WAVE;
     constexpr bool OVL = ONE && OBST && !POST;  // the one-step launch among rectangles: early and late arrays share LDS bytes (carve_lds3_ovl)
     const Lds3 W = POST ? carve_lds3_post(smem, M, AS, ko / 2) : OVL ? carve_lds3_ovl(smem, M, AS, NT, ko) : carve_lds3(smem, M, AS, NT, ko, LPL, OBST, MT);
     // the neighbour keys live in the LP scratch (a one-step launch builds no half-planes for a next step: no keys after its prologue)
@@ -1306,11 +1445,37 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
             }
         }
         if (tid == NT - 1) { W.flag[1] = 0; W.flag[2] = 0; W.flag[4] = W.flag[3]; W.flag[3] = 0; W.flag[7] = 0; W.flag[8] = 0; W.flag[9] = 0; W.flag[10] = 0; }
+        if (FUSED && tid == NT - 1) { W.flag[11] = 0; W.flag[12] = 0; }
         __syncthreads();
         WGTRACE1(26);
         STAMP(4);
         WAVETRACE(t, 6);
         PMARK("A_begin");
+        if constexpr (FUSED) {
+            const bool more = t + 1 < n_steps;
+            // ---- the fused pair phase: no barrier between the pair distances and the half-planes.  Waves 1..: pair_phase3, one lane
+            //      per unordered pair.  Wave 0: the next step's LP inputs (the pair lanes wait for them on W.flag[12]), then
+            //      Dynamics.update_ego_frame of the moved agents - neither needs anything from the pairs - and, once every pair wave
+            //      has arrived on W.flag[11], S2 below ------------------------------------------------------------------------
+            if (wave == 0) {
+                // (a world that S2 restarts afterwards gets its ego frame from init_agent, which overwrites this one)
+                if (agent_lane) {
+                    if (any_rvo && more) ego_phase3<true>(W, tid);
+                    else ego_phase3<false>(W, tid);
+                }
+                if (dsq_shared && agent_lane) {  // the key rows share their bytes with the LP scratch: own slot and padding again
+                    W.dsq[tid * MP + C.slot] = make_uint2((uint32_t)C.slot, 0x7f800000u);
+                    for (int l = M; l < MP; l++) W.dsq[tid * MP + l] = make_uint2((uint32_t)l, 0x7f800000u);
+                }
+                if (tid == 0) __hip_atomic_fetch_add(&W.flag[12], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                WAVETRACE(t, 7);
+                if (!lds_wait_ge(&W.flag[11], NWAVES - 1)) *D.dev_status = CAGYM_DEVERR_PAIR_WAIT;
+                WAVETRACE(t, 9);
+            } else {
+                if (any_rvo && more) pair_phase3<MT, true>(D, W, tid - CAGYM_WAVE, tid - CAGYM_WAVE < nup, M, MP, AS, NWAVES - 1, t);
+                else pair_phase3<MT, false>(D, W, tid - CAGYM_WAVE, tid - CAGYM_WAVE < nup, M, MP, AS, NWAVES - 1, t);
+            }
+        } else {
         // ---- phase A: pair distances, collision tests, OAS sort keys, fp32 squared distances; the last wave first prepares
         //      the next step's LP inputs (Dynamics.update_ego_frame waits for phase B: nothing before the rows needs it) -------
         if (tid >= NT - CAGYM_WAVE) {
@@ -1334,12 +1499,14 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         WGTRACE1(41);
         if (obst_lines) obstacle_lines_phase3(D, W, M, AS, ko, nagents, inv_m);
         __syncthreads();
+        WAVETRACE(t, 9);
+        }
         WGTRACE1(27);
         STAMP(5);
-        WAVETRACE(t, 9);
         PMARK("B_begin");
         // ---- phase B: wave 0 = S2 (_compute_rewards env.py:502-567, _check_which_agents_done :711-738, auto-reset);
-        //      waves 1.. = ORCA half-planes of step t+1 (wave 0 takes the pairs beyond their lanes afterwards) ----------------
+        //      waves 1.. = ORCA half-planes of step t+1 (wave 0 takes the pairs beyond their lanes afterwards).  In the fused pair
+        //      phase only S2 is left of it: the pair lanes are past their half-planes or still in pair_phase3 ------------------
         const bool more = t + 1 < n_steps;
         const int full_pairs = nup - nup % (NT - CAGYM_WAVE), tail_pairs = nup - full_pairs;
         if (wave == 0) {
@@ -1428,9 +1595,10 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
                 W.tst[tid] = S.st;
                 if (tid == 0) W.flag[0] = any_reset ? 1 : 0;
                 // Dynamics.update_ego_frame (dynamics/Dynamics.py:14-28) of the agents S1 moved: only the observation rows
-                // and the next S1 read it, and wave 0 is otherwise idle here until the half-plane lanes are done.  A world
+                // and the next S1 read it, so it waited for this phase.  (Wave 0 is no longer idle behind S2: with it, wave 0 is the
+                // last to reach barrier B - profiles/r7/wave_trace_new.txt - and the fused pair phase runs it ahead of S2.)  A world
                 // that was just reset got its ego frame from init_agent.
-                if (W.tmoved[tid] && !(AUTO_RESET && C.valid && go)) {
+                if (!FUSED && W.tmoved[tid] && !(AUTO_RESET && C.valid && go)) {
                     Agent E;
                     E.px = W.tpx[tid]; E.py = W.tpy[tid]; E.gx = W.tgx[tid]; E.gy = W.tgy[tid]; E.h = W.th[tid];
                     double prx, pry;
@@ -1440,8 +1608,8 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
             }
             PMARK("B_s2_end");
             // a last partial round of at most one wave of pairs is wave 0's (it is done with S2 before the others finish)
-            if (any_rvo && more && tail_pairs <= CAGYM_WAVE && tid < tail_pairs) half_planes3<MT>(D, W, full_pairs + tid, M, MP, AS, ko);
-        } else if (any_rvo && more) {
+            if (!FUSED && any_rvo && more && tail_pairs <= CAGYM_WAVE && tid < tail_pairs) half_planes3<MT>(D, W, full_pairs + tid, M, MP, AS, ko);
+        } else if (!FUSED && any_rvo && more) {
             const int lim = tail_pairs <= CAGYM_WAVE ? full_pairs : nup;
             PMARK("B_hp_begin");
             for (int p = tid - CAGYM_WAVE; p < lim; p += NT - CAGYM_WAVE) half_planes3<MT>(D, W, p, M, MP, AS, ko);

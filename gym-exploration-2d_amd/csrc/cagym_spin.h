@@ -22,7 +22,7 @@
 // three orders of magnitude above the longest legitimate wait (one LaserScan pass or one round of linear programs: microseconds)
 #define CAGYM_SPIN_LIMIT (1u << 20)
 
-enum { CAGYM_DEVERR_NONE = 0, CAGYM_DEVERR_LP_WAIT = 1, CAGYM_DEVERR_LASER_WAIT = 2 };
+enum { CAGYM_DEVERR_NONE = 0, CAGYM_DEVERR_LP_WAIT = 1, CAGYM_DEVERR_LASER_WAIT = 2, CAGYM_DEVERR_PAIR_WAIT = 3 };
 
 // true when load() >= target was seen within `limit` polls (the condition is tested once more after the last pause)
 template <typename Load, typename Pause>

@@ -39,8 +39,12 @@ for rep in range(12):
     env.rollout(40, out=traj)
 A = np.concatenate(acc)  # [steps, points, waves] ticks since the first wave entered the step
 names = ["step top", "busy list built", "own LP groups done", "wave 0: all LP waves done", "S1 done (w0) / rows done (others)", "after barrier X",
-         "after publish + barrier Y", "last wave: ego frame + LP inputs done", "pair distances done", "after barrier A",
+         "after publish + barrier Y", "last wave: LP inputs done", "pair distances done", "after barrier A",
          "S2 done (w0) / half-planes done (others)", "after barrier B", "step end", "LP: lines ranked, own lines loaded", "LP: first program (linearProgram2) done", "S1: action chosen (orca_post)"]
+if os.environ.get("WT_FUSED", "1") != "0" and not os.environ.get("LC_OBST"):  # the fused pair phase (free space, M = 10, 4 worlds per workgroup; WT_FUSED=0: a library from before it): points 7 - 9 mean something else
+    names[7] = "w0: LP inputs + ego frames stored (Q)"
+    names[8] = "pairs: keys stored, orca_pair done (P)"
+    names[9] = "w0: pair waves seen (P) / pairs: P and Q seen"
 print("%d worlds, workgroup 7, median over %d steps; ticks since the step's first wave started (0 = point not reached by that wave)" % (N, A.shape[0]))
 print("%-46s %9s %9s %9s %9s" % ("point", "wave 0", "wave 1", "wave 2", "wave 3"))
 for k, n in enumerate(names):
