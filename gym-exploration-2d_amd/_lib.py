@@ -53,6 +53,13 @@ class CagymGen2Params(C.Structure):
                 ("max_tries", C.c_int32), ("p_b", C.c_double)]
 
 
+class CagymExploreParams(C.Structure):
+    """cagym_explore_params (include/cagym.h)."""
+    _fields_ = [("seed", C.c_uint64), ("kinds_mask", C.c_uint32), ("n_robots", C.c_int32), ("n_targets", C.c_int32),
+                ("n_obst_min", C.c_int32), ("n_obst_max", C.c_int32), ("max_tries", C.c_int32), ("target_radius", C.c_double),
+                ("robot_pref_speed", C.c_double)]
+
+
 class CagymScenarioPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("agents6", "policy", "dynamics", "n_agents", "coop")]
 
@@ -171,6 +178,10 @@ _ARGTYPES = {
     "cagym_stream_set_params": [_vp, _P(CagymGen2Params)],
     "cagym_stream_get": [_vp, _P(CagymStreamPtrs)],
     "cagym_stream_stop": [_vp],
+    "cagym_generate_exploration_scenarios": [_vp, _P(CagymExploreParams), _P(C.c_int32), _vp],
+    "cagym_stream_exploration_scenarios": [_vp, _P(CagymExploreParams), _P(C.c_int32), _vp],
+    "cagym_stream_set_exploration_params": [_vp, _P(CagymExploreParams)],
+    "cagym_explore_stream_get": [_vp, _P(_vp), _P(_vp)],
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],

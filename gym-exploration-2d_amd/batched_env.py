@@ -120,6 +120,7 @@ class BatchedCollisionAvoidanceEnv(object):
         self._log_views = None
         self._streaming = False   # stream_reference_scenarios: one cagym_stream_refill behind every episode-advancing call
         self._stream_views = None
+        self._explore_views = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
@@ -328,6 +329,76 @@ class BatchedCollisionAvoidanceEnv(object):
         """Zero-copy device view of next_episode [N] i32: the first episode of each world whose slot has not been generated."""
         self.stream_stats()
         return self._stream_views["next_episode"]
+
+    # ---- exploration worlds (include/cagym.h: cagym_generate_exploration_scenarios, cagym_stream_exploration_*) -----------------
+    def _explore_params(self, kinds, seed, n_robots, n_targets, n_obst, target_radius, robot_pref_speed, max_tries):
+        ks = [kinds] if isinstance(kinds, (str, int, np.integer)) else list(kinds)
+        mask = 0
+        for k in ks:
+            mask |= 1 << sc.sampler_kind(k)
+        lo, hi = (-1, -1) if n_obst is None else (n_obst, n_obst) if np.isscalar(n_obst) else n_obst
+        return _lib.CagymExploreParams(int(seed), mask, int(n_robots), int(n_targets), int(lo), int(hi), int(max_tries),
+                                       float(target_radius), float(robot_pref_speed))
+
+    def _explore_pool(self, n_robots, streaming):
+        """Host state after an exploration pool was committed: the team size is known, and an attached team of that size stays."""
+        self._streaming = streaming
+        self._pool_policies = {sc.POLICY_IGMCTS, sc.POLICY_STATIC}
+        self._n_ig = int(n_robots)
+        if self._igm is not None and self._n_ig != self._igm.R:  # the attached planner was sized for another team
+            self.detach_ig_mcts()
+        if self._igm is not None:  # as set_scenarios: fresh beliefs on the new rasters' fields (on a stream it arms the refresh)
+            _lib.call(self.L, self.h, "cagym_ig_init", self._stream())
+
+    def generate_exploration_worlds(self, kinds, seed, n_robots, n_targets, n_obst=None, target_radius=0.2, robot_pref_speed=1.0,
+                                    max_tries=1000):
+        """Fill the scenario pool ON DEVICE with exploration worlds (cagym_generate_exploration_scenarios): n_robots IG robots
+        (slots 0..n_robots-1, FirstOrder) and n_targets static targets of radius target_radius among the rectangles of
+        kinds = "train_stage_1" and / or "train_stage_2" (names or scenarios.GEN_* ids); starts, goals and rectangles are the
+        stage samplers' own draws for number_of_agents = n_robots + n_targets.  n_obst and max_tries: as
+        generate_reference_scenarios.  robot_pref_speed only sets the robots' time limit.  The team size is known afterwards:
+        attach_ig_mcts() / attach_ig_greedy() work on the generated pool.  Returns n_failed."""
+        P = self._explore_params(kinds, seed, n_robots, n_targets, n_obst, target_radius, robot_pref_speed, max_tries)
+        nf = C.c_int32(0)
+        _lib.call(self.L, self.h, "cagym_generate_exploration_scenarios", C.byref(P), C.byref(nf), self._stream())
+        self._explore_pool(n_robots, False)
+        return int(nf.value)
+
+    def stream_exploration_worlds(self, kinds, seed, n_robots, n_targets, n_obst=None, target_radius=0.2, robot_pref_speed=1.0,
+                                  max_tries=1000):
+        """generate_exploration_worlds (same arguments, same pool), and from now on the pool is stream_reference_scenarios' ring:
+        world w's episode e runs on the world of key w + e * N, refilled behind every episode-advancing call.  With an IG team
+        attached (before or after this call) the same refill rebuilds the distance field of every slot it regenerated, so
+        attach_ig_mcts(episodic=True) / attach_ig_greedy(episodic=True) run under auto-reset, rollout() and CagymVecEnv on worlds
+        that never repeat; the default attach keeps refusing auto-reset.  Needs n_scenarios % n_worlds == 0 and >= 2 * n_worlds;
+        restore(), fork() and attach_episode_records() raise while it runs.  Returns n_failed."""
+        P = self._explore_params(kinds, seed, n_robots, n_targets, n_obst, target_radius, robot_pref_speed, max_tries)
+        nf = C.c_int32(0)
+        _lib.call(self.L, self.h, "cagym_stream_exploration_scenarios", C.byref(P), C.byref(nf), self._stream())
+        self._explore_pool(n_robots, True)
+        return int(nf.value)
+
+    def set_exploration_stream_params(self, kinds, seed, n_robots, n_targets, n_obst=None, target_radius=0.2, robot_pref_speed=1.0,
+                                      max_tries=1000):
+        """The curriculum switch of an exploration stream (set_stream_params' counterpart): later refills generate from these
+        arguments; worlds already in the ring stay.  n_robots must be the stream's."""
+        P = self._explore_params(kinds, seed, n_robots, n_targets, n_obst, target_radius, robot_pref_speed, max_tries)
+        _lib.call(self.L, self.h, "cagym_stream_set_exploration_params", C.byref(P))
+
+    def exploration_stream_stats(self):
+        """Host integers of the exploration stream's field refresh (this synchronises): fields_built (distance fields rebuilt
+        behind refills since the stream started), depth."""
+        if self._explore_views is None:
+            fn, fb = C.c_void_p(), C.c_void_p()
+            _lib.call(self.L, self.h, "cagym_explore_stream_get", C.byref(fn), C.byref(fb))
+            self._explore_views = {"field_next": torch.as_tensor(_DevArray(fn.value, (self.N,), "i4"), device=self.device),
+                                   "fields_built": torch.as_tensor(_DevArray(fb.value, (1,), "i8"), device=self.device)}
+        return {"fields_built": int(self._explore_views["fields_built"].item()), "depth": self.S // self.N}
+
+    def exploration_field_next(self):
+        """Zero-copy device view of field_next [N] i32: the first episode of each world whose slot's field has not been rebuilt."""
+        self.exploration_stream_stats()
+        return self._explore_views["field_next"]
 
     def _refill(self):
         rc = self._refill_fn(self.h, self._stream())

@@ -5,7 +5,7 @@ SONAME libamdhip64.so.7) so that torch streams and device pointers are valid ins
 
 Translation units (compiled in parallel, objects cached under csrc/build/ by source + flag hash):
   cagym_api.hip                      the C ABI and every kernel it launches itself: generation 1 + reset (cagym_gen1.h), laserscan /
-                                     occupancy grid / raster (cagym_sensors.h), generators, scenario stream, GA3C, IG, Dec-MCTS (HEADERS)
+                                     occupancy grid / raster (cagym_sensors.h), generators, scenario streams, GA3C, IG, Dec-MCTS (HEADERS)
   cagym_k3_tu.hip x 12               one per generation-3 specialisation (cagym_launch3.h: CAGYM_K3_SPECS x OBST); they see
                                      K3_HEADERS only
 """
@@ -25,7 +25,8 @@ LIB = os.path.join(CSRC, "libcagym_hip.so")
 K3_HEADERS = ["cagym_device.h", "cagym_trace.h", "cagym_spin.h", "cagym_orca.h", "cagym_kernels3.h", "cagym_split3.h", "cagym_launch3.h",
               "../../include/cagym.h"]
 HEADERS = K3_HEADERS + ["cagym_gen1.h", "cagym_sensors.h", "cagym_ig.h", "cagym_ga3c_state.h", "cagym_ga3c.h", "cagym_ga3c16.h", "cagym_gen.h", "cagym_gen2.h",
-                        "cagym_dmcts.h", "cagym_ig_episode.h", "cagym_ig_greedy.h", "cagym_episode_records.h", "cagym_episode_log.h", "cagym_snapshot.h", "cagym_stream.h"]
+                        "cagym_dmcts.h", "cagym_ig_episode.h", "cagym_ig_greedy.h", "cagym_episode_records.h", "cagym_episode_log.h", "cagym_snapshot.h", "cagym_stream.h",
+                        "cagym_explore.h"]
 
 
 def _k3_specs():

@@ -30,6 +30,7 @@
 #include "cagym_episode_log.h"
 #include "cagym_snapshot.h"
 #include "cagym_stream.h"
+#include "cagym_explore.h"
 
 namespace {
 
@@ -70,6 +71,9 @@ struct Env {
     bool streaming = false;          // cagym_stream_scenarios started the ring and no pool setter or cagym_stream_stop ended it
     StreamDev stream{};              // its device words (allocated by the first cagym_stream_scenarios; csrc/cagym_stream.h)
     cagym_gen2_params stream_P{};    // the parameter set cagym_stream_refill generates with (cagym_stream_set_params replaces it)
+    bool explore_stream = false;     // while streaming: cagym_stream_exploration_scenarios started the ring (csrc/cagym_explore.h)
+    ExploreTeam stream_team{};       // its team edit (cagym_stream_set_exploration_params replaces it together with stream_P)
+    ExploreDev explore{};            // the field refresh's device words (allocated by the first cagym_stream_exploration_scenarios)
 };
 enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
@@ -794,11 +798,16 @@ static Gen2Dev gen2_dev(const Env* e) {
 
 // every slot of the pool from the samplers (slot r from stream key r), its rasters, and the handle state a new pool commits;
 // d_failed: the device word the rejection loops report into (zeroed by the caller)
-static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int32_t* d_failed, int32_t* n_failed_host, hipStream_t st) {
+// team: NULL, or the team edit of an exploration pool (k_generate_exploration_scenarios; every slot then holds team->R IG robots)
+static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int32_t* d_failed, int32_t* n_failed_host, hipStream_t st,
+                     const ExploreTeam* team = nullptr) {
     CagymDev& D = e->D;
     const int K = e->cfg.max_obstacles;
     const Gen2Dev G = gen2_dev(e);
-    hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
+    if (team)
+        hipLaunchKernelGGL(k_generate_exploration_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, *team, d_failed);
+    else
+        hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
     HIPCHK(e, hipGetLastError());
     if (K > 0) {
         hipLaunchKernelGGL(k_rasterize, dim3((unsigned)G.G.S), dim3(256), 0, st, e->sc_obst, D.sc_nobst, K,
@@ -812,7 +821,7 @@ static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int
     }
     D.sc_heading0 = nullptr;  // toward the goal (agent.py:29-31)
     e->any_rvo = F.any_rvo ? 1 : 0;
-    e->n_ig = F.any_ig ? N_IG_RANDOM : 0;
+    e->n_ig = team ? team->R : F.any_ig ? N_IG_RANDOM : 0;
     e->obst_rvo = F.obst_rvo ? 1 : 0;
     e->D.ko = F.obst_rvo ? 2 * K : 0;
     e->scenarios_set = true;
@@ -834,6 +843,7 @@ int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* param
 
 // ---- streamed scenarios (csrc/cagym_stream.h) -------------------------------------------------------------------------------------------
 // what cagym_stream_scenarios and cagym_stream_set_params refuse beyond the generator's own checks
+enum { EXPLORE_COLS_GRID = 256, EXPLORE_ROWS_GRID = 2048 };  // the field refresh's fixed grids (cagym_stream_refill)
 static int stream_check(Env* e, const char* what, const cagym_gen2_params* params, Gen2Flags& F) {
     if (int rc = gen2_validate(e, params, F)) return rc;
     const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
@@ -874,11 +884,14 @@ int cagym_stream_scenarios(void* env, const cagym_gen2_params* params, int32_t* 
     if (int rc = gen2_fill(e, *params, F, T.n_failed, n_failed_host, st)) return rc;
     e->stream_P = *params;
     e->streaming = true;
+    e->explore_stream = false;
     return CAGYM_OK;
 }
 
 int cagym_stream_set_params(void* env, const cagym_gen2_params* params) {
     ENTRY_IF(e, env, e->streaming, "cagym_stream_set_params on a handle that is not streaming");
+    if (e->explore_stream)
+        return fail(e, CAGYM_E_UNSUPPORTED, "cagym_stream_set_params on an exploration stream: its switch is cagym_stream_set_exploration_params");
     Gen2Flags F;
     if (int rc = stream_check(e, "cagym_stream_set_params", params, F)) return rc;
     // slots of both parameter sets are in the ring from now on: the handle's flags cover both
@@ -895,7 +908,17 @@ int cagym_stream_refill(void* env, void* stream) {
     ENTRY_IF(e, env, e->streaming, "cagym_stream_refill on a handle that is not streaming");
     ON_DEVICE(e);
     const unsigned grid = (unsigned)((e->cfg.n_worlds + CAGYM_WAVE - 1) / CAGYM_WAVE);
-    hipLaunchKernelGGL(k_stream_refill, dim3(grid), dim3(CAGYM_WAVE), 0, reinterpret_cast<hipStream_t>(stream), gen2_dev(e), e->stream_P, e->stream);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (e->explore_stream) {  // 1 launch, or 4 once cagym_ig_init ran: the refill, then the field refresh's list, columns, rows
+        hipLaunchKernelGGL(k_explore_refill, dim3(grid), dim3(CAGYM_WAVE), 0, st, gen2_dev(e), e->stream_P, e->stream_team, e->stream, e->explore.n_list);
+        if (e->ig_ready) {
+            hipLaunchKernelGGL(k_explore_field_list, dim3(grid), dim3(CAGYM_WAVE), 0, st, e->stream, e->explore, e->cfg.n_scenarios);
+            hipLaunchKernelGGL(k_explore_field_cols, dim3(EXPLORE_COLS_GRID), dim3(320), 0, st, e->G, e->explore, e->ig_any);
+            hipLaunchKernelGGL(k_explore_field_rows, dim3(EXPLORE_ROWS_GRID), dim3(320), 0, st, e->G, e->explore, e->ig_any);
+        }
+    } else {
+        hipLaunchKernelGGL(k_stream_refill, dim3(grid), dim3(CAGYM_WAVE), 0, st, gen2_dev(e), e->stream_P, e->stream);
+    }
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
@@ -913,6 +936,138 @@ int cagym_stream_get(void* env, cagym_stream_ptrs* out) {
 int cagym_stream_stop(void* env) {
     ENTRY(e, env);
     e->streaming = false;
+    return CAGYM_OK;
+}
+
+// ---- exploration worlds and their stream (csrc/cagym_explore.h) -------------------------------------------------------------------------
+// the checks of cagym_generate_exploration_scenarios, shared with the stream entries; P: the internal stage parameter set, Tm: the team edit
+static int explore_validate(Env* e, const char* what, const cagym_explore_params* params, cagym_gen2_params& P, ExploreTeam& Tm, Gen2Flags& F) {
+    if (!params) return fail(e, CAGYM_E_INVALID, "null params");
+    const cagym_explore_params& X = *params;
+    const uint32_t stages = (1u << CAGYM_GEN_STAGE_1) | (1u << CAGYM_GEN_STAGE_2);
+    if (X.kinds_mask == 0 || (X.kinds_mask & ~stages) != 0)
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": kinds_mask takes the CAGYM_GEN_STAGE_1 / CAGYM_GEN_STAGE_2 bits only, and at least one");
+    if (X.n_robots < 1 || X.n_targets < 0 || (long long)X.n_robots + X.n_targets < 2 || (long long)X.n_robots + X.n_targets > e->cfg.max_agents)
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": need n_robots >= 1, n_targets >= 0 and 2 <= n_robots + n_targets <= max_agents");
+    if (!(X.target_radius > 0) || !(X.robot_pref_speed > 0) || std::isinf(X.target_radius) || std::isinf(X.robot_pref_speed))
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": target_radius and robot_pref_speed must be positive");
+    if (e->cfg.max_obstacles <= 0)
+        return fail(e, CAGYM_E_UNSUPPORTED, std::string(what) + ": exploration worlds need obstacle rasters (max_obstacles > 0)");
+    P = cagym_gen2_params{};
+    P.seed = X.seed;
+    P.kinds_mask = X.kinds_mask;
+    P.number_of_agents = X.n_robots + X.n_targets;
+    P.fixed_count = 1;
+    P.ego_policy = CAGYM_POL_IGMCTS;
+    P.ego_dynamics = CAGYM_DYN_FIRSTORDER;
+    P.override_policies = 1;
+    P.policy_a = P.policy_b = CAGYM_POL_STATIC;
+    P.other_dynamics = CAGYM_DYN_FIRSTORDER;
+    P.n_obst_min = X.n_obst_min;
+    P.n_obst_max = X.n_obst_max;
+    P.max_tries = X.max_tries;
+    P.p_b = 0.0;
+    Tm = ExploreTeam{X.n_robots, X.n_targets, X.target_radius, X.robot_pref_speed};
+    return gen2_validate(e, &P, F);  // max_tries, the stage ranges against the bounds and max_obstacles
+}
+
+// every slot's distance field again, on a handle cagym_ig_init has set up: its two EDT launches over S (the beliefs stay)
+static int ig_rebuild_fields(Env* e, hipStream_t st) {
+    const size_t S = e->cfg.n_scenarios;
+    HIPCHK(e, hipMemsetAsync(e->ig_any, 0, S * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_ig_edt_cols, dim3((unsigned)S), dim3(320), 0, st, e->G, e->ig_any);
+    hipLaunchKernelGGL(k_ig_edt_rows, dim3((unsigned)(S * CAGYM_MAPD)), dim3(320), 0, st, e->G, e->ig_any);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_generate_exploration_scenarios(void* env, const cagym_explore_params* params, int32_t* n_failed_host, void* stream) {
+    ENTRY(e, env);
+    cagym_gen2_params P;
+    ExploreTeam Tm;
+    Gen2Flags F;
+    if (int rc = explore_validate(e, "cagym_generate_exploration_scenarios", params, P, Tm, F)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(e);
+    if (int rc = gen_failed_word(e)) return rc;
+    HIPCHK(e, hipMemsetAsync(e->gen_failed, 0, sizeof(int32_t), st));
+    if (int rc = gen2_fill(e, P, F, e->gen_failed, n_failed_host, st, &Tm)) return rc;
+    return e->ig_ready ? ig_rebuild_fields(e, st) : CAGYM_OK;
+}
+
+// what the exploration stream's entries refuse beyond the generator's own checks (stream_check's list without its two IG refusals)
+static int explore_stream_check(Env* e, const char* what, const cagym_explore_params* params, cagym_gen2_params& P, ExploreTeam& Tm, Gen2Flags& F) {
+    if (int rc = explore_validate(e, what, params, P, Tm, F)) return rc;
+    const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
+    if (S % N != 0 || S < 2 * N)
+        return fail(e, CAGYM_E_INVALID, std::string(what) + ": n_scenarios must be a multiple of n_worlds and at least 2 * n_worlds (a ring of depth >= 2 per world)");
+    if (e->rec_ready)
+        return fail(e, CAGYM_E_STATE, std::string(what) + " with episode records initialised: their table has one row per pool slot, "
+                                                          "which a streamed pool reuses");
+    return CAGYM_OK;
+}
+
+int cagym_stream_exploration_scenarios(void* env, const cagym_explore_params* params, int32_t* n_failed_host, void* stream) {
+    ENTRY(e, env);
+    cagym_gen2_params P;
+    ExploreTeam Tm;
+    Gen2Flags F;
+    if (int rc = explore_stream_check(e, "cagym_stream_exploration_scenarios", params, P, Tm, F)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(e);
+    const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
+    if (!e->stream.next_episode) {  // as cagym_stream_scenarios: {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
+        unsigned char* buf = nullptr;
+        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
+        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
+        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
+        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
+        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
+    }
+    if (!e->explore.field_next) {  // {fields_built u64, n_list i32, pad} then field_next [N] then list [S - N]
+        unsigned char* buf = nullptr;
+        if (int rc = dalloc(e, &buf, 16 + ((size_t)N + (size_t)(S - N)) * sizeof(int32_t))) return rc;
+        e->explore.fields_built = reinterpret_cast<unsigned long long*>(buf);
+        e->explore.n_list = reinterpret_cast<int32_t*>(buf + 8);
+        e->explore.field_next = reinterpret_cast<int32_t*>(buf + 16);
+        e->explore.list = e->explore.field_next + N;
+        e->explore.cap = S - N;
+    }
+    StreamDev& T = e->stream;
+    T.episode = e->D.episode;
+    T.map_bits = const_cast<uint32_t*>(e->D.map_bits);
+    T.N = N;
+    T.depth = S / N;
+    HIPCHK(e, hipMemsetAsync(T.generated, 0, 16, st));
+    HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.generated), S, 1, st));
+    HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.next_episode), T.depth, (size_t)N, st));
+    HIPCHK(e, hipMemsetAsync(e->explore.fields_built, 0, 16, st));
+    HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->explore.field_next), T.depth, (size_t)N, st));
+    if (int rc = gen2_fill(e, P, F, T.n_failed, n_failed_host, st, &Tm)) return rc;
+    e->stream_P = P;
+    e->stream_team = Tm;
+    e->streaming = true;
+    e->explore_stream = true;
+    return e->ig_ready ? ig_rebuild_fields(e, st) : CAGYM_OK;
+}
+
+int cagym_stream_set_exploration_params(void* env, const cagym_explore_params* params) {
+    ENTRY_IF(e, env, e->streaming && e->explore_stream, "cagym_stream_set_exploration_params on a handle that streams no exploration worlds");
+    cagym_gen2_params P;
+    ExploreTeam Tm;
+    Gen2Flags F;
+    if (int rc = explore_stream_check(e, "cagym_stream_set_exploration_params", params, P, Tm, F)) return rc;
+    if (Tm.R != e->stream_team.R)
+        return fail(e, CAGYM_E_INVALID, "cagym_stream_set_exploration_params: n_robots is fixed while the stream runs (every slot of the ring holds the same team)");
+    e->stream_P = P;  // (the handle's flags do not move: no RVO agents before or after)
+    e->stream_team = Tm;
+    return CAGYM_OK;
+}
+
+int cagym_explore_stream_get(void* env, const int32_t** field_next, const uint64_t** fields_built) {
+    ENTRY_IF(e, env, e->explore.field_next != nullptr, "cagym_explore_stream_get before cagym_stream_exploration_scenarios");
+    if (field_next) *field_next = e->explore.field_next;
+    if (fields_built) *fields_built = reinterpret_cast<const uint64_t*>(e->explore.fields_built);
     return CAGYM_OK;
 }
 
@@ -1259,7 +1414,8 @@ int cagym_ga3c_forward(void* env, const float* weights, const float* state, cons
 // ---- information-gain primitives -----------------------------------------------------------------
 int cagym_ig_init(void* env, void* stream) {
     ENTRY_POOL(e, env, "cagym_ig_init");
-    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_ig_init on a streaming handle: the per-slot distance field is not rebuilt by cagym_stream_refill");
+    if (e->streaming && !e->explore_stream)
+        return fail(e, CAGYM_E_UNSUPPORTED, "cagym_ig_init on a streaming handle: the per-slot distance field is not rebuilt by cagym_stream_refill");
     if (e->cfg.max_obstacles <= 0 || !e->D.map_bits)
         return fail(e, CAGYM_E_UNSUPPORTED, "information-gain primitives need obstacle rasters (max_obstacles > 0)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1286,6 +1442,8 @@ int cagym_ig_init(void* env, void* stream) {
     hipLaunchKernelGGL(k_ig_edt_rows, dim3((unsigned)(S * CAGYM_MAPD)), dim3(320), 0, st, e->G, e->ig_any);
     hipLaunchKernelGGL(k_ig_fill_belief, dim3((unsigned)N), dim3(256), 0, st, e->G, (const uint8_t*)nullptr);
     HIPCHK(e, hipGetLastError());
+    if (e->streaming)  // an exploration stream: every field is current, which arms the refresh behind cagym_stream_refill
+        HIPCHK(e, hipMemcpyAsync(e->explore.field_next, e->stream.next_episode, N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     e->ig_ready = true;
     return CAGYM_OK;
 }

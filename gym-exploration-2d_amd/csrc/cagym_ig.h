@@ -240,50 +240,75 @@ __device__ __forceinline__ uint32_t ig_rand_primitive(uint64_t seed, uint32_t q,
 }
 
 // ---------------------------------------------------------------------------------------------------
-// EDT, pass 1: per column, distance (in cells) to the nearest occupied cell of that column.
-__global__ void __launch_bounds__(320) k_ig_edt_cols(IgDev G, uint32_t* any_flag) {
-    const int s = blockIdx.x, x = threadIdx.x;
-    if (x >= CAGYM_MAPD) return;
+// The exact EDT's two passes as device functions: k_ig_edt_cols / k_ig_edt_rows below run them over the whole pool, the field
+// refresh of an exploration stream (cagym_explore.h) over the slots a refill regenerated.  Integers throughout, so every
+// decomposition of the work gives the same bits.
+// Pass 1 of slot s by one workgroup (every thread makes the call; lm is its LDS copy of the slot's raster, CAGYM_MAPD * CAGYM_MAPW
+// words, free again after the caller's next barrier): thread x < CAGYM_MAPD walks column x once and stores, per cell, the distance
+// (in cells) to the nearest occupied cell of that column - to the last one it passed or to the next one ahead, which it looks up in
+// LDS only when it has passed the one it knew.  A column without an occupied cell gets 2^20 - y (>= 2^19: "none" to pass 2), as the
+// two-sweep form of this pass left there.  No global load besides the raster's 12 KB, one store per cell (the two sweeps of the first form
+// read the raster word and the first sweep's distance back per cell, and a refresh of ~50 slots took 185 us of load latency).
+// Returns whether column x holds an occupied cell.
+__device__ __forceinline__ bool ig_edt_cols_slot(const IgDev& G, int s, int x, uint32_t* lm) {
     const uint32_t* map = G.map_bits + (size_t)s * CAGYM_MAPD * CAGYM_MAPW;
+    for (int q = x; q < CAGYM_MAPD * CAGYM_MAPW; q += blockDim.x) lm[q] = map[q];
+    __syncthreads();
+    if (x >= CAGYM_MAPD) return false;
     uint32_t* g = G.d2 + (size_t)s * CAGYM_MAPD * CAGYM_MAPD;
     const int INF = 1 << 20;
-    int last = -INF;
+    int prev = -INF, next = -1;  // the occupied cells of the column nearest to y from below (<= y) and from above (>= y)
     bool any = false;
     for (int y = 0; y < CAGYM_MAPD; y++) {
-        if (map_bit(map, y, x)) { last = y; any = true; }
-        g[y * CAGYM_MAPD + x] = (uint32_t)(y - last);
+        if (next < y) {
+            int q = y;
+            while (q < CAGYM_MAPD && !map_bit(lm, q, x)) q++;
+            next = q < CAGYM_MAPD ? q : INF;
+        }
+        if (next == y) { prev = y; any = true; }
+        const uint32_t below = (uint32_t)(y - prev), above = (uint32_t)(next - y);
+        g[y * CAGYM_MAPD + x] = above < below ? above : below;
     }
-    last = INF;
-    for (int y = CAGYM_MAPD - 1; y >= 0; y--) {
-        if (map_bit(map, y, x)) last = y;
-        uint32_t d = (uint32_t)(last - y);
-        if (d < g[y * CAGYM_MAPD + x]) g[y * CAGYM_MAPD + x] = d;
-    }
-    if (any) atomicOr(&any_flag[s], 1u);
+    return any;
 }
 
-// EDT, pass 2: per row, lower envelope by brute force (300 candidates per cell), in place.  Every quantity fits 32 bits - a finite
-// column distance is <= 299, so a squared distance is <= 2 * 299^2 - and the candidates' squares are taken once per row (round 4: the
+// Pass 2, row y of slot s by one workgroup (every thread makes the call; g2 is its LDS row of CAGYM_MAPD words, free again at
+// return): lower envelope by brute force (300 candidates per cell), in place.  Every quantity fits 32 bits - a finite column
+// distance is <= 299, so a squared distance is <= 2 * 299^2 - and the candidates' squares are taken once per row (round 4: the
 // loop ran on 64-bit integers with a multiplication per candidate, 66.6 ms per scenario upload against 6.7 ms for pass 1).
-__global__ void __launch_bounds__(320) k_ig_edt_rows(IgDev G, const uint32_t* any_flag) {
-    __shared__ uint32_t g2[CAGYM_MAPD];  // squared column distance of the row's cells; 0x7fff0000 = no occupied cell in that column
-    const int s = blockIdx.x / CAGYM_MAPD, y = blockIdx.x % CAGYM_MAPD, x = threadIdx.x;
+__device__ __forceinline__ void ig_edt_row(const IgDev& G, int s, int y, int x, bool any, uint32_t* g2) {
     uint32_t* row = G.d2 + ((size_t)s * CAGYM_MAPD + y) * CAGYM_MAPD;
     if (x < CAGYM_MAPD) {
         const uint32_t gy = row[x];
-        g2[x] = gy >= (1u << 19) ? 0x7fff0000u : gy * gy;
+        g2[x] = gy >= (1u << 19) ? 0x7fff0000u : gy * gy;  // 0x7fff0000 = no occupied cell in that column
     }
     __syncthreads();
-    if (x >= CAGYM_MAPD) return;
-    uint32_t best = 2u * CAGYM_MAPD * CAGYM_MAPD;
-    if (any_flag[s]) {
-        for (int xx = 0; xx < CAGYM_MAPD; xx++) {
-            const int dx = x - xx;
-            const uint32_t d = (uint32_t)(dx * dx) + g2[xx];  // (< 2^31 + 2^17: no wrap; a column without an occupied cell never wins)
-            best = d < best ? d : best;
+    if (x < CAGYM_MAPD) {
+        uint32_t best = 2u * CAGYM_MAPD * CAGYM_MAPD;
+        if (any) {
+            for (int xx = 0; xx < CAGYM_MAPD; xx++) {
+                const int dx = x - xx;
+                const uint32_t d = (uint32_t)(dx * dx) + g2[xx];  // (< 2^31 + 2^17: no wrap; a column without an occupied cell never wins)
+                best = d < best ? d : best;
+            }
         }
+        row[x] = best;
     }
-    row[x] = best;
+    __syncthreads();
+}
+
+// EDT, pass 1: one workgroup per slot, one lane per column.
+__global__ void __launch_bounds__(320) k_ig_edt_cols(IgDev G, uint32_t* any_flag) {
+    __shared__ uint32_t lm[CAGYM_MAPD * CAGYM_MAPW];
+    const int s = blockIdx.x;
+    if (ig_edt_cols_slot(G, s, threadIdx.x, lm)) atomicOr(&any_flag[s], 1u);
+}
+
+// EDT, pass 2: one workgroup per row of every slot.
+__global__ void __launch_bounds__(320) k_ig_edt_rows(IgDev G, const uint32_t* any_flag) {
+    __shared__ uint32_t g2[CAGYM_MAPD];  // squared column distance of the row's cells
+    const int s = blockIdx.x / CAGYM_MAPD, y = blockIdx.x % CAGYM_MAPD;
+    ig_edt_row(G, s, y, threadIdx.x, any_flag[s] != 0, g2);
 }
 
 // world w's belief at the prior and its MI cache at ig_cell_mi(prior), by the `nthreads` threads of a block (k_ig_fill_belief and the

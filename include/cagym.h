@@ -671,7 +671,7 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
  * cagym_stream_stop: ends the stream (the pool stays as it is); a successful cagym_set_scenarios, cagym_generate_scenarios or
  *   cagym_generate_reference_scenarios does the same.
  * While streaming: cagym_restore and cagym_fork return CAGYM_E_UNSUPPORTED (the ring is not part of a snapshot; cagym_snapshot stays
- * allowed), cagym_ig_init CAGYM_E_UNSUPPORTED and cagym_episode_records_init CAGYM_E_STATE.
+ * allowed), cagym_ig_init CAGYM_E_UNSUPPORTED (an exploration stream, below, accepts it) and cagym_episode_records_init CAGYM_E_STATE.
  * Not streamed: cagym_generate_scenarios' own parameter struct (the RANDOM_POSITIONS kind covers its rule). */
 struct cagym_stream_ptrs {
     const int32_t* next_episode; /* [N] first episode of world w whose slot has not been generated */
@@ -685,6 +685,60 @@ int cagym_stream_refill(void* env, void* stream);
 int cagym_stream_set_params(void* env, const cagym_gen2_params* params);
 int cagym_stream_get(void* env, cagym_stream_ptrs* out);
 int cagym_stream_stop(void* env);
+
+/* ---- Exploration worlds: an IG team on fresh maps, generated and streamed on the device (csrc/cagym_explore.h) ---------------------
+ * A world holds a team of R = n_robots IG robots (CAGYM_POL_IGMCTS, FirstOrder, slots 0..R-1: the reference's ig_mcts indexes the
+ * team by slot) and T = n_targets static targets (slots R..R+T-1) among the rectangles of train_stage_1 / train_stage_2.
+ * The scenario of stream key v is cagym_generate_reference_scenarios' scenario of key v for the parameter set
+ *   number_of_agents = R + T, fixed_count = 1, ego_policy = IGMCTS, ego_dynamics = FIRSTORDER, override_policies = 1,
+ *   policy_a = policy_b = STATIC, p_b = 0, other_dynamics = FIRSTORDER, and the caller's seed, kinds_mask, n_obst_*, max_tries
+ * - the same draws in the same order, nothing new is drawn - followed by the team edit of its row: slots 0..R-1 get IGMCTS,
+ * FirstOrder and pref_speed = robot_pref_speed (which only sets the robots' time limit 3 (|p - g| - 0.75) / pref_speed), slots
+ * R..R+T-1 get Static and radius = target_radius (IG_agent_crossing uses 0.2, tc.py:3236-3237).  Starts and goals stay as the stage
+ * rule places them (1 m clear of every rectangle, 1.5 m apart); rectangles, RVO prep rows and rasters are built as there.
+ * cagym_generate_exploration_scenarios: CAGYM_E_INVALID for a mask that is empty or holds another bit than the two stage kinds',
+ *   n_robots < 1, n_targets < 0, n_robots + n_targets < 2 or > max_agents, a target_radius or robot_pref_speed that is not positive
+ *   and finite, and whatever cagym_generate_reference_scenarios refuses of the internal set (max_tries, the stage ranges against the
+ *   bounds and max_obstacles); CAGYM_E_UNSUPPORTED on a handle with max_obstacles == 0.  A refused call leaves the handle as it was.
+ *   An accepted one commits the handle as cagym_generate_reference_scenarios does, except that the pool's IG robot count is known:
+ *   cagym_ig_robot_inputs / _actions accept n_robots = R.  On a handle cagym_ig_init has set up it rebuilds every slot's distance
+ *   field itself (the two EDT launches over S; beliefs and planner state are the caller's to restart).
+ * cagym_stream_exploration_scenarios: cagym_stream_scenarios' ring contract exactly (S % N == 0, S >= 2 N, slot (w + e N) % S holds
+ *   the scenario of key (uint32_t)(w + e N), the first fill equals cagym_generate_exploration_scenarios bit for bit, the counters of
+ *   cagym_stream_get restart, CAGYM_E_STATE with episode records initialised).  A handle with information-gain state is accepted:
+ *   the fill is followed by the rebuild of every field.  From then on cagym_stream_refill launches the exploration refill kernel
+ *   (k_stream_refill's windows and counters plus the team edit) and, once cagym_ig_init has run, the FIELD REFRESH behind it:
+ *   when the call returns - in stream order - edf_d2[s] is the exact squared-distance transform of the raster of every pool slot s.
+ *   field_next[w] is the first episode of world w whose slot has been regenerated but not rebuilt; behind a refill the world's
+ *   window is episodes max(field_next[w], episode[w] + 1) .. next_episode[w] - 1, then field_next[w] = next_episode[w]; the slot of
+ *   a world's current episode is never written; fields_built counts the rebuilt slots since the stream started.
+ *   Launches per cagym_stream_refill on this stream: 1 before cagym_ig_init, 4 after it (refill; work list; EDT columns; EDT rows -
+ *   fixed grids striding over the device-built list), no host synchronisation, no allocation.  A refill after which no world
+ *   finished costs the refresh a few loads per workgroup.  The kernels coordinate through the launch boundaries only.
+ * cagym_ig_init on this stream (refused on a cagym_stream_scenarios one): builds all S fields and arms the refresh,
+ *   field_next[w] = next_episode[w].
+ * cagym_stream_set_exploration_params: the curriculum switch, as cagym_stream_set_params (same validation as the stream's start;
+ *   takes effect for the slots later refills generate).  n_robots must stay what the stream started with (CAGYM_E_INVALID): every
+ *   slot of the ring holds the same team.  CAGYM_E_STATE on a handle that streams no exploration worlds.
+ * cagym_explore_stream_get: zero-copy DEVICE views field_next [N] i32 and fields_built u64 (either pointer may be NULL);
+ *   CAGYM_E_STATE before the first cagym_stream_exploration_scenarios.  cagym_stream_ptrs / cagym_stream_get keep their fields.
+ * Still refused while this stream runs: cagym_restore / cagym_fork, cagym_episode_records_init, and cagym_stream_set_params with
+ *   the cagym_gen2_params struct (CAGYM_E_UNSUPPORTED).  cagym_stream_stop and the pool setters end it as they end any stream; the
+ *   fields stay valid for the pool as it stands.
+ * Out of scope: streaming a host-uploaded IG pool, snapshots of an attached planner, per-robot beliefs, a linear-time EDT. */
+struct cagym_explore_params {
+    uint64_t seed;
+    uint32_t kinds_mask;          /* (1 << CAGYM_GEN_STAGE_1) and / or (1 << CAGYM_GEN_STAGE_2) only */
+    int32_t n_robots, n_targets;  /* R >= 1, T >= 0, 2 <= R + T <= max_agents */
+    int32_t n_obst_min, n_obst_max, max_tries; /* as cagym_gen2_params */
+    double target_radius;
+    double robot_pref_speed;
+};
+typedef struct cagym_explore_params cagym_explore_params;  /* (declared as cagym_stream_ptrs is) */
+int cagym_generate_exploration_scenarios(void* env, const cagym_explore_params* params, int32_t* n_failed_host, void* stream);
+int cagym_stream_exploration_scenarios(void* env, const cagym_explore_params* params, int32_t* n_failed_host, void* stream);
+int cagym_stream_set_exploration_params(void* env, const cagym_explore_params* params);
+int cagym_explore_stream_get(void* env, const int32_t** field_next, const uint64_t** fields_built);
 
 #ifdef __cplusplus
 }
