@@ -114,6 +114,21 @@ class CagymStreamPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("next_episode", "generated", "n_failed", "n_lapped")]
 
 
+class CagymTerminalOutputs(C.Structure):
+    """cagym_terminal_outputs (include/cagym.h)."""
+    _fields_ = [("obs_oas", C.c_void_p), ("obs_ego", C.c_void_p), ("laserscan", C.c_void_p)]
+
+
+TRAJ_COLUMNS = ("t", "pos_x", "pos_y", "goal_x", "goal_y", "radius", "pref_speed", "vel_x", "vel_y", "speed", "heading", "a0", "a1")
+# cagym_trajectory_ptrs: (field, typestr, shape in terms of L / C = 13 columns / N / M); the int32 n_slices closes the struct
+TRAJ_FIELDS = [("rows", "f8", "LCNM"), ("moved", "u1", "LNM"), ("episode", "i4", "LN"), ("last", "u1", "LN"), ("head", "u8", "1"),
+               ("desync", "i4", "1"), ("t_prev", "f8", "NM"), ("seen", "i4", "NM")]
+
+
+class CagymTrajectoryPtrs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _, _ in TRAJ_FIELDS] + [("n_slices", C.c_int32)]
+
+
 # ---- the prototypes of include/cagym.h: name -> argtypes; every function returns int except those of _RESTYPES ----------------
 _vp, _int, _dbl, _P = C.c_void_p, C.c_int, C.c_double, C.POINTER
 _OUT = _P(CagymOutputs)
@@ -182,6 +197,10 @@ _ARGTYPES = {
     "cagym_stream_exploration_scenarios": [_vp, _P(CagymExploreParams), _P(C.c_int32), _vp],
     "cagym_stream_set_exploration_params": [_vp, _P(CagymExploreParams)],
     "cagym_explore_stream_get": [_vp, _P(_vp), _P(_vp)],
+    "cagym_step_autoreset_keep": [_vp, _vp, _OUT, _P(CagymTerminalOutputs), _vp],
+    "cagym_trajectory_init": [_vp, _int, _vp],
+    "cagym_trajectory_restart": [_vp, _vp, _int, _vp],
+    "cagym_trajectory_get": [_vp, _P(CagymTrajectoryPtrs)],
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],

@@ -95,6 +95,7 @@ class BatchedCollisionAvoidanceEnv(object):
         self._step_fn = (self.L.cagym_step, self.L.cagym_step_autoreset)
         self._rollout_fn, self._records_fn = self.L.cagym_rollout, self.L.cagym_episode_records_update
         self._refill_fn, self._log_fn = self.L.cagym_stream_refill, self.L.cagym_episode_log_update
+        self._keep_fn = self.L.cagym_step_autoreset_keep
         N, M, K = self.N, self.M, self.K
         dev = self.device
         self.obs_oas = torch.zeros((N, M, K, 10), dtype=torch.float32, device=dev)
@@ -121,6 +122,10 @@ class BatchedCollisionAvoidanceEnv(object):
         self._streaming = False   # stream_reference_scenarios: one cagym_stream_refill behind every episode-advancing call
         self._stream_views = None
         self._explore_views = None
+        self._term = None         # keep_terminal_observations: {"other_agents_states", "ego", "laserscan"} env-owned tensors
+        self._term_c = None       # ... as the cagym_terminal_outputs step() passes
+        self._traj = None         # n_slices of attach_trajectory_ring, None while detached
+        self._traj_views = None
 
     # ---- plumbing ------------------------------------------------------------------------------
     @staticmethod
@@ -480,6 +485,8 @@ class BatchedCollisionAvoidanceEnv(object):
 
     def _attach_ig(self, kind, detect_fov, detect_range, xdt, episodic, make_planner):
         """Attach an IG policy, whichever it is: the primitives, the robots' input buffers, then its planner."""
+        self._refuse_keep("attach_%s" % kind, "an attached IG planner's per-world restart reads the game_over of the auto-resetting launch; "
+                          "the three-launch step has not been taken through it")
         R = self._n_ig if self._n_ig is not None else 0
         self._igm = None
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
@@ -553,13 +560,17 @@ class BatchedCollisionAvoidanceEnv(object):
             g.ig.robot_actions(g.R, planned, table)
         return table
 
-    def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None):
+    def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None, term=False):
         """One step with whatever is attached, three parts in stream order: the internal actions (_internal_actions), the step
         launch into the CagymOutputs `o`, and the episodic IG team's end of the step - its running return and the restart of the
-        worlds of `restart` (under auto_reset the game_over tensor `o` points at, else None).  (No torch.cuda.device context
+        worlds of `restart` (under auto_reset the game_over tensor `o` points at, else None).  term: hand the env's terminal buffers
+        to the step (step() does, rollout() does not).  (No torch.cuda.device context
         here or anywhere else around the C ABI: every launching entry makes the handle's device current itself.)"""
         a = self._internal_actions(a, team_reward_out, oas)
-        rc = self._step_fn[bool(auto_reset)](self.h, _lib.ptr(a), C.byref(o), self._stream())
+        if auto_reset and (self._traj is not None or (term and self._term is not None)):  # same results, three launches (cagym_step_autoreset_keep)
+            rc = self._keep_fn(self.h, _lib.ptr(a), C.byref(o), self._term_c if term else None, self._stream())
+        else:
+            rc = self._step_fn[bool(auto_reset)](self.h, _lib.ptr(a), C.byref(o), self._stream())
         if rc:
             _lib.check(self.L, self.h, rc, "cagym_step")
         g = self._igm
@@ -577,9 +588,12 @@ class BatchedCollisionAvoidanceEnv(object):
                                "communicated plans) is not implemented for this attach; attach_%s(episodic=True), or step "
                                "without auto-reset and reset() yourself" % (k, k))
         self._records_contract(auto_reset, "step")
-        self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None)
+        self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None, term=True)
         self._after_steps(auto_reset, self.flags, self.reward, self.game_over, 1)
-        return self._obs(), self.reward, self.game_over, {"flags": self.flags}
+        info = {"flags": self.flags}
+        if auto_reset and self._term is not None:
+            info["terminal"] = dict(self._term, valid=self.game_over)
+        return self._obs(), self.reward, self.game_over, info
 
     # ---- per-scenario episode records (include/cagym.h: cagym_episode_records_*) ---------------------------------------------
     def attach_episode_records(self, keep="first"):
@@ -616,6 +630,9 @@ class BatchedCollisionAvoidanceEnv(object):
             self._records_update(flags, reward, game_over, T)
 
     def _records_contract(self, auto_reset, what):
+        if self._traj is not None and not auto_reset:
+            raise RuntimeError("%s(auto_reset=False) with a trajectory ring attached: the ring is fed by cagym_step_autoreset_keep "
+                               "only, every step exactly once and in order (include/cagym.h); detach_trajectory_ring() first" % what)
         if self._log is not None and not auto_reset:
             raise RuntimeError("%s(auto_reset=False) with an episode log attached: cagym_episode_log_update takes the outputs "
                                "of auto-reset stepping only, every step exactly once and in order (include/cagym.h); "
@@ -748,6 +765,110 @@ class BatchedCollisionAvoidanceEnv(object):
         rows["count"] = torch.ones((n,), dtype=torch.int32, device=self.device)
         return rows
 
+    # ---- terminal observations and the trajectory ring (include/cagym.h: cagym_step_autoreset_keep, cagym_trajectory_*) ---------
+    def _refuse_keep(self, what, why):
+        if self._term is not None or self._traj is not None:
+            on = "a trajectory ring attached" if self._traj is not None else "keep_terminal_observations() on"
+            raise RuntimeError("%s() with %s: %s" % (what, on, why))
+
+    def _refuse_keep_with_planner(self, what):
+        if self._igm is not None:
+            raise RuntimeError("%s() with %s attached: an attached IG planner's per-world restart reads the game_over of the "
+                               "auto-resetting launch; the three-launch step has not been taken through it; detach_ig_mcts() first"
+                               % (what, self._igm.kind))
+
+    def _refuse_split_keep(self, auto_reset, what):
+        if auto_reset:
+            self._refuse_keep("%s(auto_reset=True)" % what, "the split step ends in the auto-resetting launch, which overwrites the "
+                              "terminal observation and the terminal state; use step(auto_reset=True)")
+
+    def _refuse_with_ring(self, what):
+        if self._traj is not None:
+            raise RuntimeError("%s() with a trajectory ring attached: its running values would describe another timeline (the library "
+                               "refuses as long as the ring is initialised)" % what)
+
+    def keep_terminal_observations(self, on=True):
+        """From now on step(auto_reset=True) keeps the observation every finished world ENDED on, which the auto-reset overwrites with
+        the first one of the new episode: info["terminal"] = {"other_agents_states" [N, M, M-1, 10], "ego" [N, M, 12], "laserscan"
+        [N, M, 16] (with a LaserScan sensor), "valid": game_over}.  The tensors are the env's own and are rewritten in place; a
+        world's rows are meaningful where `valid` is set and otherwise hold what its last finished episode left (zeros before
+        the first).  The step then runs as three launches with the same results, bit for bit (cagym_step_autoreset_keep: step,
+        capture, reset of the finished worlds).  step_finish / step_overlapped with auto_reset=True and an attached IG planner are
+        refused while it is on; rollout() stays the single launch and returns no terminal observations.  on=False switches back."""
+        if not on:
+            self._term = self._term_c = None
+            return self
+        self._refuse_keep_with_planner("keep_terminal_observations")
+        t = {"other_agents_states": torch.zeros_like(self.obs_oas), "ego": torch.zeros_like(self.obs_ego)}
+        if self.laserscan:
+            t["laserscan"] = torch.zeros_like(self.obs_laser)
+        self._term = t
+        self._term_c = _lib.CagymTerminalOutputs(t["other_agents_states"].data_ptr(), t["ego"].data_ptr(), _lib.ptr(t.get("laserscan")))
+        return self
+
+    def attach_trajectory_ring(self, n_slices):
+        """From now on every step(auto_reset=True) adds one slice to a device ring of n_slices steps: per agent that moved, the
+        reference's global_state_history row [t_before, px, py, gx, gy, radius, pref_speed, vx, vy, speed, heading, a0, a1]
+        (agent.py:198-201: the state AFTER the move, the time stamp of before it), the terminal row of every episode included,
+        plus the world's episode index and game_over.  trajectory(world, episode) reads an episode back, dataset.export_ring
+        writes the reference's trajectory pickle.  The step runs as three launches with the same results (see
+        keep_terminal_observations), and rollout(auto_reset=True) as the chain of such steps (see rollout).  The ring takes every
+        step exactly once and in order: step(auto_reset=False), rollout(auto_reset=False), step_finish / step_overlapped with
+        auto_reset=True, restore(), fork() and an attached IG planner are refused while attached.  A ring attached in mid-episode
+        starts there.  Attaching again clears the ring and may change n_slices.  Needs a scenario pool."""
+        n_slices = int(n_slices)
+        if n_slices < 1:
+            raise ValueError("attach_trajectory_ring: n_slices must be >= 1, got %d" % n_slices)
+        self._refuse_keep_with_planner("attach_trajectory_ring")
+        _lib.call(self.L, self.h, "cagym_trajectory_init", n_slices, self._stream())
+        self._traj, self._traj_views = n_slices, None
+        return self
+
+    def detach_trajectory_ring(self):
+        """Stop feeding the ring (the library keeps it, and keeps refusing restore / fork; attach again to clear and resume)."""
+        self._traj = None
+
+    def _refuse_without_ring(self, what):
+        if self._traj is None:
+            raise RuntimeError("%s() without a trajectory ring: attach_trajectory_ring() first" % what)
+
+    def trajectory_views(self):
+        """Zero-copy device views of the ring, no synchronisation: rows [L, 13, N, M] f64 (column planes, _lib.TRAJ_COLUMNS),
+        moved [L, N, M] u8, episode [L, N] i32, last [L, N] u8, head [1] i64 (slices ever written; slice i lives at index i % L),
+        desync [1] i32, and the ring's running t_prev [N, M] f64, seen [N, M] i32."""
+        self._refuse_without_ring("trajectory_views")
+        if self._traj_views is None:
+            tp = _lib.CagymTrajectoryPtrs()
+            _lib.call(self.L, self.h, "cagym_trajectory_get", C.byref(tp))
+            L, N, M = int(tp.n_slices), self.N, self.M
+            dims = {"LCNM": (L, len(_lib.TRAJ_COLUMNS), N, M), "LNM": (L, N, M), "LN": (L, N), "NM": (N, M), "1": (1,)}
+            v = {}
+            for name, ts, shape in _lib.TRAJ_FIELDS:
+                ts = {"u8": "i8"}.get(ts, ts)  # the bits, in the signed type torch computes with
+                v[name] = torch.as_tensor(_DevArray(getattr(tp, name), dims[shape], ts), device=self.device)
+            self._traj_views = v
+        return dict(self._traj_views)
+
+    def trajectory(self, world, episode, check=True):
+        """The slices of episode `episode` of world `world` that are still in the ring, oldest first, as host arrays: "history"
+        [T, M, 13] (a row is meaningful where `moved`), "moved" [T, M] bool, "complete": the episode's first row and its `last`
+        slice (the step that set game_over) are both present.  One synchronisation.  check: raise RuntimeError when a step went
+        past the ring (desync != 0)."""
+        from . import dataset
+        v = self.trajectory_views()
+        w = int(world)
+        if not 0 <= w < self.N:
+            raise ValueError("trajectory: world must lie in [0, %d), got %d" % (self.N, w))
+        head, d = torch.cat([v["head"], v["desync"].to(torch.int64)]).tolist()
+        if check and d:
+            raise RuntimeError("the trajectory ring is out of step with the env (desync: %d agent-steps went past it): the env was "
+                               "stepped through another entry than step(auto_reset=True) / rollout(auto_reset=True); "
+                               "attach_trajectory_ring() again to clear" % d)
+        planes = {"rows": v["rows"][:, :, w:w + 1].cpu().numpy(), "moved": v["moved"][:, w:w + 1].cpu().numpy(),
+                  "episode": v["episode"][:, w:w + 1].cpu().numpy(), "last": v["last"][:, w:w + 1].cpu().numpy(), "head": head}
+        H, mv, complete = dataset.ring_slices(planes, 0, int(episode))
+        return {"history": H, "moved": mv, "complete": complete}
+
     # ---- the split step: env.step() in two launches (include/cagym.h: cagym_step_begin / cagym_step_finish) ------------------
     def step_begin(self, stream=None):
         """First half of step(): the internal RVO policies' half-planes and linear programs on the current state (they do not
@@ -767,6 +888,7 @@ class BatchedCollisionAvoidanceEnv(object):
         """Second half of step(): everything else, with every agent's action in hand.  Same results as step(), bit for bit.
         Takes every action from the caller: refused while attach_ga3c / attach_ig_mcts drive agents inside step()."""
         self._refuse_split()
+        self._refuse_split_keep(auto_reset, "step_finish")
         self._records_contract(auto_reset, "step_finish")
         a = self._actions(actions)
         _lib.call(self.L, self.h, "cagym_step_finish", _lib.ptr(a), C.byref(self._out), int(bool(auto_reset)), self._stream())
@@ -780,6 +902,7 @@ class BatchedCollisionAvoidanceEnv(object):
         measured on MI355X (profiles/r4/cfg4_overlap_trace_*.txt) the two kernels do run side by side, but sharing the CUs halves
         each one's occupancy and both take twice as long - 0.251 ms per cfg4 step against 0.194 ms for the fused launch."""
         self._refuse_split()
+        self._refuse_split_keep(auto_reset, "step_overlapped")
         main = torch.cuda.current_stream(self.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -812,7 +935,14 @@ class BatchedCollisionAvoidanceEnv(object):
         On a streaming env (stream_reference_scenarios) the ring is refilled ONCE, behind the last step: a world may finish at
         most n_scenarios / n_worlds - 1 episodes per launch.  A world that finishes more starts an episode on a slot that was not
         refilled (it replays an older scenario); nothing faults, and stream_stats()["n_lapped"] counts it - that is how a caller
-        finds out, and the remedy is a shorter rollout or a deeper ring."""
+        finds out, and the remedy is a shorter rollout or a deeper ring.
+        With a trajectory ring attached (attach_trajectory_ring) rollout(auto_reset=True) gives up the single launch: the roll-out
+        kernel keeps the agents on chip for all T steps and restarts finished worlds in place, so the state after each move never
+        reaches memory where the ring's capture kernel could read it.  It runs T x (step, capture, reset) instead - the chain of
+        step(auto_reset=True), each step writing slice t of the buffers, with one log update, one refill and one records update
+        behind the last step, as the GA3C chain does; no host synchronisation.  The results are the single launch's, bit for bit;
+        the cost is three launches per step (tools/terminal_cost.py measures it).  rollout() returns no terminal observations:
+        with keep_terminal_observations() alone it stays the single launch."""
         self._records_contract(auto_reset, "rollout")
         T, g = int(n_steps), self._igm
         if g is not None and not g.episodic:
@@ -829,7 +959,7 @@ class BatchedCollisionAvoidanceEnv(object):
         if g is not None and out.get("team_reward") is None:
             out["team_reward"] = torch.empty((T, self.N), dtype=torch.float64, device=self.device)
         caller_out, out = out, self._records_out(out, T)
-        if g is None and not self._drives_ga3c():
+        if g is None and not self._drives_ga3c() and not (auto_reset and self._traj is not None):
             o = self._outputs(*[out.get(k) for k in _OUT_KEYS])
             rc = self._rollout_fn(self.h, T, int(bool(auto_reset)), C.byref(o), self._stream())
             if rc:
@@ -955,6 +1085,7 @@ class BatchedCollisionAvoidanceEnv(object):
         initialised."""
         self._refuse_with_planner("restore")
         self._refuse_with_log("restore")
+        self._refuse_with_ring("restore")
         self._refuse_streaming("restore", "the ring of scenario slots is not part of a snapshot (a restored episode index would meet "
                                "other scenarios)")
         valid = None
@@ -990,6 +1121,7 @@ class BatchedCollisionAvoidanceEnv(object):
         afterwards."""
         self._refuse_with_planner("fork")
         self._refuse_with_log("fork")
+        self._refuse_with_ring("fork")
         self._refuse_streaming("fork", "the ring of scenario slots is not part of a snapshot, and a refill would overwrite the forked slot")
         s, hs = self._id_list(src, "fork(src)", check, self.N, distinct=False)
         d, hd = self._id_list(dst, "fork(dst)", check, self.N)

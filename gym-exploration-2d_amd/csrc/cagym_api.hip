@@ -31,6 +31,7 @@
 #include "cagym_snapshot.h"
 #include "cagym_stream.h"
 #include "cagym_explore.h"
+#include "cagym_terminal.h"
 
 namespace {
 
@@ -74,6 +75,11 @@ struct Env {
     bool explore_stream = false;     // while streaming: cagym_stream_exploration_scenarios started the ring (csrc/cagym_explore.h)
     ExploreTeam stream_team{};       // its team edit (cagym_stream_set_exploration_params replaces it together with stream_P)
     ExploreDev explore{};            // the field refresh's device words (allocated by the first cagym_stream_exploration_scenarios)
+    uint8_t* go_scratch = nullptr;   // [N] game_over of cagym_step_autoreset_keep when the caller gives none
+    TrajRing traj{};                 // trajectory ring (cagym_trajectory_init allocates it: the running block once, the ring per n_slices)
+    bool traj_ready = false;
+    void* traj_ring = nullptr;       // the ring's one allocation (TrajRing's planes are carved from it)
+    size_t traj_ring_bytes = 0;
 };
 enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
@@ -289,10 +295,31 @@ inline int eplog_restart(Env* e, const uint8_t* world_mask, bool clear_rows, hip
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
-// what a new pool means to both: the records describe the pool (cleared); the log is history (its rows stay, the running values go)
+// the trajectory ring's restart / clear (csrc/cagym_terminal.h); a no-op for handles that never initialised it
+inline int traj_restart(Env* e, const uint8_t* world_mask, bool clear, hipStream_t st) {
+    if (!e->traj_ready) return CAGYM_OK;
+    const size_t NM = (size_t)e->cfg.n_worlds * e->cfg.max_agents;
+    if (clear) {  // every slice; head, desync and the workgroups' copies of head open the running block
+        HIPCHK(e, hipMemsetAsync(e->traj_ring, 0, e->traj_ring_bytes, st));
+        HIPCHK(e, hipMemsetAsync(e->traj.head, 0, 16 + 8 * (size_t)tcap_slice_wgs(e->cfg.n_worlds, e->cfg.max_agents), st));
+    }
+    hipLaunchKernelGGL(k_trajectory_restart, dim3((unsigned)std::min<size_t>((NM + 255) / 256, 4096)), dim3(256), 0, st, e->D, e->traj, world_mask);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+// what a new pool means to the three: the records describe the pool (cleared); the log and the ring are history (their rows stay, the
+// running values go)
 inline int episodes_new_pool(Env* e, hipStream_t st) {
     if (int rc = eprec_restart(e, nullptr, true, st)) return rc;
-    return eplog_restart(e, nullptr, false, st);
+    if (int rc = eplog_restart(e, nullptr, false, st)) return rc;
+    return traj_restart(e, nullptr, false, st);
+}
+// the reset kernel as cagym_reset and cagym_step_autoreset_keep launch it
+inline int launch_reset(Env* e, const uint8_t* world_mask, int advance_episode, const CagymOut& o, hipStream_t st) {
+    hipLaunchKernelGGL(k_reset, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, world_mask,
+                       advance_episode, o);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
 }
 
 // ---- the field tables of csrc/cagym_snapshot.h ----------------------------------------------------------------------------------------
@@ -431,6 +458,7 @@ static int alloc_state(Env* e) {
     A(dalloc(e, &D.stat_steps, N)); A(dalloc(e, &D.stat_outcomes, N * 3));
     A(dalloc(e, &e->ga3c_ctr, 4));  // at creation: cagym_ga3c_act may run inside a stream capture (no allocation there)
     A(dalloc(e, &e->ga3c_packed, GA16_PACKED_BYTES));
+    A(dalloc(e, &e->go_scratch, N));  // at creation, as the GA3C words: cagym_step_autoreset_keep may run inside a stream capture
 #undef A
     return CAGYM_OK;
 }
@@ -1095,11 +1123,10 @@ int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const
     ON_DEVICE_VOIDS_BEGUN(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const CagymOut o = to_out(e, out, true);
-    hipLaunchKernelGGL(k_reset, dim3(n_waves(e)), dim3(64), cagym_lds_bytes(e->cfg.max_agents), st, e->D, world_mask,
-                       advance_episode, o);
-    HIPCHK(e, hipGetLastError());
+    if (int rc = launch_reset(e, world_mask, advance_episode, o, st)) return rc;
     if (int rc = eprec_restart(e, world_mask, false, st)) return rc;  // an abandoned episode leaves no record
     if (int rc = eplog_restart(e, world_mask, false, st)) return rc;  // ... and no row
+    if (int rc = traj_restart(e, world_mask, false, st)) return rc;   // ... keeps its rows in the ring, without a `last` slice
     if (e->cfg.laserscan && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);
     return CAGYM_OK;
 }
@@ -1125,6 +1152,100 @@ int cagym_step_autoreset(void* env, const float* ext_actions, const cagym_output
     launch3(e, K3_HALF_NONE, false, true, ext_actions, 1, o, st);
     HIPCHK(e, hipGetLastError());
     return fill_empty_scan(e, o, st);  // the scan of the (possibly restarted) worlds is part of the launch
+}
+
+// ---- terminal observations and the trajectory ring (csrc/cagym_terminal.h) ---------------------------------------------------------
+int cagym_step_autoreset_keep(void* env, const float* ext_actions, const cagym_outputs* out, const cagym_terminal_outputs* term, void* stream) {
+    ENTRY_POOL(e, env, "cagym_step_autoreset_keep");
+    ON_DEVICE_VOIDS_BEGUN(e);
+    if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_step_autoreset_keep needs the generation-3 kernels");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    CagymOut o = to_out(e, out);
+    if (!o.game_over) o.game_over = e->go_scratch;
+    // 1. the step, without the restart: `out` and the state hold the terminal observation and the terminal state
+    launch3(e, K3_HALF_NONE, false, false, ext_actions, 1, o, st);
+    HIPCHK(e, hipGetLastError());
+    if (int rc = fill_empty_scan(e, o, st)) return rc;
+    // 2. the finished worlds' rows into `term`, and the ring's slice
+    TermOut t{};
+    if (term) {
+        t.obs_oas = o.obs_oas ? term->obs_oas : nullptr;
+        t.obs_ego = o.obs_ego ? term->obs_ego : nullptr;
+        t.laserscan = o.laserscan ? term->laserscan : nullptr;
+    }
+    const unsigned n_row_wg = (t.obs_oas || t.obs_ego || t.laserscan) ? tcap_row_wgs(e->cfg.n_worlds) : 0u;
+    const unsigned n_slice_wg = e->traj_ready ? tcap_slice_wgs(e->cfg.n_worlds, e->cfg.max_agents) : 0u;
+    if (n_row_wg + n_slice_wg) {
+        hipLaunchKernelGGL(k_terminal_capture, dim3(n_row_wg + n_slice_wg), dim3(TCAP_NT), 0, st, e->D, o, t, e->traj, n_row_wg);
+        HIPCHK(e, hipGetLastError());
+    }
+    // 3. DummyVecEnv's restart of exactly those worlds: only their observations are rewritten, the terminal reward / flags / game_over stay
+    CagymOut r = to_out(e, out, true);
+    r.reward = nullptr; r.flags = nullptr; r.game_over = nullptr;
+    if (int rc = launch_reset(e, o.game_over, 1, r, st)) return rc;
+    if (e->cfg.laserscan && r.laserscan) return cagym_laserscan(env, r.laserscan, stream);
+    return CAGYM_OK;
+}
+
+int cagym_trajectory_init(void* env, int n_slices, void* stream) {
+    ENTRY_POOL(e, env, "cagym_trajectory_init");
+    if (n_slices < 1) return fail(e, CAGYM_E_INVALID, "cagym_trajectory_init: n_slices must be >= 1");
+    if (e->generation != 3) return fail(e, CAGYM_E_UNSUPPORTED, "the trajectory ring is fed by cagym_step_autoreset_keep, which needs the generation-3 kernels");
+    ON_DEVICE(e);
+    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, NM = N * M, L = (size_t)n_slices, n_wg = tcap_slice_wgs((int)N, (int)M);
+    TrajRing R = e->traj;
+    if (!R.t_prev) {  // the running block: once per handle (8-byte words first)
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, 16 + 8 * n_wg + 8 * NM + 4 * NM)) return rc;
+        R.head = reinterpret_cast<unsigned long long*>(b); b += 8;
+        R.desync = reinterpret_cast<int32_t*>(b); b += 8;
+        R.head_wg = reinterpret_cast<unsigned long long*>(b); b += 8 * n_wg;
+        R.t_prev = reinterpret_cast<double*>(b); b += 8 * NM;
+        R.seen = reinterpret_cast<int32_t*>(b);
+        e->traj = R;  // kept whatever becomes of the ring's allocation
+    }
+    if (!e->traj_ring || R.L != n_slices) {  // the ring: once per n_slices (8-byte plane first, then the 4-byte one, then bytes)
+        const size_t per_slice = 8 * TRAJ_COLS * NM + 4 * N + NM + N;
+        if (L > ((size_t)1 << 46) / per_slice) return fail(e, CAGYM_E_NOMEM, "cagym_trajectory_init: the ring does not fit");
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, L * per_slice)) {
+            (void)hipGetLastError();  // a refused allocation must not surface as the next launch's error: the handle goes on as it was
+            return rc;
+        }
+        if (e->traj_ring) {  // the old ring: no launch may still use it
+            HIPCHK(e, hipDeviceSynchronize());
+            e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->traj_ring));
+            HIPCHK(e, hipFree(e->traj_ring));
+        }
+        e->traj_ring = b;
+        e->traj_ring_bytes = L * per_slice;
+        R.rows = reinterpret_cast<double*>(b); b += 8 * TRAJ_COLS * NM * L;
+        R.episode = reinterpret_cast<int32_t*>(b); b += 4 * N * L;
+        R.moved = b; b += NM * L;
+        R.last = b;
+        R.L = n_slices;
+    }
+    e->traj = R;
+    e->traj_ready = true;
+    return traj_restart(e, nullptr, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_trajectory_restart(void* env, const uint8_t* world_mask, int clear, void* stream) {
+    ENTRY_POOL(e, env, "cagym_trajectory_restart");
+    if (!e->traj_ready) return fail(e, CAGYM_E_STATE, "cagym_trajectory_restart before cagym_trajectory_init");
+    ON_DEVICE(e);
+    return traj_restart(e, world_mask, clear != 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_trajectory_get(void* env, cagym_trajectory_ptrs* out) {
+    ENTRY_POOL(e, env, "cagym_trajectory_get");
+    if (!e->traj_ready) return fail(e, CAGYM_E_STATE, "cagym_trajectory_get before cagym_trajectory_init");
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    const TrajRing& R = e->traj;
+    out->rows = R.rows; out->moved = R.moved; out->episode = R.episode; out->last = R.last;
+    out->head = reinterpret_cast<const uint64_t*>(R.head); out->desync = R.desync; out->t_prev = R.t_prev; out->seen = R.seen;
+    out->n_slices = R.L;
+    return CAGYM_OK;
 }
 
 // ---- the split step (csrc/cagym_split3.h) -----------------------------------------------------------------------------------------
@@ -1883,6 +2004,8 @@ int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* bl
                                       "detach the records first");
     if (e->log_ready)
         return fail(e, CAGYM_E_STATE, "cagym_restore with an episode log initialised: its running rows would describe another timeline");
+    if (e->traj_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_restore with a trajectory ring initialised: its running values would describe another timeline");
     ON_DEVICE_VOIDS_BEGUN(e);
     return snap_launch(e, snap_state_table(e, SNAP_SCATTER), rows, nullptr, const_cast<void*>(blob), n, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1897,6 +2020,8 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
                                       "detach the records first");
     if (e->log_ready)
         return fail(e, CAGYM_E_STATE, "cagym_fork with an episode log initialised: its running rows would describe another timeline");
+    if (e->traj_ready)
+        return fail(e, CAGYM_E_STATE, "cagym_fork with a trajectory ring initialised: its running values would describe another timeline");
     if (e->cfg.n_scenarios % e->cfg.n_worlds != 0)
         return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork needs n_scenarios to be a multiple of n_worlds: otherwise two worlds can share a scenario "
                                             "slot and the copy of src's slot over dst's could hit a third world");

@@ -86,6 +86,79 @@ def to_reference_records(rec, world, dt=0.1, last_time=0.0):
     return trajs, (d["time"] + 1.0 if d is not None else last_time)
 
 
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def ring_slices(planes, world, episode):
+    """The slices of (world, episode) still in a trajectory ring, oldest first (pure array code; numpy arrays or tensors).
+    planes: "rows" [L, 13, N, M] (or [L, 13, N * M]), "moved" [L, N, M], "episode" [L, N], "last" [L, N], "head" (slices ever
+    written; slice i lives at index i % L) - env.trajectory_views(), or copies of it.
+    Returns (history [T, M, 13] in slice order, moved [T, M] bool, complete).  An agent's first row carries t_before == 0.0
+    (Agent.t starts at 0), which is how the start of an episode is recognised: `complete` means that row and the slice whose
+    `last` byte is set are both present.  Where reset(world_mask) restarted the same episode index, the newest run is returned."""
+    episode_plane, last = _host(planes["episode"]), _host(planes["last"])
+    L, N = episode_plane.shape
+    moved = _host(planes["moved"]).reshape(L, N, -1)
+    M = moved.shape[2]
+    rows = _host(planes["rows"]).reshape(L, 13, N, M)
+    head = int(np.asarray(_host(planes["head"])).reshape(-1)[0])
+    n = min(head, L)
+    order = np.arange(head - n, head) % L
+    sel = order[episode_plane[order, world] == episode]
+    H = np.transpose(rows[sel][:, :, world, :], (0, 2, 1))  # [T, M, 13]
+    mv = moved[sel, world] != 0
+    starts = np.nonzero((mv & (H[:, :, 0] == 0.0)).any(axis=1))[0]
+    if starts.size:
+        sel, H, mv = sel[starts[-1]:], H[starts[-1]:], mv[starts[-1]:]
+    complete = bool(starts.size and sel.size and last[sel[-1], world] != 0)
+    return np.ascontiguousarray(H), mv, complete
+
+
+def ring_episode(planes, world, episode, n_agents, coop):
+    """One episode out of a trajectory ring as the `rec` dict to_reference_records takes, for ONE world (pass world=0 there):
+    history [T, 1, M, 13] with every agent's rows packed to the front (the rows of agent i are history[:step_num[0, i], 0, i],
+    the history[:step_num] rule of record_episode), step_num [1, M] = the rows present, n_agents [1], coop [1, M]; "complete"
+    rides along (ring_slices).  n_agents: the episode's agent count, coop: its [M] cooperation coefficients - the pool row of
+    slot (world + episode * N) % S on a fixed pool, the episode log's n_agents under streaming."""
+    H, mv, complete = ring_slices(planes, world, episode)
+    T, M = mv.shape
+    hist = np.zeros((T, 1, M, 13), dtype=np.float64)
+    steps = mv.sum(axis=0).astype(np.int32)
+    for i in range(M):
+        hist[:steps[i], 0, i] = H[mv[:, i], i]
+    return {"history": hist, "step_num": steps[None, :], "n_agents": np.asarray([int(n_agents)], dtype=np.int32),
+            "coop": np.asarray(coop, dtype=np.float64).reshape(1, M), "complete": complete}
+
+
+def export_ring(env, path, episodes, n_agents=None, coop=None, complete_only=True):
+    """Write the reference-schema trajectory pickle of the listed (world, episode) pairs - e.g. the world / episode columns of
+    env.episode_log() - out of the env's trajectory ring (attach_trajectory_ring).  One synchronisation and one host copy of
+    the ring.  n_agents / coop: per listed episode ([K] / [K, M]); default: the pool rows of slot (world + episode * N) % S,
+    which describe the episode only on a pool that is not streamed (a streamed slot is regenerated once its episode ends:
+    pass the log's n_agents and the sampler's coefficients there).  complete_only: skip episodes whose first row or last slice
+    is no longer in the ring.  Returns the number of agent trajectories written."""
+    planes = {k: _host(v) for k, v in env.trajectory_views().items()}
+    if int(planes["desync"][0]):
+        raise RuntimeError("export_ring: the trajectory ring is out of step with the env (desync %d)" % int(planes["desync"][0]))
+    episodes = [(int(w), int(e)) for w, e in episodes]
+    if (n_agents is None or coop is None) and getattr(env, "_streaming", False):
+        raise ValueError("export_ring on a streaming env needs n_agents and coop: the pool slot of a finished episode has been regenerated")
+    sc = {k: _host(v) for k, v in env.scenarios().items()} if (n_agents is None or coop is None) else None
+    out, last = [], 0.0
+    for k, (w, e) in enumerate(episodes):
+        slot = (w + e * env.N) % env.S
+        rec = ring_episode(planes, w, e, sc["n_agents"][slot] if n_agents is None else n_agents[k],
+                           sc["coop"][slot] if coop is None else coop[k])
+        if complete_only and not rec["complete"]:
+            continue
+        trajs, last = to_reference_records(rec, 0, last_time=last)
+        out.extend(trajs)
+    with open(path, "wb") as f:
+        pickle.dump(out, f)
+    return len(out)
+
+
 def export(env, path, max_steps=1000):
     """Record one episode of every world and write the reference-schema trajectories of all of them to `path`."""
     rec = record_episode(env, max_steps)

@@ -48,18 +48,21 @@ class FlatObservation(object):
         self.agent_size = self.size // benv.M
 
     def __call__(self, obs=None):
+        """The flat rows of the env's current observation tensors, or of `obs`: a dict of tensors of the same shapes under the
+        keys "other_agents_states", "ego" and "laserscan" (e.g. step()'s info["terminal"])."""
         b = self.b
+        oas, ego, laser = (b.obs_oas, b.obs_ego, b.obs_laser) if obs is None else (obs["other_agents_states"], obs["ego"], obs.get("laserscan"))
         parts = []
         for key in self.keys:
             if key in _EGO:
                 c, w = _EGO[key]
-                parts.append(b.obs_ego[:, :, c:c + w])
+                parts.append(ego[:, :, c:c + w])
             elif key == "other_agents_states":
-                parts.append(b.obs_oas.reshape(b.N, b.M, -1))
+                parts.append(oas.reshape(b.N, b.M, -1))
             elif key == "other_agent_states":
-                parts.append(b.obs_oas[:, :, 0, :])
+                parts.append(oas[:, :, 0, :])
             elif key == "laserscan":
-                parts.append(b.obs_laser)
+                parts.append(laser)
         return torch.cat(parts, dim=2).reshape(b.N, self.size)
 
     def array_to_dict(self, row):
@@ -70,14 +73,19 @@ class FlatObservation(object):
 
 class CagymVecEnv(object):
     """n_envs = N worlds.  rews: agent 0's reward when single_agent (Config.TRAIN_SINGLE_AGENT, env.py:565-566)
-    else [N, M]."""
+    else [N, M].  terminal_observation=True: infos["terminal_observation"] is the [N, D] flat observation every world that
+    finished on this step ENDED on (DummyVecEnv's infos[i]["terminal_observation"]; the returned obs is the first one of its new
+    episode); rows are valid where dones.  It switches the env's keep_terminal_observations() on."""
 
-    def __init__(self, benv, dict_keys, single_agent=True):
+    def __init__(self, benv, dict_keys, single_agent=True, terminal_observation=False):
         self.b = benv
         self.num_envs = benv.N
         self.flat = FlatObservation(benv, dict_keys)
         self.single_agent = single_agent
         self._actions = None
+        self.terminal_observation = bool(terminal_observation)
+        if self.terminal_observation:
+            benv.keep_terminal_observations()
 
     def reset(self):
         self.b.reset()
@@ -102,6 +110,8 @@ class CagymVecEnv(object):
         infos = {"flags": info["flags"]}
         if getattr(b, "_igm", None) is not None:  # an episodic attach_ig_mcts: the team's MI reward of this step, [N] f64
             infos["team_reward"] = b.team_reward
+        if self.terminal_observation:
+            infos["terminal_observation"] = self.flat(info["terminal"])
         return self.flat(), rews, go.bool(), infos
 
     def step(self, actions):

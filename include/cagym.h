@@ -740,6 +740,67 @@ int cagym_stream_exploration_scenarios(void* env, const cagym_explore_params* pa
 int cagym_stream_set_exploration_params(void* env, const cagym_explore_params* params);
 int cagym_explore_stream_get(void* env, const int32_t** field_next, const uint64_t** fields_built);
 
+/* ---- Terminal observations and a trajectory ring under auto-reset (csrc/cagym_terminal.h) -------------------------------------------
+ * cagym_step_autoreset writes the first observation of the new episode over the one the agents ended on (DummyVecEnv hands that one
+ * to the learner as infos[i]["terminal_observation"]) and restarts the state, so the last row of every agent's global_state_history
+ * (agent.py:80-84, 198-201) is gone when the launch returns.  cagym_step followed by cagym_reset(mask = game_over, advance_episode)
+ * equals the auto-resetting launch bit for bit - outputs, state and episode statistics (tests/test_hip_parity.py, tests/test_cfg4.py)
+ * - and between those two launches both still exist.  No step, reset or roll-out kernel knows of any of this.
+ * cagym_step_autoreset_keep: cagym_step_autoreset's results in `out` and in the handle, as THREE launches chained by stream order:
+ *   1. the step without auto-reset, writing `out` (reward / flags / game_over are the terminal ones, as cagym_step_autoreset's);
+ *   2. k_terminal_capture: for every world whose game_over byte is set, its rows of out->obs_oas / obs_ego / laserscan are copied to
+ *      the same world index of `term` (rows of other worlds are NOT touched); with a trajectory ring initialised, one slice is added;
+ *   3. the reset kernel for mask = out->game_over with advance_episode, writing only the restarted worlds' observations into `out`
+ *      (with cfg.laserscan the on-demand scan follows, as in cagym_reset).  Unlike cagym_reset it enqueues no recorder restart: the
+ *      episodes ended properly, and the episode records / log are fed from `out` exactly as behind cagym_step_autoreset.
+ *   term: caller-owned DEVICE buffers shaped like their cagym_outputs counterparts; any pointer, or term itself, may be NULL.  A row is
+ *   copied where both the `out` and the `term` pointer are given.  out->game_over == NULL: a handle-owned [N] scratch takes its place.
+ *   No argument advances on the host: the call can be captured in a graph.  Generation-3 handles only (CAGYM_E_UNSUPPORTED).
+ * The trajectory ring: a dense, handle-owned ring of L = n_slices step slices, one per cagym_step_autoreset_keep:
+ *   rows [L][13][N*M] f64 in COLUMN PLANES (a wave's stores are contiguous), columns t_before, px, py, gx, gy, radius, pref_speed, vx,
+ *   vy, speed, heading, a0, a1 - the reference's row, read AFTER the move with the time stamp of before it; moved [L][N*M] u8: the agent
+ *   took this step (step_num advanced; rows of agents that did not move are stale); episode [L][N] i32: the episode index the world was
+ *   on; last [L][N] u8: that step's game_over; head, one u64: slices ever written, slice i lives at i % L; desync, one i32.
+ *   Running, the ring's own: t_prev [N,M] f64 and seen [N,M] i32, the t and step_num of every agent when the ring last saw it.
+ *   CONTRACT: fed by cagym_step_autoreset_keep only, every step exactly once and in order.  A step taken through any other entry goes
+ *   past the ring: the next slice finds agents whose step_num is not seen + 1, adds 1 to desync per such agent and resynchronises.
+ * cagym_trajectory_init: allocate and clear; t_prev / seen are taken from the current state, so a ring attached in mid-episode starts
+ *   there.  A second call clears again and may change n_slices (that synchronises the device and frees the old ring).  CAGYM_E_NOMEM
+ *   when the ring does not fit.
+ * cagym_trajectory_restart: the masked worlds (DEVICE [N] u8, NULL = all) take t_prev / seen from the current state; clear != 0 also
+ *   zeroes every slice, head and desync.
+ * cagym_trajectory_get: zero-copy DEVICE views, owned by the handle (the ring's views change when init changes n_slices).
+ * Once initialised: a successful cagym_reset enqueues the restart for its mask (the abandoned episode keeps its rows and has no `last`
+ * slice); a successful pool setter (cagym_set_scenarios, cagym_generate_*, cagym_stream_*scenarios) restarts every world and keeps the
+ * rows.  cagym_restore and cagym_fork return CAGYM_E_STATE while a ring is initialised (its running values would describe another
+ * timeline, as the log's would); cagym_snapshot stays allowed.  Handles that never called init behave as before.
+ * Errors: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before a pool is installed, and for restart / get before init;
+ * CAGYM_E_UNSUPPORTED on a handle that does not run the generation-3 kernels; CAGYM_E_INVALID for n_slices < 1 or a NULL cagym_trajectory_ptrs;
+ * CAGYM_E_DEVICE as every launching entry. */
+struct cagym_terminal_outputs {
+    float* obs_oas;   /* [N, M, M-1, 10] f32 */
+    float* obs_ego;   /* [N, M, 12]      f32 */
+    float* laserscan; /* [N, M, 16]      f32 (only when cfg.laserscan) */
+};
+typedef struct cagym_terminal_outputs cagym_terminal_outputs; /* (declared as cagym_stream_ptrs is) */
+struct cagym_trajectory_ptrs {
+    const double* rows;
+    const uint8_t* moved;
+    const int32_t* episode;
+    const uint8_t* last;
+    const uint64_t* head;
+    const int32_t* desync;
+    const double* t_prev;
+    const int32_t* seen;
+    int32_t n_slices;
+};
+typedef struct cagym_trajectory_ptrs cagym_trajectory_ptrs;
+int cagym_step_autoreset_keep(void* env, const float* ext_actions, const cagym_outputs* out, const cagym_terminal_outputs* term,
+                              void* stream);
+int cagym_trajectory_init(void* env, int n_slices, void* stream);
+int cagym_trajectory_restart(void* env, const uint8_t* world_mask, int clear, void* stream);
+int cagym_trajectory_get(void* env, cagym_trajectory_ptrs* out);
+
 #ifdef __cplusplus
 }
 #endif
