@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import torch  # (before the library is loaded: load() binds to the HIP runtime torch already mapped)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAGYM_LIB") or os.path.join(HERE, "csrc", "libcagym_hip.so")  # CAGYM_LIB: diagnostic builds
 
@@ -23,17 +25,45 @@ class CagymOutputs(C.Structure):
                 ("reward", C.c_void_p), ("flags", C.c_void_p), ("game_over", C.c_void_p)]
 
 
-STATE_FIELDS = [("pos_x", "f8"), ("pos_y", "f8"), ("vel_x", "f8"), ("vel_y", "f8"), ("heading", "f8"),
-                ("heading_ego", "f8"), ("dist_to_goal", "f8"), ("time_remaining", "f8"), ("t", "f8"),
-                ("goal_x", "f8"), ("goal_y", "f8"), ("radius", "f8"), ("pref_speed", "f8"), ("speed", "f8"),
-                ("delta_heading", "f8"), ("aux0", "f8"), ("aux1", "f8"), ("action", "f4"), ("status", "u4"),
-                ("step_num", "i4"), ("n_agents", "i4"), ("n_observed", "i4"), ("episode", "i4"),
-                ("map_bits", "u4"), ("stat_return", "f4"), ("stat_episodes", "i4"), ("stat_steps", "i4"),
-                ("stat_outcomes", "i4")]
+class _DevArray(object):
+    """Minimal __cuda_array_interface__ holder: zero-copy torch view of a raw device pointer."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<" + typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+def views(ptrs, fields, device, **sizes):
+    """Zero-copy device tensors of a struct of device pointers (or a dict of addresses): one per row (name, typestr, shape) of
+    `fields`.  A shape spells its dims: a letter is looked up in `sizes`, a digit or an int stands for itself.  u4 / u8 words come
+    as int32 / int64: the bits, in the signed types torch computes with.  A null pointer gives no entry."""
+    out = {}
+    for name, ts, shape in fields:
+        p = ptrs[name] if isinstance(ptrs, dict) else getattr(ptrs, name)
+        if p:
+            shape = [c if isinstance(c, int) else int(c) if c.isdigit() else sizes[c] for c in shape]
+            out[name] = torch.as_tensor(_DevArray(p, shape, {"u4": "i4", "u8": "i8"}.get(ts, ts)), device=device)
+    return out
+
+
+# The field tables of the pointer structs and address lists: N worlds, M agents, S pool slots, K max_obstacles, L ring rows, C = 13.
+STATE_FIELDS = [("pos_x", "f8", "NM"), ("pos_y", "f8", "NM"), ("vel_x", "f8", "NM"), ("vel_y", "f8", "NM"), ("heading", "f8", "NM"),
+                ("heading_ego", "f8", "NM"), ("dist_to_goal", "f8", "NM"), ("time_remaining", "f8", "NM"), ("t", "f8", "NM"),
+                ("goal_x", "f8", "NM"), ("goal_y", "f8", "NM"), ("radius", "f8", "NM"), ("pref_speed", "f8", "NM"), ("speed", "f8", "NM"),
+                ("delta_heading", "f8", "NM"), ("aux0", "f8", "NM"), ("aux1", "f8", "NM"), ("action", "f4", "NM2"), ("status", "u4", "NM"),
+                ("step_num", "i4", "NM"), ("n_agents", "i4", "N"), ("n_observed", "i4", "NM"), ("episode", "i4", "N"),
+                ("map_bits", "u4", ("S", 300, 10)), ("stat_return", "f4", "N"), ("stat_episodes", "i4", "N"), ("stat_steps", "i4", "N"),
+                ("stat_outcomes", "i4", "N3")]
+SCENARIO_FIELDS = [("agents6", "f8", "SM6"), ("policy", "i4", "SM"), ("dynamics", "i4", "SM"), ("n_agents", "i4", "S"), ("coop", "f8", "SM")]
+OBSTACLE_FIELDS = [("obstacles", "f8", "SK4"), ("n_obst", "i4", "S")]             # cagym_get_obstacles' two addresses
+STREAM_FIELDS = [("next_episode", "i4", "N"), ("generated", "i8", "1"), ("n_failed", "i4", "1"), ("n_lapped", "i4", "1")]
+EXPLORE_STREAM_FIELDS = [("field_next", "i4", "N"), ("fields_built", "i8", "1")]  # cagym_explore_stream_get's
+IG_FIELDS = [("edf_d2", "i4", ("S", 300, 300)), ("belief", "f8", ("N", 60, 60))]  # cagym_ig_get's
+IG_EPISODE_FIELDS = [("running", "f8", "N"), ("sum", "f8", "N"), ("last", "f8", "N"), ("episodes", "i4", "N")]  # cagym_ig_get_episode_stats'
 
 
 class CagymStatePtrs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n, _ in STATE_FIELDS]
+    _fields_ = [(n, C.c_void_p) for n, _, _ in STATE_FIELDS]
 
 
 class CagymGenParams(C.Structure):
@@ -61,7 +91,7 @@ class CagymExploreParams(C.Structure):
 
 
 class CagymScenarioPtrs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("agents6", "policy", "dynamics", "n_agents", "coop")]
+    _fields_ = [(n, C.c_void_p) for n, _, _ in SCENARIO_FIELDS]
 
 
 EPREC_KEEP = {"first": 0, "last": 1}  # CAGYM_EPREC_KEEP_*
@@ -111,7 +141,7 @@ class CagymSnapshotLayout(C.Structure):
 
 class CagymStreamPtrs(C.Structure):
     """cagym_stream_ptrs (include/cagym.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("next_episode", "generated", "n_failed", "n_lapped")]
+    _fields_ = [(n, C.c_void_p) for n, _, _ in STREAM_FIELDS]
 
 
 class CagymTerminalOutputs(C.Structure):
@@ -128,6 +158,13 @@ TRAJ_FIELDS = [("rows", "f8", "LCNM"), ("moved", "u1", "LNM"), ("episode", "i4",
 class CagymTrajectoryPtrs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in TRAJ_FIELDS] + [("n_slices", C.c_int32)]
 
+
+STRUCTS = {"cagym_config": CagymConfig, "cagym_outputs": CagymOutputs, "cagym_state_ptrs": CagymStatePtrs,
+           "cagym_scenario_ptrs": CagymScenarioPtrs, "cagym_gen_params": CagymGenParams, "cagym_gen2_params": CagymGen2Params,
+           "cagym_explore_params": CagymExploreParams, "cagym_dmcts_params": DmctsParams, "cagym_ig_greedy_params": GreedyParams,
+           "cagym_episode_record_ptrs": CagymEpisodeRecordPtrs, "cagym_episode_log_ptrs": CagymEpisodeLogPtrs,
+           "cagym_snapshot_layout": CagymSnapshotLayout, "cagym_stream_ptrs": CagymStreamPtrs,
+           "cagym_terminal_outputs": CagymTerminalOutputs, "cagym_trajectory_ptrs": CagymTrajectoryPtrs}  # every struct of include/cagym.h
 
 # ---- the prototypes of include/cagym.h: name -> argtypes; every function returns int except those of _RESTYPES ----------------
 _vp, _int, _dbl, _P = C.c_void_p, C.c_int, C.c_double, C.POINTER
@@ -215,7 +252,6 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    import torch  # noqa: F401  (maps torch/lib/libamdhip64.so before our DT_NEEDED is resolved)
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             "libcagym_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "

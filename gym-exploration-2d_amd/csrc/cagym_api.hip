@@ -123,6 +123,9 @@ struct DeviceGuard {
 #define ENTRY(e, env) ENTRY_IF(e, env, true, "")
 #define ENTRY_POOL(e, env, name) ENTRY_IF(e, env, e->scenarios_set, name " before cagym_set_scenarios")
 #define ENTRY_IG(e, env, name) ENTRY_IF(e, env, e->ig_ready, name " before cagym_ig_init")
+// ... behind ENTRY_POOL, of a call that needs what an *_init call sets up (a missing pool is reported first)
+#define REQUIRE(e, ready, name, init) \
+    if (!(ready)) return fail(e, CAGYM_E_STATE, name " before " init)
 #define ON_DEVICE(e)                                                                                       \
     DeviceGuard _guard((e)->cfg.device);                                                                   \
     if (_guard.status != hipSuccess) return fail(e, CAGYM_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_guard.status)); \
@@ -307,12 +310,31 @@ inline int traj_restart(Env* e, const uint8_t* world_mask, bool clear, hipStream
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
-// what a new pool means to the three: the records describe the pool (cleared); the log and the ring are history (their rows stay, the
-// running values go)
-inline int episodes_new_pool(Env* e, hipStream_t st) {
-    if (int rc = eprec_restart(e, nullptr, true, st)) return rc;
-    if (int rc = eplog_restart(e, nullptr, false, st)) return rc;
-    return traj_restart(e, nullptr, false, st);
+// The three behind cagym_reset - the episode the masked worlds abandon leaves no record, no row, and its rows in the ring without a
+// `last` slice - and behind a new pool (every world): the records describe the pool (cleared); the log and the ring are history (their
+// rows stay, the running values go)
+inline int episodes_restart(Env* e, const uint8_t* world_mask, bool new_pool, hipStream_t st) {
+    if (int rc = eprec_restart(e, world_mask, new_pool, st)) return rc;
+    if (int rc = eplog_restart(e, world_mask, false, st)) return rc;
+    return traj_restart(e, world_mask, false, st);
+}
+// The one allocation of a ring (e->elog_ring, e->traj_ring: `name`), made again when its size changes: the new block first, and only
+// when there is one the old block goes, behind a device sync (no launch may still use it).  quiet: a refused allocation must not
+// surface as the next launch's error - the handle goes on as it was.
+inline int ring_alloc(Env* e, void** ring, const char* name, size_t bytes, bool quiet) {
+    unsigned char* b = nullptr;
+    if (int rc = dalloc(e, &b, bytes)) {
+        if (quiet) (void)hipGetLastError();
+        return rc;
+    }
+    if (*ring) {
+        HIPCHK(e, hipDeviceSynchronize());
+        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), *ring));
+        const hipError_t s = hipFree(*ring);
+        if (s != hipSuccess) return fail(e, CAGYM_E_HIP, std::string("hipFree(e->") + name + "): " + hipGetErrorString(s));
+    }
+    *ring = b;
+    return CAGYM_OK;
 }
 // the reset kernel as cagym_reset and cagym_step_autoreset_keep launch it
 inline int launch_reset(Env* e, const uint8_t* world_mask, int advance_episode, const CagymOut& o, hipStream_t st) {
@@ -697,7 +719,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->scenarios_set = true;
     e->streaming = false;  // the pool is the caller's again
     e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
-    return episodes_new_pool(e, st);
+    return episodes_restart(e, nullptr, true, st);
 }
 
 // the handle's scenario pool as the generator kernels write it
@@ -756,7 +778,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     e->scenarios_set = true;
     e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return episodes_new_pool(e, st);
+    return episodes_restart(e, nullptr, true, st);
 }
 
 // what a parameter set of the reference samplers implies for the handle (gen2_validate)
@@ -855,7 +877,7 @@ static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int
     e->scenarios_set = true;
     e->streaming = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
-    return episodes_new_pool(e, st);
+    return episodes_restart(e, nullptr, true, st);
 }
 
 int cagym_generate_reference_scenarios(void* env, const cagym_gen2_params* params, int32_t* n_failed_host, void* stream) {
@@ -1124,9 +1146,7 @@ int cagym_reset(void* env, const uint8_t* world_mask, int advance_episode, const
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const CagymOut o = to_out(e, out, true);
     if (int rc = launch_reset(e, world_mask, advance_episode, o, st)) return rc;
-    if (int rc = eprec_restart(e, world_mask, false, st)) return rc;  // an abandoned episode leaves no record
-    if (int rc = eplog_restart(e, world_mask, false, st)) return rc;  // ... and no row
-    if (int rc = traj_restart(e, world_mask, false, st)) return rc;   // ... keeps its rows in the ring, without a `last` slice
+    if (int rc = episodes_restart(e, world_mask, false, st)) return rc;
     if (e->cfg.laserscan && o.laserscan) return cagym_laserscan(env, o.laserscan, stream);
     return CAGYM_OK;
 }
@@ -1207,17 +1227,8 @@ int cagym_trajectory_init(void* env, int n_slices, void* stream) {
     if (!e->traj_ring || R.L != n_slices) {  // the ring: once per n_slices (8-byte plane first, then the 4-byte one, then bytes)
         const size_t per_slice = 8 * TRAJ_COLS * NM + 4 * N + NM + N;
         if (L > ((size_t)1 << 46) / per_slice) return fail(e, CAGYM_E_NOMEM, "cagym_trajectory_init: the ring does not fit");
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, L * per_slice)) {
-            (void)hipGetLastError();  // a refused allocation must not surface as the next launch's error: the handle goes on as it was
-            return rc;
-        }
-        if (e->traj_ring) {  // the old ring: no launch may still use it
-            HIPCHK(e, hipDeviceSynchronize());
-            e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->traj_ring));
-            HIPCHK(e, hipFree(e->traj_ring));
-        }
-        e->traj_ring = b;
+        if (int rc = ring_alloc(e, &e->traj_ring, "traj_ring", L * per_slice, true)) return rc;
+        unsigned char* b = static_cast<unsigned char*>(e->traj_ring);
         e->traj_ring_bytes = L * per_slice;
         R.rows = reinterpret_cast<double*>(b); b += 8 * TRAJ_COLS * NM * L;
         R.episode = reinterpret_cast<int32_t*>(b); b += 4 * N * L;
@@ -1232,14 +1243,14 @@ int cagym_trajectory_init(void* env, int n_slices, void* stream) {
 
 int cagym_trajectory_restart(void* env, const uint8_t* world_mask, int clear, void* stream) {
     ENTRY_POOL(e, env, "cagym_trajectory_restart");
-    if (!e->traj_ready) return fail(e, CAGYM_E_STATE, "cagym_trajectory_restart before cagym_trajectory_init");
+    REQUIRE(e, e->traj_ready, "cagym_trajectory_restart", "cagym_trajectory_init");
     ON_DEVICE(e);
     return traj_restart(e, world_mask, clear != 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cagym_trajectory_get(void* env, cagym_trajectory_ptrs* out) {
     ENTRY_POOL(e, env, "cagym_trajectory_get");
-    if (!e->traj_ready) return fail(e, CAGYM_E_STATE, "cagym_trajectory_get before cagym_trajectory_init");
+    REQUIRE(e, e->traj_ready, "cagym_trajectory_get", "cagym_trajectory_init");
     if (!out) return fail(e, CAGYM_E_INVALID, "null out");
     const TrajRing& R = e->traj;
     out->rows = R.rows; out->moved = R.moved; out->episode = R.episode; out->last = R.last;
@@ -1831,8 +1842,8 @@ int cagym_episode_records_init(void* env, int keep, void* stream) {
 #define A(call) if (int rc = (call)) return rc;
         A(dalloc(e, &R.extra_t, S * M)); A(dalloc(e, &R.flags, S * M)); A(dalloc(e, &R.ret, S)); A(dalloc(e, &R.steps, S));
         A(dalloc(e, &R.outcome, S)); A(dalloc(e, &R.count, S)); A(dalloc(e, &R.claim, S));
-        A(dalloc(e, &R.t_run, N * M)); A(dalloc(e, &R.ret_run, N)); A(dalloc(e, &R.steps_run, N)); A(dalloc(e, &R.atgoal_run, N));
-        A(dalloc(e, &R.cursor, N)); A(dalloc(e, &R.desync, 1)); A(dalloc(e, &R.seq, 1));
+        A(dalloc(e, &R.run.t_run, N * M)); A(dalloc(e, &R.run.ret_run, N)); A(dalloc(e, &R.run.steps_run, N)); A(dalloc(e, &R.run.atgoal_run, N));
+        A(dalloc(e, &R.run.cursor, N)); A(dalloc(e, &R.run.desync, 1)); A(dalloc(e, &R.seq, 1));
         A(dalloc(e, &R.t, S * M));  // last: the handle holds the records only when every allocation succeeded
 #undef A
         e->rec = R;
@@ -1844,7 +1855,7 @@ int cagym_episode_records_init(void* env, int keep, void* stream) {
 
 int cagym_episode_records_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_records_update");
-    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_update before cagym_episode_records_init");
+    REQUIRE(e, e->rec_ready, "cagym_episode_records_update", "cagym_episode_records_init");
     if (!flags || !reward || !game_over) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_update: flags, reward and game_over are required");
     if (T < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_records_update: T must be >= 1");
     ON_DEVICE(e);
@@ -1862,19 +1873,19 @@ int cagym_episode_records_update(void* env, const uint8_t* flags, const float* r
 
 int cagym_episode_records_restart(void* env, const uint8_t* world_mask, int clear_table, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_records_restart");
-    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_restart before cagym_episode_records_init");
+    REQUIRE(e, e->rec_ready, "cagym_episode_records_restart", "cagym_episode_records_init");
     ON_DEVICE(e);
     return eprec_restart(e, world_mask, clear_table != 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out) {
     ENTRY_POOL(e, env, "cagym_episode_records_get");
-    if (!e->rec_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_records_get before cagym_episode_records_init");
+    REQUIRE(e, e->rec_ready, "cagym_episode_records_get", "cagym_episode_records_init");
     if (!out) return fail(e, CAGYM_E_INVALID, "null out");
     const EpRec& R = e->rec;
     out->t = R.t; out->extra_t = R.extra_t; out->flags = R.flags; out->ret = R.ret; out->steps = R.steps; out->outcome = R.outcome;
-    out->count = R.count; out->t_run = R.t_run; out->ret_run = R.ret_run; out->steps_run = R.steps_run; out->atgoal_run = R.atgoal_run;
-    out->cursor = R.cursor; out->desync = R.desync;
+    out->count = R.count; out->t_run = R.run.t_run; out->ret_run = R.run.ret_run; out->steps_run = R.run.steps_run;
+    out->atgoal_run = R.run.atgoal_run; out->cursor = R.run.cursor; out->desync = R.run.desync;
     return CAGYM_OK;
 }
 
@@ -1885,30 +1896,24 @@ int cagym_episode_log_init(void* env, int capacity, void* stream) {
     ON_DEVICE(e);
     const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
     EpLog G = e->elog;
-    if (!G.t_run) {  // the running block: once per handle
+    if (!G.run.t_run) {  // the running block: once per handle
         unsigned char* b = nullptr;
         if (int rc = dalloc(e, &b, 8 * (N * M + 2 * N + 2) + 4 * (4 * N + 2))) return rc;
-        G.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
-        G.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
+        G.run.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
+        G.run.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
         G.pos = reinterpret_cast<unsigned long long*>(b); b += 8 * N;
         G.seq = reinterpret_cast<unsigned long long*>(b); b += 8;
         G.head = reinterpret_cast<unsigned long long*>(b); b += 8;
-        G.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
-        G.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.run.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.run.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
+        G.run.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
         G.cnt = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.desync = reinterpret_cast<int32_t*>(b);
+        G.run.desync = reinterpret_cast<int32_t*>(b);
         e->elog = G;  // kept whatever becomes of the ring's allocation
     }
     if (!e->elog_ring || G.capacity != capacity) {  // the ring: once per capacity (8-byte columns first, then 4-byte ones, then bytes)
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, L * (8 * (2 + 2 * M) + 4 * 7 + M))) return rc;
-        if (e->elog_ring) {  // the old ring: no launch may still use it
-            HIPCHK(e, hipDeviceSynchronize());
-            e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->elog_ring));
-            HIPCHK(e, hipFree(e->elog_ring));
-        }
-        e->elog_ring = b;
+        if (int rc = ring_alloc(e, &e->elog_ring, "elog_ring", L * (8 * (2 + 2 * M) + 4 * 7 + M), false)) return rc;
+        unsigned char* b = static_cast<unsigned char*>(e->elog_ring);
         G.slice = reinterpret_cast<long long*>(b); b += 8 * L;
         G.ret = reinterpret_cast<double*>(b); b += 8 * L;
         G.t = reinterpret_cast<double*>(b); b += 8 * L * M;
@@ -1930,7 +1935,7 @@ int cagym_episode_log_init(void* env, int capacity, void* stream) {
 
 int cagym_episode_log_update(void* env, const uint8_t* flags, const float* reward, const uint8_t* game_over, int T, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_log_update");
-    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_update before cagym_episode_log_init");
+    REQUIRE(e, e->log_ready, "cagym_episode_log_update", "cagym_episode_log_init");
     if (!flags || !reward || !game_over) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_update: flags, reward and game_over are required");
     if (T < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_update: T must be >= 1");
     ON_DEVICE(e);
@@ -1948,20 +1953,21 @@ int cagym_episode_log_update(void* env, const uint8_t* flags, const float* rewar
 
 int cagym_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_log_restart");
-    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_restart before cagym_episode_log_init");
+    REQUIRE(e, e->log_ready, "cagym_episode_log_restart", "cagym_episode_log_init");
     ON_DEVICE(e);
     return eplog_restart(e, world_mask, clear_rows != 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cagym_episode_log_get(void* env, cagym_episode_log_ptrs* out) {
     ENTRY_POOL(e, env, "cagym_episode_log_get");
-    if (!e->log_ready) return fail(e, CAGYM_E_STATE, "cagym_episode_log_get before cagym_episode_log_init");
+    REQUIRE(e, e->log_ready, "cagym_episode_log_get", "cagym_episode_log_init");
     if (!out) return fail(e, CAGYM_E_INVALID, "null out");
     const EpLog& G = e->elog;
     out->key = G.key; out->world = G.world; out->episode = G.episode; out->slice = reinterpret_cast<const int64_t*>(G.slice); out->steps = G.steps;
     out->ret = G.ret; out->outcome = G.outcome; out->n_agents = G.n_agents; out->n_obst = G.n_obst; out->t = G.t; out->extra_t = G.extra_t;
-    out->flags = G.flags; out->t_run = G.t_run; out->ret_run = G.ret_run; out->steps_run = G.steps_run; out->atgoal_run = G.atgoal_run;
-    out->cursor = G.cursor; out->head = reinterpret_cast<const uint64_t*>(G.head); out->desync = G.desync; out->capacity = G.capacity;
+    const EpRunning& Q = G.run;
+    out->flags = G.flags; out->t_run = Q.t_run; out->ret_run = Q.ret_run; out->steps_run = Q.steps_run; out->atgoal_run = Q.atgoal_run;
+    out->cursor = Q.cursor; out->head = reinterpret_cast<const uint64_t*>(G.head); out->desync = Q.desync; out->capacity = G.capacity;
     return CAGYM_OK;
 }
 
@@ -1977,6 +1983,17 @@ int cagym_snapshot_layout_of(void* env, cagym_snapshot_layout* out) {
 static int snap_check_blob(Env* e, const char* what, const void* blob, int n) {
     if (n < 0 || n > e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, std::string(what) + ": n must be in [0, n_worlds]");
     if (!blob || (reinterpret_cast<uintptr_t>(blob) & 15)) return fail(e, CAGYM_E_INVALID, std::string(what) + ": the blob must be a 16-byte aligned device buffer");
+    return CAGYM_OK;
+}
+
+// cagym_restore and cagym_fork move worlds onto another timeline: what cannot follow them there
+static int refuse_other_timeline(Env* e, const char* what) {
+    const std::string w(what);
+    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, w + " on a streaming handle: the ring of scenario slots is not part of a snapshot");
+    if (e->rec_ready)
+        return fail(e, CAGYM_E_STATE, w + " with episode records initialised: their running rows would describe another timeline; detach the records first");
+    if (e->log_ready) return fail(e, CAGYM_E_STATE, w + " with an episode log initialised: its running rows would describe another timeline");
+    if (e->traj_ready) return fail(e, CAGYM_E_STATE, w + " with a trajectory ring initialised: its running values would describe another timeline");
     return CAGYM_OK;
 }
 
@@ -1998,14 +2015,7 @@ int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* bl
         layout->reserved != own.reserved || layout->row_bytes != own.row_bytes)
         return fail(e, CAGYM_E_INVALID, "cagym_restore: the blob's layout is not this handle's (n_worlds, max_agents, n_scenarios, max_obstacles, "
                                         "cagym_ig_init done or not, magic and version must all match)");
-    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_restore on a streaming handle: the ring of scenario slots is not part of a snapshot");
-    if (e->rec_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_restore with episode records initialised: their running rows would describe another timeline; "
-                                      "detach the records first");
-    if (e->log_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_restore with an episode log initialised: its running rows would describe another timeline");
-    if (e->traj_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_restore with a trajectory ring initialised: its running values would describe another timeline");
+    if (int rc = refuse_other_timeline(e, "cagym_restore")) return rc;
     ON_DEVICE_VOIDS_BEGUN(e);
     return snap_launch(e, snap_state_table(e, SNAP_SCATTER), rows, nullptr, const_cast<void*>(blob), n, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2014,14 +2024,7 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
     ENTRY_POOL(e, env, "cagym_fork");
     if (n < 0 || n > e->cfg.n_worlds) return fail(e, CAGYM_E_INVALID, "cagym_fork: n must be in [0, n_worlds]");
     if (n > 0 && (!src || !dst)) return fail(e, CAGYM_E_INVALID, "cagym_fork: null src / dst");
-    if (e->streaming) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork on a streaming handle: the ring of scenario slots is not part of a snapshot");
-    if (e->rec_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_fork with episode records initialised: their running rows would describe another timeline; "
-                                      "detach the records first");
-    if (e->log_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_fork with an episode log initialised: its running rows would describe another timeline");
-    if (e->traj_ready)
-        return fail(e, CAGYM_E_STATE, "cagym_fork with a trajectory ring initialised: its running values would describe another timeline");
+    if (int rc = refuse_other_timeline(e, "cagym_fork")) return rc;
     if (e->cfg.n_scenarios % e->cfg.n_worlds != 0)
         return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork needs n_scenarios to be a multiple of n_worlds: otherwise two worlds can share a scenario "
                                             "slot and the copy of src's slot over dst's could hit a third world");

@@ -31,12 +31,7 @@ struct EpLog {
     int32_t *outcome, *n_agents, *n_obst;
     double *t, *extra_t;
     uint8_t* flags;
-    // running [N, ...], the log's own
-    double *t_run, *ret_run;
-    int32_t* steps_run;
-    uint32_t* atgoal_run;
-    int32_t* cursor;
-    int32_t* desync;
+    EpRunning run;             // the log's own
     unsigned long long* seq;   // slices fed since the last clear
     unsigned long long* head;  // rows ever appended since the last clear
     // between the launches of one update
@@ -47,18 +42,6 @@ struct EpLog {
 
 #define EPLOG_NT_SCAN 1024 /* lanes of the single scan workgroup */
 #define EPLOG_CNT_WAVES 16 /* waves per workgroup of the count pass, each on its own slices */
-
-// the running arrays as the recorder's device functions take them (eprec_load / eprec_store / eprec_check)
-__device__ __forceinline__ EpRec eplog_running(const EpLog& G) {
-    EpRec E{};
-    E.t_run = G.t_run;
-    E.ret_run = G.ret_run;
-    E.steps_run = G.steps_run;
-    E.atgoal_run = G.atgoal_run;
-    E.cursor = G.cursor;
-    E.desync = G.desync;
-    return E;
-}
 
 // grid = ceil(N / 64), 64 x EPLOG_CNT_WAVES lanes: wave y sums the slices y, y + EPLOG_CNT_WAVES, ... of 64 worlds (one lane per
 // world: a slice's 64 bytes are contiguous), the waves' sums meet in LDS and wave 0 adds them up
@@ -114,13 +97,12 @@ __global__ void __launch_bounds__(EPREC_NT) k_episode_log_write(CagymDev D, EpLo
                                                                 const float* __restrict__ reward, const uint8_t* __restrict__ game_over,
                                                                 int T) {
     const int M = D.M;
-    const EpRec E = eplog_running(G);
     const EpLane L = eprec_lane(D.N, M, blockIdx.x * (EPREC_NT / CAGYM_WAVE) + (threadIdx.x >> 6));
     const unsigned long long head = *G.head, seq0 = *G.seq - (unsigned long long)T, cap = (unsigned long long)G.capacity;
     EpRun R{};
     unsigned long long pos = 0;
     if (L.valid) {
-        R = eprec_load(E, L, M);
+        R = eprec_load(G.run, L, M);
         pos = G.pos[L.world];
     }
     for (int t = 0; t < T; t++) {
@@ -155,26 +137,16 @@ __global__ void __launch_bounds__(EPREC_NT) k_episode_log_write(CagymDev D, EpLo
             eprec_next(R);
         }
     }
-    eprec_check(D, E, L, R);
-    eprec_store(E, L, M, R);
+    eprec_check(D, G.run, L, R);
+    eprec_store(G.run, L, M, R);
 }
 
-// The masked worlds (null = all) forget the episode in progress and take the handle's episode index; clear_rows: every row of the
-// ring, head, the slice counter and desync as cagym_episode_log_init leaves them.  Grid-stride over max(N, capacity) * M.
+// eprec_forget; clear_rows: every row of the ring, head, the slice counter and desync as cagym_episode_log_init leaves them.
+// Grid-stride over max(N, capacity) * M.
 __global__ void __launch_bounds__(256) k_episode_log_restart(CagymDev D, EpLog G, const uint8_t* __restrict__ world_mask, int clear_rows) {
-    const size_t NM = (size_t)D.N * D.M, LM = (size_t)G.capacity * D.M, stride = (size_t)gridDim.x * blockDim.x;
+    const size_t LM = (size_t)G.capacity * D.M, stride = (size_t)gridDim.x * blockDim.x;
     const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (size_t i = i0; i < NM; i += stride) {
-        const size_t w = i / D.M;
-        if (world_mask && !world_mask[w]) continue;
-        G.t_run[i] = 0.0;
-        if (i - w * D.M == 0) {
-            G.ret_run[w] = 0.0;
-            G.steps_run[w] = 0;
-            G.atgoal_run[w] = 0u;
-            G.cursor[w] = D.episode[w];
-        }
-    }
+    eprec_forget(D, G.run, world_mask, i0, stride);
     if (!clear_rows) return;
     for (size_t i = i0; i < LM; i += stride) {
         G.t[i] = 0.0;
@@ -193,7 +165,7 @@ __global__ void __launch_bounds__(256) k_episode_log_restart(CagymDev D, EpLog G
         }
     }
     if (i0 == 0) {
-        *G.desync = 0;
+        *G.run.desync = 0;
         *G.seq = 0ull;
         *G.head = 0ull;
     }

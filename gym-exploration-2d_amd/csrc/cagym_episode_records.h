@@ -24,6 +24,15 @@
 #pragma once
 #include "cagym_device.h"
 
+// the episode in progress of every world, [N, ...] (t_run [N, M]), and the desync word: the recorder and the log each keep their own
+struct EpRunning {
+    double *t_run, *ret_run;
+    int32_t* steps_run;
+    uint32_t* atgoal_run;
+    int32_t* cursor;
+    int32_t* desync;
+};
+
 struct EpRec {
     // table [S, ...]
     double *t, *extra_t;
@@ -31,12 +40,7 @@ struct EpRec {
     double* ret;
     int32_t *steps, *outcome, *count;
     unsigned long long* claim;  // [S] key of the episode that owns the row (shared kernel only)
-    // running [N, ...]
-    double *t_run, *ret_run;
-    int32_t* steps_run;
-    uint32_t* atgoal_run;
-    int32_t* cursor;
-    int32_t* desync;
+    EpRunning run;
     unsigned long long* seq;  // slices fed since the last clear (shared kernel only)
     int keep;                 // CAGYM_EPREC_KEEP_*
 };
@@ -66,7 +70,7 @@ struct EpRun {
     int steps, cursor;
     bool atgoal;
 };
-__device__ __forceinline__ EpRun eprec_load(const EpRec& E, const EpLane& L, int M) {
+__device__ __forceinline__ EpRun eprec_load(const EpRunning& E, const EpLane& L, int M) {
     EpRun R;
     R.t = E.t_run[(size_t)L.world * M + L.slot];
     R.ret = E.ret_run[L.world];
@@ -76,7 +80,7 @@ __device__ __forceinline__ EpRun eprec_load(const EpRec& E, const EpLane& L, int
     return R;
 }
 // every lane of the wave calls this (ballot); invalid lanes store nothing
-__device__ __forceinline__ void eprec_store(const EpRec& E, const EpLane& L, int M, const EpRun& R) {
+__device__ __forceinline__ void eprec_store(const EpRunning& E, const EpLane& L, int M, const EpRun& R) {
     const uint64_t b = __ballot(L.valid && R.atgoal);
     if (!L.valid) return;
     E.t_run[(size_t)L.world * M + L.slot] = R.t;
@@ -164,7 +168,7 @@ __device__ __forceinline__ void eprec_finish(const CagymDev& D, const EpRec& E, 
 
 // After the last slice: the recorder's episode index and step count against the ones the step kernels keep.  A skipped, doubled
 // or non-auto-reset step shows here: count it, take the handle's values and drop the world's running values.
-__device__ __forceinline__ void eprec_check(const CagymDev& D, const EpRec& E, const EpLane& L, EpRun& R) {
+__device__ __forceinline__ void eprec_check(const CagymDev& D, const EpRunning& E, const EpLane& L, EpRun& R) {
     if (!L.valid) return;
     const int ep = D.episode[L.world], len = D.ep_len[L.world];
     if (R.cursor == ep && R.steps == len) return;
@@ -183,7 +187,7 @@ __global__ void __launch_bounds__(EPREC_NT) k_episode_records_update(CagymDev D,
     const int M = D.M;
     const EpLane L = eprec_lane(D.N, M, blockIdx.x * (EPREC_NT / CAGYM_WAVE) + (threadIdx.x >> 6));
     EpRun R{};
-    if (L.valid) R = eprec_load(E, L, M);
+    if (L.valid) R = eprec_load(E.run, L, M);
     for (int t = 0; t < T; t++) {
         uint32_t f = 0;
         bool go = false;
@@ -202,8 +206,8 @@ __global__ void __launch_bounds__(EPREC_NT) k_episode_records_update(CagymDev D,
         cnt = __shfl(cnt, L.base);
         eprec_finish(D, E, L, R, go, E.keep == CAGYM_EPREC_KEEP_LAST || cnt == 0, f);
     }
-    eprec_check(D, E, L, R);
-    eprec_store(E, L, M, R);
+    eprec_check(D, E.run, L, R);
+    eprec_store(E.run, L, M, R);
 }
 
 // any S: one workgroup, slices in order, rows owned by key (see the head of this file).  grid = 1, EPREC_NT_SHARED lanes.
@@ -220,7 +224,7 @@ __global__ void __launch_bounds__(EPREC_NT_SHARED) k_episode_records_update_shar
             const EpLane L = eprec_lane(D.N, M, g);
             EpRun R{};
             if (L.valid) {
-                R = eprec_load(E, L, M);
+                R = eprec_load(E.run, L, M);
                 eprec_advance(D, L, R, flags, reward, (size_t)t);
                 if (L.slot == 0 && game_over[(size_t)t * D.N + L.world]) {
                     const int s = eprec_scenario(D, L.world, R.cursor);
@@ -229,7 +233,7 @@ __global__ void __launch_bounds__(EPREC_NT_SHARED) k_episode_records_update_shar
                     else atomicMin(&E.claim[s], key);
                 }
             }
-            eprec_store(E, L, M, R);
+            eprec_store(E.run, L, M, R);
         }
         __syncthreads();
         // phase 2: the owner of a row writes it, every finisher counts
@@ -241,7 +245,7 @@ __global__ void __launch_bounds__(EPREC_NT_SHARED) k_episode_records_update_shar
             uint32_t f = 0;
             bool write = false;
             if (go) {
-                R = eprec_load(E, L, M);
+                R = eprec_load(E.run, L, M);
                 f = flags[((size_t)t * D.N + L.world) * M + L.slot];
                 const int s = eprec_scenario(D, L.world, R.cursor);
                 const unsigned long long key = (seq0 + (unsigned long long)t) * (unsigned long long)D.N + (unsigned long long)L.world + 1ull;
@@ -252,25 +256,24 @@ __global__ void __launch_bounds__(EPREC_NT_SHARED) k_episode_records_update_shar
             eprec_finish(D, E, L, R, go, write, f);
             EpLane Ls = L;  // only the worlds that finished changed
             Ls.valid = go;
-            eprec_store(E, Ls, M, R);
+            eprec_store(E.run, Ls, M, R);
         }
         __syncthreads();
     }
     for (int g = wave; g < ngroups; g += nwaves) {
         const EpLane L = eprec_lane(D.N, M, g);
         EpRun R{};
-        if (L.valid) R = eprec_load(E, L, M);
-        eprec_check(D, E, L, R);
-        eprec_store(E, L, M, R);
+        if (L.valid) R = eprec_load(E.run, L, M);
+        eprec_check(D, E.run, L, R);
+        eprec_store(E.run, L, M, R);
     }
     if (threadIdx.x == 0) *E.seq = seq0 + (unsigned long long)T;
 }
 
-// The masked worlds (null = all) forget the episode in progress and take the handle's episode index; clear_table: every row,
-// the keys, the slice counter and desync as cagym_episode_records_init leaves them.  Grid-stride over max(N, S) * M.
-__global__ void __launch_bounds__(256) k_episode_records_restart(CagymDev D, EpRec E, const uint8_t* __restrict__ world_mask, int clear_table) {
-    const size_t NM = (size_t)D.N * D.M, SM = (size_t)D.S * D.M, stride = (size_t)gridDim.x * blockDim.x;
-    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+// The masked worlds (null = all) forget the episode in progress and take the handle's episode index: the first loop of both restart
+// kernels, grid-stride over N * M from i0.
+__device__ __forceinline__ void eprec_forget(const CagymDev& D, const EpRunning& E, const uint8_t* __restrict__ world_mask, size_t i0, size_t stride) {
+    const size_t NM = (size_t)D.N * D.M;
     for (size_t i = i0; i < NM; i += stride) {
         const size_t w = i / D.M;
         if (world_mask && !world_mask[w]) continue;
@@ -282,6 +285,14 @@ __global__ void __launch_bounds__(256) k_episode_records_restart(CagymDev D, EpR
             E.cursor[w] = D.episode[w];
         }
     }
+}
+
+// eprec_forget; clear_table: every row, the keys, the slice counter and desync as cagym_episode_records_init leaves them.
+// Grid-stride over max(N, S) * M.
+__global__ void __launch_bounds__(256) k_episode_records_restart(CagymDev D, EpRec E, const uint8_t* __restrict__ world_mask, int clear_table) {
+    const size_t SM = (size_t)D.S * D.M, stride = (size_t)gridDim.x * blockDim.x;
+    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    eprec_forget(D, E.run, world_mask, i0, stride);
     if (!clear_table) return;
     for (size_t i = i0; i < SM; i += stride) {
         E.t[i] = 0.0;
@@ -296,7 +307,7 @@ __global__ void __launch_bounds__(256) k_episode_records_restart(CagymDev D, EpR
         }
     }
     if (i0 == 0) {
-        *E.desync = 0;
+        *E.run.desync = 0;
         *E.seq = 0ull;
     }
 }

@@ -26,18 +26,11 @@ class InfoGain(object):
         self.b = benv
         self.L = benv.L
         self.fov, self.range, self.xdt, self.dt = float(fov_rad), float(sens_range), int(xdt), float(dt)
-        vp = C.c_void_p
         _lib.call(self.L, self.b.h, "cagym_ig_init", benv._stream())
-        d2, bel = vp(), vp()
-        _lib.call(self.L, self.b.h, "cagym_ig_get", C.byref(d2), C.byref(bel))
-        from .batched_env import _DevArray
-        self.edf_d2 = torch.as_tensor(_DevArray(d2.value, (benv.S, 300, 300), "i4"), device=benv.device)
-        self.belief = torch.as_tensor(_DevArray(bel.value, (benv.N, 60, 60), "f8"), device=benv.device)
-        acc = [vp() for _ in range(4)]
-        _lib.call(self.L, self.b.h, "cagym_ig_get_episode_stats", *[C.byref(a) for a in acc])
+        v = benv._address_views("cagym_ig_get", _lib.IG_FIELDS)
+        self.edf_d2, self.belief = v["edf_d2"], v["belief"]
         # the team reward's per-world episode accumulators (cagym_ig_episode_boundary); zeroed by cagym_ig_init
-        self.episode_stats = {k: torch.as_tensor(_DevArray(a.value, (benv.N,), ts), device=benv.device)
-                              for k, a, ts in zip(("running", "sum", "last", "episodes"), acc, ("f8", "f8", "f8", "i4"))}
+        self.episode_stats = benv._address_views("cagym_ig_get_episode_stats", _lib.IG_EPISODE_FIELDS)
 
     def _t(self, x, dtype, shape=None):
         t = torch.as_tensor(x, device=self.b.device).to(dtype)

@@ -77,9 +77,14 @@ def _c_compiler():
 
 
 def _header_struct_fields():
-    """struct name -> field names in order, from the header's typedefs (`double *a, *b;` and `double v[3], w[3];` included)."""
+    """struct name -> field names in order, from the header's typedefs (`double *a, *b;` and `double v[3], w[3];` included), in
+    both forms the header declares them: `typedef struct [name] { ... } name;` and `struct name { ... }; typedef struct name name;`."""
     out = {}
-    for body, name in re.findall(r"typedef\s+struct(?:\s+\w+)?\s*\{(.*?)\}\s*(\w+)\s*;", _header_source(), flags=re.S):
+    src = _header_source()
+    defs = re.findall(r"typedef\s+struct(?:\s+\w+)?\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)
+    defs += [(body, name) for name, body in re.findall(r"^struct\s+(\w+)\s*\{(.*?)\}\s*;", src, flags=re.S | re.M)
+             if re.search(r"typedef\s+struct\s+%s\s+%s\s*;" % (name, name), src)]
+    for body, name in defs:
         fields = []
         for decl in body.split(";"):
             decl = decl.strip()
@@ -92,12 +97,9 @@ def _header_struct_fields():
 def test_struct_mirrors_match_the_header_layout(tmp_path):
     """sizeof and every field's name and offsetof, as the host C compiler lays out include/cagym.h, against the ctypes mirrors."""
     lib = __import__("importlib").import_module("gym-exploration-2d_amd._lib")
-    mirrors = {"cagym_config": lib.CagymConfig, "cagym_outputs": lib.CagymOutputs, "cagym_state_ptrs": lib.CagymStatePtrs,
-               "cagym_scenario_ptrs": lib.CagymScenarioPtrs, "cagym_gen_params": lib.CagymGenParams,
-               "cagym_gen2_params": lib.CagymGen2Params, "cagym_dmcts_params": lib.DmctsParams,
-               "cagym_ig_greedy_params": lib.GreedyParams, "cagym_episode_record_ptrs": lib.CagymEpisodeRecordPtrs}
+    mirrors = lib.STRUCTS
     header = _header_struct_fields()
-    assert sorted(header) == sorted(mirrors)  # the package mirrors every struct the header defines
+    assert len(header) == 15 and sorted(header) == sorted(mirrors)  # the package mirrors every struct the header defines
     lines = []
     for name, fields in header.items():
         lines.append('printf("%s %%d\\n", (int)sizeof(%s));' % (name, name))
