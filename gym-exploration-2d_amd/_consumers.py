@@ -60,11 +60,14 @@ class _ConsumersMixin(object):
 
     def _after_steps(self, auto_reset, flags, reward, game_over, T):
         """What follows the step launch(es) of one call on the stream, in this order: the episode log's update (it reads the pool
-        slot of the episode that ended, which the refill regenerates next), the stream's refill, the records' update."""
+        slot of the episode that ended, which the refill regenerates next), the replay harvest (attach_replay with outcomes: it reads
+        the rows the update appended and the key table of the same slots), the stream's refill, the records' update."""
         if self._log is not None:
             rc = self._log_fn(self.h, flags.data_ptr(), reward.data_ptr(), game_over.data_ptr(), int(T), self._stream())
             if rc:
                 _lib.check(self.L, self.h, rc, "cagym_episode_log_update")
+            if self._replay is not None and self._replay["mask"]:
+                self._harvest()
         if self._streaming and auto_reset:
             self._refill()
         if self._rec is not None:

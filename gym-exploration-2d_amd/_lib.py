@@ -58,6 +58,10 @@ SCENARIO_FIELDS = [("agents6", "f8", "SM6"), ("policy", "i4", "SM"), ("dynamics"
 OBSTACLE_FIELDS = [("obstacles", "f8", "SK4"), ("n_obst", "i4", "S")]             # cagym_get_obstacles' two addresses
 STREAM_FIELDS = [("next_episode", "i4", "N"), ("generated", "i8", "1"), ("n_failed", "i4", "1"), ("n_lapped", "i4", "1")]
 EXPLORE_STREAM_FIELDS = [("field_next", "i4", "N"), ("fields_built", "i8", "1")]  # cagym_explore_stream_get's
+# cagym_stream_replay_get's addresses (Q = the buffer's capacity); REPLAY_WORDS names the six u64 of `words`
+REPLAY_FIELDS = [("buf_key", "u4", "Q"), ("words", "u8", "6"), ("slot_key", "u4", "S"), ("slot_gen", "u4", "S")]
+REPLAY_WORDS = ("count", "harvested", "pushed", "replayed", "n_missed", "n_stale")
+REPLAY_OUTCOMES = {"collision": 1, "goal": 2, "stuck": 4}  # the episode log's outcome bits
 IG_FIELDS = [("edf_d2", "i4", ("S", 300, 300)), ("belief", "f8", ("N", 60, 60))]  # cagym_ig_get's
 IG_EPISODE_FIELDS = [("running", "f8", "N"), ("sum", "f8", "N"), ("last", "f8", "N"), ("episodes", "i4", "N")]  # cagym_ig_get_episode_stats'
 
@@ -230,6 +234,11 @@ _ARGTYPES = {
     "cagym_stream_set_params": [_vp, _P(CagymGen2Params)],
     "cagym_stream_get": [_vp, _P(CagymStreamPtrs)],
     "cagym_stream_stop": [_vp],
+    "cagym_stream_replay_init": [_vp, _int, C.c_uint64, _vp],
+    "cagym_stream_replay_set": [_vp, _dbl, C.c_uint32],
+    "cagym_stream_replay_push": [_vp, _vp, _int, _vp],
+    "cagym_stream_replay_harvest": [_vp, _vp],
+    "cagym_stream_replay_get": [_vp, _P(_vp), _P(_vp), _P(_vp), _P(_vp), _P(C.c_int)],
     "cagym_generate_exploration_scenarios": [_vp, _P(CagymExploreParams), _P(C.c_int32), _vp],
     "cagym_stream_exploration_scenarios": [_vp, _P(CagymExploreParams), _P(C.c_int32), _vp],
     "cagym_stream_set_exploration_params": [_vp, _P(CagymExploreParams)],

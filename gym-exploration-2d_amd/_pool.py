@@ -24,12 +24,16 @@ class _PoolMixin(object):
         self._streaming = False   # stream_reference_scenarios: one cagym_stream_refill behind every episode-advancing call
         self._stream_views = None
         self._explore_views = None
+        self._replay = None       # attach_replay: {"capacity", "p", "mask"} while the stream's replay is armed
+        self._replay_views = None
+        self._harvest_fn = self.L.cagym_stream_replay_harvest
 
     def _pool_committed(self, streaming, policies, n_ig):
         """Host state after a pool was committed (as the library: a new pool ends the stream unless it starts one).  An attached IG
         team is detached when the team size is unknown (a generated pool's robot count is not known on the host) or the planner was
         sized for another team; else it gets fresh beliefs on the new rasters' fields (cagym_ig_init; on a stream it arms the refresh)."""
         self._streaming, self._pool_policies, self._n_ig = streaming, policies, n_ig
+        self._replay = None  # (a new stream starts un-armed)
         if n_ig is None or (self._igm is not None and n_ig != self._igm.R):
             self.detach_ig_mcts()
         if self._igm is not None:
@@ -164,6 +168,7 @@ class _PoolMixin(object):
         """End the stream: the pool stays as it is and is replayed from here on, as a fixed pool is."""
         _lib.call(self.L, self.h, "cagym_stream_stop")
         self._streaming = False
+        self._replay = None
 
     def stream_stats(self):
         """Host integers of the stream (this synchronises): generated (slots generated since stream_reference_scenarios, its first
@@ -179,6 +184,90 @@ class _PoolMixin(object):
         """Zero-copy device view of next_episode [N] i32: the first episode of each world whose slot has not been generated."""
         self.stream_stats()
         return self._stream_views["next_episode"]
+
+    # ---- replay of failed scenarios (include/cagym.h: cagym_stream_replay_*) ------------------------------------------------------
+    @staticmethod
+    def _outcome_mask(outcomes):
+        names = [outcomes] if isinstance(outcomes, str) else list(outcomes or ())
+        bad = [n for n in names if n not in _lib.REPLAY_OUTCOMES]
+        if bad:
+            raise ValueError("replay outcomes must be among %s, got %r" % (", ".join(sorted(_lib.REPLAY_OUTCOMES)), bad[0]))
+        return sum({_lib.REPLAY_OUTCOMES[n] for n in names})
+
+    def attach_replay(self, capacity=4096, p=0.25, outcomes=("collision", "stuck"), seed=0):
+        """Hard-case replay on a stream_reference_scenarios stream: a device buffer of `capacity` stream keys, filled from the
+        attached episode log - one harvest launch behind every log update appends the key of each finished episode whose outcome is
+        among `outcomes` ("collision", "goal", "stuck") - or by replay_push(); from now on the refill generates each slot from a key
+        sampled from the buffer with probability p (with replacement; a key that fails again is appended again and so weighs more)
+        and from its fresh key w + e * N otherwise.  The draw is a pure function of (seed, w + e * N, p, buffer):
+        scenarios.replay_choice states it.  The log's key column and stream_keys() then name the scenario each episode really ran,
+        and a logged failure stays reproducible from its key.  outcomes=None: push-only (no harvest launch).  The buffer holds for
+        one parameter set: set_stream_params() empties it at the next harvest or push.  There is no detach - set_replay(p=0)
+        pauses -; stop_streaming() and every pool setter end it, and a new stream starts un-armed.  Attaching again clears the
+        buffer and may change the capacity.  Raises RuntimeError when not streaming, on an exploration stream, or with outcomes
+        but no attached episode log."""
+        mask = self._outcome_mask(outcomes)
+        if mask and self._streaming and self._log is None:
+            raise RuntimeError("attach_replay(outcomes=%r) without an episode log: the buffer is harvested from the log's rows; "
+                               "attach_episode_log() first, or outcomes=None to push keys yourself" % (outcomes,))
+        _lib.call(self.L, self.h, "cagym_stream_replay_init", int(capacity), int(seed) & 0xFFFFFFFFFFFFFFFF, self._stream())
+        self._replay, self._replay_views = {"capacity": int(capacity), "p": 0.0, "mask": 0}, None
+        _lib.call(self.L, self.h, "cagym_stream_replay_set", float(p), mask)
+        self._replay.update(p=float(p), mask=mask)
+        return self
+
+    def _refuse_without_replay(self, what):
+        if self._replay is None:
+            raise RuntimeError("%s() without replay: attach_replay() first" % what)
+
+    def set_replay(self, p=None, outcomes=None):
+        """Change the replay probability and / or the harvested outcomes (None: as it is); takes effect at the next launch.
+        p=0 is the pause: the per-slot key tables stay maintained and the harvest goes on."""
+        self._refuse_without_replay("set_replay")
+        mask = self._replay["mask"] if outcomes is None else self._outcome_mask(outcomes)
+        if mask and self._log is None:
+            raise RuntimeError("set_replay(outcomes=%r) without an episode log: attach_episode_log() first" % (outcomes,))
+        p = self._replay["p"] if p is None else float(p)
+        _lib.call(self.L, self.h, "cagym_stream_replay_set", p, mask)
+        self._replay.update(p=p, mask=mask)
+
+    def replay_push(self, keys):
+        """Append stream keys (any integer sequence or tensor; taken mod 2^32) to the replay buffer, in order, on the current stream."""
+        self._refuse_without_replay("replay_push")
+        k = torch.as_tensor(keys, device=self.device).to(torch.int64).bitwise_and(0xFFFFFFFF).flatten()
+        k = torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32).contiguous()  # the u32 bits
+        _lib.call(self.L, self.h, "cagym_stream_replay_push", k.data_ptr(), int(k.numel()), self._stream())
+
+    def replay_views(self):
+        """Zero-copy device views of the replay state, no synchronisation: buf_key [capacity] (u32 bits as int32; entry i since the
+        last clear lives at i % capacity), words [6] i64 (_lib.REPLAY_WORDS: count, harvested, pushed, replayed, n_missed,
+        n_stale), slot_key [S] (u32 bits as int32) and slot_gen [S] i32."""
+        if self._replay_views is None:
+            a = [C.c_void_p() for _ in _lib.REPLAY_FIELDS]
+            q = C.c_int(0)
+            _lib.call(self.L, self.h, "cagym_stream_replay_get", *([C.byref(x) for x in a] + [C.byref(q)]))
+            self._replay_views = _lib.views({f[0]: x.value for f, x in zip(_lib.REPLAY_FIELDS, a)}, _lib.REPLAY_FIELDS, self.device,
+                                            S=self.S, Q=int(q.value))
+        return dict(self._replay_views)
+
+    def replay_stats(self):
+        """Host integers of the replay buffer (this synchronises): count (keys appended since the last clear), harvested, pushed,
+        replayed (slots generated from a buffered key), n_missed (log rows overwritten before the harvest saw them), n_stale
+        (rows of slots generated under an earlier parameter set), live = min(count, capacity), capacity, p."""
+        self._refuse_without_replay("replay_stats")
+        st = dict(zip(_lib.REPLAY_WORDS, self.replay_views()["words"].tolist()))
+        st.update(live=min(st["count"], self._replay["capacity"]), capacity=self._replay["capacity"], p=self._replay["p"])
+        return st
+
+    def stream_keys(self):
+        """Zero-copy device view of slot_key [S] (u32 bits as int32): the stream key each pool slot was generated from."""
+        self._refuse_without_replay("stream_keys")
+        return self.replay_views()["slot_key"]
+
+    def _harvest(self):
+        rc = self._harvest_fn(self.h, self._stream())
+        if rc:
+            _lib.check(self.L, self.h, rc, "cagym_stream_replay_harvest")
 
     # ---- exploration worlds (include/cagym.h: cagym_generate_exploration_scenarios, cagym_stream_exploration_*) -----------------
     def _explore_params(self, kinds, seed, n_robots, n_targets, n_obst, target_radius, robot_pref_speed, max_tries):

@@ -31,6 +31,7 @@
 #include "cagym_snapshot.h"
 #include "cagym_stream.h"
 #include "cagym_explore.h"
+#include "cagym_replay.h"
 #include "cagym_terminal.h"
 
 namespace {
@@ -75,6 +76,13 @@ struct Env {
     bool explore_stream = false;     // while streaming: cagym_stream_exploration_scenarios started the ring (csrc/cagym_explore.h)
     ExploreTeam stream_team{};       // its team edit (cagym_stream_set_exploration_params replaces it together with stream_P)
     ExploreDev explore{};            // the field refresh's device words (allocated by the first cagym_stream_exploration_scenarios)
+    bool replay_on = false;          // while streaming: cagym_stream_replay_init armed the replay refill (csrc/cagym_replay.h)
+    ReplayDev replay{};              // its device words and per-slot tables (allocated by the first cagym_stream_replay_init)
+    void* replay_ring = nullptr;     // the buffer's one allocation (once per capacity)
+    double replay_p = 0.0;           // cagym_stream_replay_set
+    uint32_t replay_mask = 0;
+    uint64_t replay_seed = 0;
+    uint32_t stream_gen = 1;         // parameter generation: 1 at the stream's start, + 1 with every cagym_stream_set_params
     uint8_t* go_scratch = nullptr;   // [N] game_over of cagym_step_autoreset_keep when the caller gives none
     TrajRing traj{};                 // trajectory ring (cagym_trajectory_init allocates it: the running block once, the ring per n_slices)
     bool traj_ready = false;
@@ -296,6 +304,8 @@ inline int eplog_restart(Env* e, const uint8_t* world_mask, bool clear_rows, hip
     const unsigned grid = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
     hipLaunchKernelGGL(k_episode_log_restart, dim3(grid), dim3(256), 0, st, e->D, e->elog, world_mask, clear_rows ? 1 : 0);
     HIPCHK(e, hipGetLastError());
+    if (clear_rows && e->replay.words)  // head restarts at 0: so does the row number the replay harvest has reached
+        HIPCHK(e, hipMemsetAsync(e->replay.words + RPW_CURSOR, 0, sizeof(unsigned long long), st));
     return CAGYM_OK;
 }
 // the trajectory ring's restart / clear (csrc/cagym_terminal.h); a no-op for handles that never initialised it
@@ -717,7 +727,7 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
     e->obst_rvo = new_obst_rvo;
     e->D.ko = new_ko;
     e->scenarios_set = true;
-    e->streaming = false;  // the pool is the caller's again
+    e->streaming = e->replay_on = false;  // the pool is the caller's again
     e->begun = false;  // a pending cagym_step_begin solved the old pool's worlds: its velocities are void
     return episodes_restart(e, nullptr, true, st);
 }
@@ -776,7 +786,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     }
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     e->scenarios_set = true;
-    e->streaming = false;
+    e->streaming = e->replay_on = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
     return episodes_restart(e, nullptr, true, st);
 }
@@ -875,7 +885,7 @@ static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int
     e->obst_rvo = F.obst_rvo ? 1 : 0;
     e->D.ko = F.obst_rvo ? 2 * K : 0;
     e->scenarios_set = true;
-    e->streaming = false;
+    e->streaming = e->replay_on = false;
     e->begun = false;  // as in cagym_set_scenarios: a pending cagym_step_begin is void
     return episodes_restart(e, nullptr, true, st);
 }
@@ -935,6 +945,7 @@ int cagym_stream_scenarios(void* env, const cagym_gen2_params* params, int32_t* 
     e->stream_P = *params;
     e->streaming = true;
     e->explore_stream = false;
+    e->stream_gen = 1;
     return CAGYM_OK;
 }
 
@@ -951,6 +962,7 @@ int cagym_stream_set_params(void* env, const cagym_gen2_params* params) {
     e->obst_rvo = obst_rvo;
     e->D.ko = obst_rvo ? 2 * e->cfg.max_obstacles : 0;
     e->stream_P = *params;
+    e->stream_gen += 1;  // a key redrawn under another set is another scenario: the replay buffer holds for one generation
     return CAGYM_OK;
 }
 
@@ -966,6 +978,9 @@ int cagym_stream_refill(void* env, void* stream) {
             hipLaunchKernelGGL(k_explore_field_cols, dim3(EXPLORE_COLS_GRID), dim3(320), 0, st, e->G, e->explore, e->ig_any);
             hipLaunchKernelGGL(k_explore_field_rows, dim3(EXPLORE_ROWS_GRID), dim3(320), 0, st, e->G, e->explore, e->ig_any);
         }
+    } else if (e->replay_on) {
+        hipLaunchKernelGGL(k_stream_refill_replay, dim3(grid), dim3(CAGYM_WAVE), 0, st, gen2_dev(e), e->stream_P, e->stream, e->replay, e->replay_p,
+                           e->replay_seed, e->stream_gen);
     } else {
         hipLaunchKernelGGL(k_stream_refill, dim3(grid), dim3(CAGYM_WAVE), 0, st, gen2_dev(e), e->stream_P, e->stream);
     }
@@ -985,7 +1000,86 @@ int cagym_stream_get(void* env, cagym_stream_ptrs* out) {
 
 int cagym_stream_stop(void* env) {
     ENTRY(e, env);
-    e->streaming = false;
+    e->streaming = e->replay_on = false;
+    return CAGYM_OK;
+}
+
+// ---- replay of logged scenarios in the stream (csrc/cagym_replay.h) -----------------------------------------------------------------------
+int cagym_stream_replay_init(void* env, int capacity, uint64_t seed, void* stream) {
+    ENTRY_IF(e, env, e->streaming, "cagym_stream_replay_init on a handle that is not streaming");
+    if (e->explore_stream)
+        return fail(e, CAGYM_E_UNSUPPORTED, "cagym_stream_replay_init on an exploration stream: its refill also rebuilds distance fields");
+    if (capacity < 1) return fail(e, CAGYM_E_INVALID, "cagym_stream_replay_init: capacity must be >= 1");
+    ON_DEVICE(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t S = (size_t)e->cfg.n_scenarios;
+    ReplayDev R = e->replay;
+    if (!R.words) {  // once per handle: the words (u64), buf_gen and a pad word, then the two per-slot tables
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, 8 * (size_t)RPW_WORDS + 8 + 8 * S)) return rc;
+        R.words = reinterpret_cast<unsigned long long*>(b); b += 8 * (size_t)RPW_WORDS;
+        R.buf_gen = reinterpret_cast<uint32_t*>(b); b += 8;
+        R.slot_key = reinterpret_cast<uint32_t*>(b); b += 4 * S;
+        R.slot_gen = reinterpret_cast<uint32_t*>(b);
+        e->replay = R;  // kept whatever becomes of the buffer's allocation
+    }
+    if (!e->replay_ring || R.Q != capacity) {
+        if (int rc = ring_alloc(e, &e->replay_ring, "replay_ring", 4 * (size_t)capacity, false)) return rc;
+        R.buf_key = static_cast<uint32_t*>(e->replay_ring);
+        R.Q = capacity;
+    }
+    e->replay = R;
+    e->replay_seed = seed;
+    // a handle that is armed already keeps its tables (they name replayed keys): only the buffer and the counters are cleared
+    const unsigned grid = (unsigned)((e->cfg.n_worlds + CAGYM_WAVE - 1) / CAGYM_WAVE);
+    hipLaunchKernelGGL(k_replay_arm, dim3(grid), dim3(CAGYM_WAVE), 0, st, R, e->stream, (int)S, e->stream_gen, e->replay_on ? 0 : 1,
+                       e->stream_gen == 1 ? 1 : 0, e->log_ready ? e->elog.head : nullptr);
+    HIPCHK(e, hipGetLastError());
+    if (!e->replay_on) {
+        e->replay_p = 0.0;
+        e->replay_mask = 0;
+    }
+    e->replay_on = true;
+    return CAGYM_OK;
+}
+
+int cagym_stream_replay_set(void* env, double p, uint32_t outcome_mask) {
+    ENTRY_IF(e, env, e->replay_on, "cagym_stream_replay_set before cagym_stream_replay_init");
+    if (!(p >= 0.0 && p <= 1.0)) return fail(e, CAGYM_E_INVALID, "cagym_stream_replay_set: p must lie in [0, 1]");
+    if (outcome_mask & ~7u) return fail(e, CAGYM_E_INVALID, "cagym_stream_replay_set: outcome_mask takes the bits 1 (collision), 2 (all at goal), 4 (stuck)");
+    e->replay_p = p;
+    e->replay_mask = outcome_mask;
+    return CAGYM_OK;
+}
+
+int cagym_stream_replay_push(void* env, const uint32_t* keys, int n, void* stream) {
+    ENTRY_IF(e, env, e->replay_on, "cagym_stream_replay_push before cagym_stream_replay_init");
+    if (n < 0 || (n > 0 && !keys)) return fail(e, CAGYM_E_INVALID, "cagym_stream_replay_push: need n >= 0 and a device array of n keys");
+    if (n == 0) return CAGYM_OK;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_replay_push, dim3(1), dim3(REPLAY_NT), 0, reinterpret_cast<hipStream_t>(stream), e->replay, keys, n, e->stream_gen);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_stream_replay_harvest(void* env, void* stream) {
+    ENTRY_IF(e, env, e->replay_on, "cagym_stream_replay_harvest before cagym_stream_replay_init");
+    REQUIRE(e, e->log_ready, "cagym_stream_replay_harvest", "cagym_episode_log_init");
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_replay_harvest, dim3(1), dim3(REPLAY_NT), 0, reinterpret_cast<hipStream_t>(stream), e->elog, e->replay, e->cfg.n_worlds,
+                       e->cfg.n_scenarios, e->replay_mask, e->stream_gen);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_stream_replay_get(void* env, const uint32_t** buf_key, const uint64_t** words, const uint32_t** slot_key, const uint32_t** slot_gen,
+                            int* capacity) {
+    ENTRY_IF(e, env, e->replay.words != nullptr, "cagym_stream_replay_get before cagym_stream_replay_init");
+    if (buf_key) *buf_key = e->replay.buf_key;
+    if (words) *words = reinterpret_cast<const uint64_t*>(e->replay.words);
+    if (slot_key) *slot_key = e->replay.slot_key;
+    if (slot_gen) *slot_gen = e->replay.slot_gen;
+    if (capacity) *capacity = e->replay.Q;
     return CAGYM_OK;
 }
 
@@ -1945,7 +2039,9 @@ int cagym_episode_log_update(void* env, const uint8_t* flags, const float* rewar
         hipLaunchKernelGGL(k_episode_log_count, dim3((unsigned)((N + CAGYM_WAVE - 1) / CAGYM_WAVE)), dim3(CAGYM_WAVE * EPLOG_CNT_WAVES), 0, st, e->elog, N,
                            game_over, T);
     hipLaunchKernelGGL(k_episode_log_scan, dim3(1), dim3(EPLOG_NT_SCAN), 0, st, e->elog, N, T, T > 1 ? nullptr : game_over);
-    hipLaunchKernelGGL(k_episode_log_write, dim3((unsigned)((n_waves(e) + waves_per_wg - 1) / waves_per_wg)), dim3(EPREC_NT), 0, st, e->D, e->elog,
+    EpLog G = e->elog;
+    G.slot_key = e->replay_on ? e->replay.slot_key : nullptr;  // armed: the key column names the scenario that ran
+    hipLaunchKernelGGL(k_episode_log_write, dim3((unsigned)((n_waves(e) + waves_per_wg - 1) / waves_per_wg)), dim3(EPREC_NT), 0, st, e->D, G,
                        flags, reward, game_over, T);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;

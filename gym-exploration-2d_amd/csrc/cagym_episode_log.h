@@ -38,6 +38,7 @@ struct EpLog {
     int32_t* cnt;             // [N] episodes world w finishes in this update
     unsigned long long* pos;  // [N] row number of its first one
     int capacity;
+    const uint32_t* slot_key;  // [S] the key each pool slot was generated from while replay is armed (cagym_replay.h), else NULL
 };
 
 #define EPLOG_NT_SCAN 1024 /* lanes of the single scan workgroup */
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(EPREC_NT) k_episode_log_write(CagymDev D, EpLo
             G.extra_t[k] = W.extra;
             G.flags[k] = W.fb;
             if (L.slot == 0) {
-                G.key[r] = (uint32_t)L.world + (uint32_t)R.cursor * (uint32_t)D.N;
+                G.key[r] = G.slot_key ? G.slot_key[W.s] : (uint32_t)L.world + (uint32_t)R.cursor * (uint32_t)D.N;
                 G.world[r] = L.world;
                 G.episode[r] = R.cursor;
                 G.slice[r] = (long long)(seq0 + (unsigned long long)t);

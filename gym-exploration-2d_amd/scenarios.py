@@ -72,6 +72,34 @@ def reference_curriculum(total_steps, names=TRAINING_SCENARIOS):
     return sorted({kinds[i] for i in idx}), n
 
 
+_MASK64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def generator_u01(seed, s, k):
+    """Draw k of the stream (seed, s) of the device's counter-based generator (csrc/cagym_gen.h: gen_u01), in [0, 1)."""
+    h = _mix64((int(seed) & _MASK64) ^ _mix64(((int(s) & 0xFFFFFFFF) << 32) | (int(k) & 0xFFFFFFFF)))
+    return float(h >> 11) * 2.0 ** -53
+
+
+def replay_choice(seed, key, p, live):
+    """The replay draw of the armed stream refill (include/cagym.h: cagym_stream_replay_*) in plain Python: for the slot of stream
+    key `key` = w + e * N, replay seed `seed`, probability p and `live` entries in the buffer, returns (replay, j) - whether the
+    slot is generated from a buffered key, and which of the live entries, oldest first (j = 0 when it is not)."""
+    key = int(key) & 0xFFFFFFFF
+    rs = (int(seed) ^ 0x9E3779B97F4A7C15) & _MASK64
+    live = int(live)
+    if not (live > 0 and generator_u01(rs, key, 0) < float(p)):
+        return False, 0
+    return True, min(live - 1, int(generator_u01(rs, key, 1) * float(live)))
+
+
 def random_world(rng, M, side=7.5, min_travel=4.0, min_sep=1.5, radius=0.5, pref_speed=1.0):
     """One world: float64 [M, 6] rows [sx, sy, gx, gy, pref_speed, radius]."""
     out = np.zeros((M, 6), dtype=np.float64)

@@ -524,7 +524,8 @@ int cagym_episode_records_get(void* env, cagym_episode_record_ptrs* out);
  * The log is not keyed by slot: a device ring of `capacity` rows, ONE ROW PER FINISHED EPISODE, rebuilt from the same step outputs by
  * launches of its own behind the auto-resetting step(s).  No step, reset, roll-out or refill kernel knows of it.
  * Row columns (structure of arrays, L = capacity rows):
- *   key [L] u32 = (uint32_t)(w + e * N), the stream key of the episode that ended (world w, episode index e); world, episode [L] i32;
+ *   key [L] u32 = (uint32_t)(w + e * N), the stream key of the episode that ended (world w, episode index e; while
+ *   cagym_stream_replay_* is armed: the key its slot was really generated from); world, episode [L] i32;
  *   slice [L] i64, the index of the slice that ended the episode counted over all update calls since init / clear;
  *   steps [L] i32; ret [L] f64 (sum of agent 0's reward in step order); outcome [L] i32 (the records' bits: 1 any collision, 2 all at
  *   goal, 4 any neither); n_agents, n_obst [L] i32 from the pool row of the episode's slot (w + e * N) % S (n_obst 0 without
@@ -685,6 +686,60 @@ int cagym_stream_refill(void* env, void* stream);
 int cagym_stream_set_params(void* env, const cagym_gen2_params* params);
 int cagym_stream_get(void* env, cagym_stream_ptrs* out);
 int cagym_stream_stop(void* env);
+
+/* ---- Replay of failed scenarios from the episode log, inside the stream (csrc/cagym_replay.h) ----------------------------------------
+ * On a cagym_stream_scenarios stream, an optional REPLAY BUFFER of stream keys on the device.  A harvest launch fills it from the
+ * episode log (the rows whose outcome matches a mask), a caller may push keys directly, and once armed the refill decides for each
+ * slot it generates, by a counter-based draw, between the fresh key w + e * N and a key sampled from the buffer - with replacement:
+ * nothing is consumed, no workgroup waits on another, atomics on counters only, everything stream-ordered, no host synchronisation
+ * and no allocation after init.  No step, reset or roll-out kernel knows of it.
+ * State on the handle (allocated by init; written with ordinary stores or atomics):
+ *   buf_key [Q] u32  ring of replay keys: entry number i since the last clear lives at i % Q
+ *   count u64        entries appended since the last clear; live = min(count, Q)
+ *   buf_gen u32      the generation the buffer belongs to
+ *   cursor u64       log row number up to which rows were harvested
+ *   slot_key [S] u32 key each pool slot was generated from;  slot_gen [S] u32 generation it was generated under (0: unknown)
+ *   and the u64 counters harvested, pushed, replayed, n_missed, n_stale.
+ * Generation: the host keeps gen, 1 at cagym_stream_scenarios, + 1 with every successful cagym_stream_set_params, passed to the
+ *   kernels by value.  A key redrawn under another parameter set is a different scenario, so the buffer is valid for one generation:
+ *   the harvest and push kernels clear it when buf_gen != gen (count = 0, buf_gen = gen), the refill treats it as empty.
+ * Arming (k_replay_arm, one lane per world, at init): for j in 0 .. depth-1, e = episode[w] + j, slot = (w + e N) % S:
+ *   e < next_episode[w]: slot_key = (uint32)(w + e N), slot_gen = gen; otherwise (a lapped world's slot) slot_gen = 0.  When a
+ *   parameter switch preceded init (gen > 1) the ring may hold slots of an older set: every slot_gen starts as 0.  cursor = the
+ *   log's head (rows logged before init ran on slots that may have been regenerated since), 0 without a log.
+ * Refill with replay (k_stream_refill_replay; the un-armed launch stays k_stream_refill): windows, early exit, rasterisation and
+ *   counters as there.  For each (w, e) it generates, idx = w + e N, key32 = (uint32)idx, rs = replay_seed ^ 0x9E3779B97F4A7C15:
+ *   u0 = u(rs, key32, 0), u1 = u(rs, key32, 1) (the generator of cagym_generate_scenarios);
+ *   replay iff live > 0 && buf_gen == gen && u0 < p (fp64); then j = min(live - 1, (int)(u1 * live)),
+ *   key = buf_key[(count - live + j) % Q]; otherwise key = key32.  The slot (uint32)(idx % S) gets the scenario of `key`;
+ *   slot_key[slot] = key, slot_gen[slot] = gen; `replayed` grows by one atomic per wave.
+ *   With p == 0 or an empty buffer the pool, the steps and the log are bitwise the plain stream's.
+ * Harvest (k_replay_harvest, ONE workgroup of 1024 lanes): log rows [max(cursor, head - capacity_log), head) in ascending row number;
+ *   n_missed += rows overwritten before it saw them; a row (world, episode) maps to slot = (world + episode N) % S and is accepted
+ *   iff (outcome & mask) != 0 && slot_gen[slot] == gen; a row whose slot_gen is neither 0 nor gen counts in n_stale; accepted rows
+ *   append slot_key[slot] in row order; then cursor = head.  Enqueue it behind cagym_episode_log_update and before
+ *   cagym_stream_refill (it reads slot_key of the slot the refill regenerates next - the contract the log has).  A replayed key that
+ *   fails again is appended again: duplicates weigh it up; a success removes nothing.  Clearing the log restarts cursor at 0.
+ * Episode log: while replay is armed the log's key column holds slot_key of the slot the episode ran on instead of w + e N - also
+ *   under lapping it names the scenario that actually ran.  Without replay the log is unchanged.
+ * cagym_stream_replay_init: allocates and arms (p = 0, mask = 0).  A second call clears the buffer and the counters and may change
+ *   the capacity; the per-slot tables stay.  CAGYM_E_STATE when not streaming, CAGYM_E_UNSUPPORTED on an exploration stream,
+ *   CAGYM_E_INVALID for capacity < 1.
+ * cagym_stream_replay_set: host only, takes effect at the next launch.  p in [0, 1]; outcome_mask holds bits of the log's outcome
+ *   (1 collision, 2 all at goal, 4 stuck), 0 = harvest nothing.  CAGYM_E_INVALID otherwise, CAGYM_E_STATE when not armed.
+ * cagym_stream_replay_push: keys [n] u32 is a DEVICE pointer; appends in order under the current gen (one launch).
+ * cagym_stream_replay_harvest: one launch; CAGYM_E_STATE without an initialised log or armed replay.
+ * cagym_stream_replay_get: zero-copy DEVICE views (any pointer may be NULL); words [6] u64 = count, harvested, pushed, replayed,
+ *   n_missed, n_stale.  CAGYM_E_STATE before the first init; they stay readable after the stream stopped.
+ * cagym_stream_refill launches the replay variant once armed.  cagym_stream_stop and every pool setter end replay with the stream; a
+ * new stream starts un-armed.
+ * Out of scope: exploration streams, eviction on success, priorities beyond duplicates, replay across generations. */
+int cagym_stream_replay_init(void* env, int capacity, uint64_t seed, void* stream);
+int cagym_stream_replay_set(void* env, double p, uint32_t outcome_mask);
+int cagym_stream_replay_push(void* env, const uint32_t* keys, int n, void* stream);
+int cagym_stream_replay_harvest(void* env, void* stream);
+int cagym_stream_replay_get(void* env, const uint32_t** buf_key, const uint64_t** words, const uint32_t** slot_key, const uint32_t** slot_gen,
+                            int* capacity);
 
 /* ---- Exploration worlds: an IG team on fresh maps, generated and streamed on the device (csrc/cagym_explore.h) ---------------------
  * A world holds a team of R = n_robots IG robots (CAGYM_POL_IGMCTS, FirstOrder, slots 0..R-1: the reference's ig_mcts indexes the
