@@ -1335,8 +1335,11 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
                         else
                             orca_lp_group_n<GW, 2, OVL>(W.sorted, P, a, j, nol, nn, ko, rad, pv.x, pv.y, vx, vy, AS, &W.flag[3]);
                     } else {
-                        orca_lp_group<GW, TWO, (MT > 0 ? MT - 1 : 0)>(W.sorted, W.lp3 + LPL * (tid & ~(GW - 1)), a, j, nn, rad, pv.x, pv.y, vx, vy, AS, &W.flag[3],
-                                                                      LPCOUNT_DBG(), LPWT_ROWS(t, base));
+                        // (W.lpc[a] is the program's start until lane 0 of the group stores the result there, below: the publisher of
+                        // W.lpv[a] wrote both, and W.busy[a] was decided on it)
+                        const float2 ps = W.lpc[a];
+                        orca_lp_group<GW, TWO, (MT > 0 ? MT - 1 : 0), true>(W.sorted, W.lp3 + LPL * (tid & ~(GW - 1)), a, j, nn, rad, pv.x, pv.y, vx, vy, AS,
+                                                                            &W.flag[3], LPCOUNT_DBG(), LPWT_ROWS(t, base), ps.x, ps.y);
                     }
                     if (j == 0) W.lpc[a] = make_float2(vx, vy);
                 }

@@ -277,6 +277,7 @@ __device__ inline void orca_action(const NbrTile& T, float4* L, float4* P, int l
 // One reduction level = ONE instruction: v_max/min_f32 with a DPP source operand (the builtin route costs a DPP
 // move plus canonicalising maxes per level).  s_nop 1 covers the VALU-write -> DPP-read hazard, which the
 // compiler's hazard recogniser does not see inside inline assembly.  Operands are never NaN here.
+// (These one-level helpers serve orca_lp_group_n, the solver among rectangles; orca_lp_group uses grp_max_min / grp_min_u32 below.)
 #define CAGYM_DPP_OP(name, op, ctrl)                                                            \
     __device__ __forceinline__ float name(float v) {                                           \
         float r;                                                                               \
@@ -306,6 +307,55 @@ __device__ __forceinline__ float grp_min(float v) {
     v = dpp_min_quad2(v);
     return dpp_min_quad1(v);
 }
+// The maximum of a and the minimum of b over the group in ONE asm block, the two chains interleaved (round 9).  A VALU write needs
+// two wait states before a DPP read of the register (the compiler's hazard recogniser does not see inside inline assembly, and it
+// does not know what wrote a and b last): s_nop 1 in front; between a level's write and the next level's read of the same
+// register stand the other chain's instruction - an independent VALU instruction is a wait state - and one s_nop 0.  In place: a
+// DPP row operation reads all its lanes' sources before it writes.  Operands are never NaN here.
+#define CAGYM_DPP_MM(ctrl)                                                         \
+    "v_max_f32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf\n\t"            \
+    "v_min_f32_dpp %1, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf\n\t"
+template <int GW>
+__device__ __forceinline__ void grp_max_min(float& a, float& b) {
+    static_assert(GW == 4 || GW == 8 || GW == 16, "an LP group is 4, 8 or 16 lanes of one DPP row");
+    if (GW == 16)
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MM("row_mirror") "s_nop 0\n\t" CAGYM_DPP_MM("row_half_mirror") "s_nop 0\n\t"
+                     CAGYM_DPP_MM("quad_perm:[2,3,0,1]") "s_nop 0\n\t" CAGYM_DPP_MM("quad_perm:[1,0,3,2]") : "+v"(a), "+v"(b));
+    else if (GW == 8)
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MM("row_half_mirror") "s_nop 0\n\t" CAGYM_DPP_MM("quad_perm:[2,3,0,1]") "s_nop 0\n\t"
+                     CAGYM_DPP_MM("quad_perm:[1,0,3,2]") : "+v"(a), "+v"(b));
+    else
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MM("quad_perm:[2,3,0,1]") "s_nop 0\n\t" CAGYM_DPP_MM("quad_perm:[1,0,3,2]") : "+v"(a), "+v"(b));
+}
+// The group's minimum of an unsigned key: the next violated line is the smallest index among the lanes' violated lines, which is
+// find-first-set of the group's ballot mask without the ballots, the per-lane 64-bit shifts and the merge.  One chain: s_nop 1
+// between the levels.
+#define CAGYM_DPP_MINU(ctrl) "v_min_u32_dpp %0, %0, %0 " ctrl " row_mask:0xf bank_mask:0xf\n\t"
+template <int GW>
+__device__ __forceinline__ uint32_t grp_min_u32(uint32_t k) {
+    if (GW == 16)
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MINU("row_mirror") "s_nop 1\n\t" CAGYM_DPP_MINU("row_half_mirror") "s_nop 1\n\t"
+                     CAGYM_DPP_MINU("quad_perm:[2,3,0,1]") "s_nop 1\n\t" CAGYM_DPP_MINU("quad_perm:[1,0,3,2]") : "+v"(k));
+    else if (GW == 8)
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MINU("row_half_mirror") "s_nop 1\n\t" CAGYM_DPP_MINU("quad_perm:[2,3,0,1]") "s_nop 1\n\t"
+                     CAGYM_DPP_MINU("quad_perm:[1,0,3,2]") : "+v"(k));
+    else
+        asm volatile("s_nop 1\n\t" CAGYM_DPP_MINU("quad_perm:[2,3,0,1]") "s_nop 1\n\t" CAGYM_DPP_MINU("quad_perm:[1,0,3,2]") : "+v"(k));
+    return k;
+}
+// max / min as the ONE instruction they are: fmaxf / fminf go through the compiler's canonicalisation of a possible signalling
+// NaN (a v_max_f32 x, x, x per operand it knows nothing about).  Never NaN here; both order -0 below +0.
+__device__ __forceinline__ float vmax_f32(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float vmin_f32(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+constexpr uint32_t ORCA_NO_LINE = 0xffffu;  // "no violated line" key of grp_min_u32
 
 // linearProgram1 on the group: half-plane `ln` against the lanes' own lines (`m0` taking part when `take0`, the lane's
 // second line `m1` when `take1`).  dir_opt as in RVO2.  Returns false when infeasible (result untouched).
@@ -322,8 +372,9 @@ __device__ __forceinline__ void orca_clip_by(const float4 ln, const float4 mine,
 }
 // The chord of a line in the disc of radius `radius` (linearProgram1's first lines): (tLeft, tRight) = -dot -+ sqrt(disc), or
 // (+inf, -inf) when the line misses the disc (disc < 0: "return false" - the empty interval fails the tLeft > tRight test instead).
-// It depends on the line alone: the lane that owns a line computes it ONCE (round 3) and the group fetches it by lane shuffle in
-// every round that projects onto that line, instead of every lane recomputing dot, disc and a correctly rounded sqrt per round.
+// It depends on the line alone: the lane that owns a line computes it ONCE (round 3) and offers it to the reductions of every round
+// that projects onto that line (round 9; by lane shuffle before), instead of every lane recomputing dot, disc and a correctly
+// rounded sqrt per round.
 __device__ __forceinline__ float2 orca_chord(const float4 ln, float radius) {
     const float dot = ln.x * ln.z + ln.y * ln.w;
     const float disc = dot * dot + radius * radius - (ln.x * ln.x + ln.y * ln.y);
@@ -331,10 +382,16 @@ __device__ __forceinline__ float2 orca_chord(const float4 ln, float radius) {
     const float sq = sqrtf(disc);
     return make_float2(-dot - sq, -dot + sq);
 }
+// lo: what the lane offers before it clips - the chord of `ln` on the lane that owns the line, (-inf, +inf) on every other lane:
+// the chord goes THROUGH the reductions (max and min order +0 and -0: whichever lane offers a bound, the group's bound is the
+// same bits), not around them by two lane shuffles and a second max / min.  The owner of a line never clips it with its first
+// slot when TWO is false (take0 is false for j == i), so there `lo` costs the selects alone.  beyond (TWO = false): `ln` is the
+// line beyond the lanes - nobody holds its chord, the round computes it and every lane offers it.
 template <int GW, bool TWO>
-__device__ __forceinline__ bool orca_lp1_group(const float4 ln, float tl, float tr, const float4 m0, bool take0, const float4 m1, bool take1,
-                                               float ox, float oy, bool dir_opt, float& rx, float& ry) {
-    float ltl = -INFINITY, ltr = INFINITY;
+__device__ __forceinline__ bool orca_lp1_group(const float4 ln, const float2 lo, const float4 m0, bool take0, const float4 m1, bool take1,
+                                               float ox, float oy, bool dir_opt, float& rx, float& ry, bool beyond = false,
+                                               float radius = 0.f) {
+    float ltl = lo.x, ltr = lo.y;
     if (!TWO) {
         if (take0) {  // one candidate per lane: plain selects
             const float den = detf(ln.z, ln.w, m0.z, m0.w);
@@ -351,16 +408,22 @@ __device__ __forceinline__ bool orca_lp1_group(const float4 ln, float tl, float 
         if (take0) orca_clip_by(ln, m0, ltl, ltr);
         if (take1) orca_clip_by(ln, m1, ltl, ltr);  // lines GW .. 2 GW - 1 (more than GW + 1 neighbours only)
     }
-    tl = fmaxf(tl, grp_max<GW>(ltl));
-    tr = fminf(tr, grp_min<GW>(ltr));
+    if (!TWO && beyond) {  // group-uniform
+        const float2 c = orca_chord(ln, radius);
+        ltl = vmax_f32(ltl, c.x);
+        ltr = vmin_f32(ltr, c.y);
+    }
+    grp_max_min<GW>(ltl, ltr);
+    const float tl = ltl, tr = ltr;
     if (tl > tr) return false;
     float t;
     if (dir_opt) {
         t = (ox * ln.z + oy * ln.w > 0.0f) ? tr : tl;
     } else {
-        t = ln.z * (ox - ln.x) + ln.w * (oy - ln.y);
-        if (t < tl) t = tl;
-        else if (t > tr) t = tr;
+        // t < tl ? tl : (t > tr ? tr : t) with tl <= tr and no NaN is min(max(t, tl), tr): two instructions, no exec-mask branches.
+        // (Not v_med3_f32: with tl = -0 and tr = +0 - a line tangent to the disc through the origin, which the lattice worlds of the
+        // tests reach - its result for t = -0 hangs on how it breaks the tie; max then min keeps t's own zero there as the compares do.)
+        t = vmin_f32(vmax_f32(ln.z * (ox - ln.x) + ln.w * (oy - ln.y), tl), tr);
     }
     rx = ln.x + t * ln.z;
     ry = ln.y + t * ln.w;
@@ -395,17 +458,23 @@ __device__ __forceinline__ bool orca_project(const float4 li, const float4 lj, f
 // scratch of 2 GW projected lines.
 // ROWS: compile-time row count of the ego's column (M - 1) or 0: lanes j < ROWS load their first half-plane without
 // waiting for nn (a stale row is never looked at: every use is guarded by j < nn).
-template <int GW, bool TWO, int ROWS = 0>
+// START: (sx, sy) is the program's start - (ox, oy) clipped to the disc, which the publisher of the LP inputs stored beside them
+// with these very expressions (publish_pref_velocity3 / ego_phase3: W.lpc) - instead of clipping again on every LP wave.
+template <int GW, bool TWO, int ROWS = 0, bool START = false>
 __device__ inline void orca_lp_group(const float4* L, float4* P, int a, int j, int nn, float radius, float ox, float oy,
                                      float& rx, float& ry, int stride, int* lp3_flag = nullptr, int* dbg = nullptr,
-                                     unsigned long long* wt = nullptr) {
+                                     unsigned long long* wt = nullptr, float sx = 0.f, float sy = 0.f) {
     LPCOUNT_DECL();
-    const int gbase = (threadIdx.x & 63) & ~(GW - 1);
-    const uint64_t gbits = (1ull << GW) - 1ull;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float2 open = make_float2(-INFINITY, INFINITY);
     const float4 l0 = (ROWS >= GW || j < nn) ? L[j * stride + a] : zero4;
-    const float4 l1 = j + GW < nn ? L[(j + GW) * stride + a] : zero4;
-    if (ox * ox + oy * oy > radius * radius) {
+    // the line beyond the lanes (lane 0's second one) of a compile-time column: one 16-byte read on every lane, without waiting for
+    // nn either - the other lanes read their own row again, and nobody but lane 0 ever looks (j + GW < nn <= GW + 1)
+    const float4 l1 = (!TWO && ROWS > GW) ? L[(j == 0 ? GW : j) * stride + a] : (j + GW < nn ? L[(j + GW) * stride + a] : zero4);
+    if (START) {
+        rx = sx;
+        ry = sy;
+    } else if (ox * ox + oy * oy > radius * radius) {
         const float inv = 1.0f / sqrtf(ox * ox + oy * oy);
         rx = ox * inv * radius;
         ry = oy * inv * radius;
@@ -420,28 +489,20 @@ __device__ inline void orca_lp_group(const float4* L, float4* P, int a, int j, i
     LPWT(wt, 13);
     // linearProgram2.  The reference walks the lines in order and projects onto each violated one; between two
     // projections the result does not change, so "the next violated line at or after cur" is one parallel test
-    // (lane j tests its half-planes) + a find-first-set.  The groups of a wave then run linearProgram1 in lockstep,
+    // (lane j tests its half-planes) + the group's minimum of the violated indices.  The groups of a wave then run linearProgram1 in lockstep,
     // each on its own line index, instead of diverging over an unrolled loop on i.
     int fail = nn;
     for (int cur = 0; cur < nn;) {  // cur grows by at least 1 per trip: every lane leaves after <= nn trips
         const bool v0 = j >= cur && j < nn && detf(l0.z, l0.w, l0.x - rx, l0.y - ry) > 0.0f;
         const bool v1 = j + GW >= cur && j + GW < nn && detf(l1.z, l1.w, l1.x - rx, l1.y - ry) > 0.0f;
-        const uint32_t m = (uint32_t)((__ballot(v0) >> gbase) & gbits) | ((uint32_t)((__ballot(v1) >> gbase) & gbits) << GW);
-        if (!m) break;
-        const int i = __ffs((int)m) - 1;
+        const int i = (int)grp_min_u32<GW>(v0 ? (uint32_t)j : (v1 ? (uint32_t)(j + GW) : ORCA_NO_LINE));
+        if (i == (int)ORCA_NO_LINE) break;
         LPCOUNT(c_lp2);
         const float4 li = L[i * stride + a];
-        const int own = gbase + (i & (GW - 1));  // the lane of the group that owns line i (slot i / GW)
-        float tl0, tr0;
-        if (!TWO && i >= GW) {  // group-uniform
-            const float2 ci = orca_chord(li, radius);
-            tl0 = ci.x;
-            tr0 = ci.y;
-        } else {
-            tl0 = __shfl((TWO && i >= GW) ? c1.x : c0.x, own, 64);
-            tr0 = __shfl((TWO && i >= GW) ? c1.y : c0.y, own, 64);
-        }
-        if (!orca_lp1_group<GW, TWO>(li, tl0, tr0, l0, j < i, l1, j + GW < i, ox, oy, false, rx, ry)) {
+        // the lane that owns line i (slot i / GW) offers its chord to the round's reductions (TWO = false: the line beyond the lanes
+        // has no owner - j == i holds on no lane - and the round computes its chord)
+        const float2 lo = (TWO ? j == (i & (GW - 1)) : j == i) ? ((TWO && i >= GW) ? c1 : c0) : open;
+        if (!orca_lp1_group<GW, TWO>(li, lo, l0, j < i, l1, j + GW < i, ox, oy, false, rx, ry, i >= GW, radius)) {
             fail = i;  // result keeps the value it had before this line (tempResult)
             break;
         }
@@ -455,9 +516,8 @@ __device__ inline void orca_lp_group(const float4* L, float4* P, int a, int j, i
     for (int cur = fail; cur < nn;) {
         const bool w0 = j >= cur && j < nn && detf(l0.z, l0.w, l0.x - rx, l0.y - ry) > distance;
         const bool w1 = j + GW >= cur && j + GW < nn && detf(l1.z, l1.w, l1.x - rx, l1.y - ry) > distance;
-        const uint32_t wm = (uint32_t)((__ballot(w0) >> gbase) & gbits) | ((uint32_t)((__ballot(w1) >> gbase) & gbits) << GW);
-        if (!wm) break;
-        const int i = __ffs((int)wm) - 1;
+        const int i = (int)grp_min_u32<GW>(w0 ? (uint32_t)j : (w1 ? (uint32_t)(j + GW) : ORCA_NO_LINE));
+        if (i == (int)ORCA_NO_LINE) break;
         cur = i + 1;
         LPCOUNT(c_lp3o);
         const float4 li = L[i * stride + a];
@@ -480,16 +540,14 @@ __device__ inline void orca_lp_group(const float4* L, float4* P, int a, int j, i
         for (int kcur = 0; kcur < i;) {
             const bool u0 = have0 && j >= kcur && detf(p0.z, p0.w, p0.x - qx, p0.y - qy) > 0.0f;
             const bool u1 = TWO && have1 && j + GW >= kcur && detf(p1.z, p1.w, p1.x - qx, p1.y - qy) > 0.0f;
-            uint32_t um = (uint32_t)((__ballot(u0) >> gbase) & gbits);
-            if (TWO) um |= (uint32_t)((__ballot(u1) >> gbase) & gbits) << GW;
-            if (!um) break;
-            const int k = __ffs((int)um) - 1;
+            const int k = (int)grp_min_u32<GW>(u0 ? (uint32_t)j : (u1 ? (uint32_t)(j + GW) : ORCA_NO_LINE));
+            if (k == (int)ORCA_NO_LINE) break;
             kcur = k + 1;
             LPCOUNT(c_lp3i);
             const float4 pk = P[k];  // projected line k (same wave: the LDS write above is ordered before this read)
-            const int ownk = gbase + (k & (GW - 1));
-            const float tlk = __shfl((TWO && k >= GW) ? pc1.x : pc0.x, ownk, 64), trk = __shfl((TWO && k >= GW) ? pc1.y : pc0.y, ownk, 64);
-            if (!orca_lp1_group<GW, TWO>(pk, tlk, trk, p0, j < k && have0, p1, j + GW < k && have1, px, py, true, qx, qy)) {
+            // (projected lines are lines before i: k < GW when TWO is false, the owner is lane k)
+            const float2 lok = j == (k & (GW - 1)) ? ((TWO && k >= GW) ? pc1 : pc0) : open;
+            if (!orca_lp1_group<GW, TWO>(pk, lok, p0, j < k && have0, p1, j + GW < k && have1, px, py, true, qx, qy)) {
                 failed = true;
                 break;
             }

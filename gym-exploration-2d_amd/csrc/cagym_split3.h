@@ -149,7 +149,9 @@ __device__ inline void run_rvo_pre3(const CagymDev& D, unsigned char* smem) {
                     if (__ballot(nol + nn > 2 * GW) != 0ull) orca_lp_group_n<GW, 4, true>(W.sorted, P, a, j, nol, nn, ko, rad, pv.x, pv.y, vx, vy, AS, nullptr);
                     else orca_lp_group_n<GW, 2, true>(W.sorted, P, a, j, nol, nn, ko, rad, pv.x, pv.y, vx, vy, AS, nullptr);
                 } else {
-                    orca_lp_group<GW, TWO, (MT > 0 ? MT - 1 : 0)>(W.sorted, P, a, j, nn, rad, pv.x, pv.y, vx, vy, AS, nullptr);
+                    const float2 ps = W.lpc[a];  // the program's start, stored with W.lpv[a] by ego_lp_inputs3 above
+                    orca_lp_group<GW, TWO, (MT > 0 ? MT - 1 : 0), true>(W.sorted, P, a, j, nn, rad, pv.x, pv.y, vx, vy, AS, nullptr, nullptr, nullptr,
+                                                                        ps.x, ps.y);
                 }
                 if (j == 0) W.lpc[a] = make_float2(vx, vy);
             }
