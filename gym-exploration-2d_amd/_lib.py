@@ -250,7 +250,7 @@ _ARGTYPES = {
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],
-                   "cagym_debug_wgtrace": [_vp, _int]}
+                   "cagym_debug_wgtrace": [_vp, _int], "cagym_debug_xtrace": [_vp]}
 
 _lib = None
 

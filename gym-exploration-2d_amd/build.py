@@ -22,7 +22,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libcagym_hip.so")
 # what the generation-3 units include, transitively: an edit of any other header leaves their twelve objects fresh
-K3_HEADERS = ["cagym_device.h", "cagym_trace.h", "cagym_spin.h", "cagym_orca.h", "cagym_kernels3.h", "cagym_split3.h", "cagym_launch3.h",
+K3_HEADERS = ["cagym_device.h", "cagym_trace.h", "cagym_spin.h", "cagym_oas_rank.h", "cagym_orca.h", "cagym_kernels3.h", "cagym_split3.h", "cagym_launch3.h",
               "../../include/cagym.h"]
 HEADERS = K3_HEADERS + ["cagym_gen1.h", "cagym_sensors.h", "cagym_ig.h", "cagym_ga3c_state.h", "cagym_ga3c.h", "cagym_ga3c16.h", "cagym_gen.h", "cagym_gen2.h",
                         "cagym_dmcts.h", "cagym_ig_episode.h", "cagym_ig_greedy.h", "cagym_episode_records.h", "cagym_episode_log.h", "cagym_snapshot.h", "cagym_stream.h",

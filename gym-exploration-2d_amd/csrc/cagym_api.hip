@@ -1603,6 +1603,12 @@ int cagym_debug_wavetrace(unsigned long long* out) {
 }
 #endif
 
+#ifdef CAGYM_XTRACE
+int cagym_debug_xtrace(unsigned long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xtrace), sizeof(unsigned long long) * CAGYM_XT_WGS * CAGYM_XT_STEPS * 8);
+}
+#endif
+
 #ifdef CAGYM_WGTRACE
 int cagym_debug_wgtrace(unsigned long long* out, int n_wg) {
     if (n_wg > CAGYM_WGTRACE_MAXWG) n_wg = CAGYM_WGTRACE_MAXWG;

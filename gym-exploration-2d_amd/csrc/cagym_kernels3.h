@@ -37,6 +37,7 @@
 
 #include "cagym_spin.h"   // lds_wait_ge: the bounded intra-workgroup wait
 #include "cagym_trace.h"  // STAMP / WGTRACE / WAVETRACE / PMARK: diagnostic hooks, empty in the shipped library
+#include "cagym_oas_rank.h"  // the OtherAgentsStates row of a key: integer count with an exact fallback
 
 #ifndef CAGYM_GW10
 #define CAGYM_GW10 8  // lanes per ORCA LP group when M <= 10 (nn <= 9 half-planes)
@@ -87,18 +88,32 @@ __device__ __forceinline__ LaneCtx make_ctx2(const CagymDev& D, int M, int wpw) 
     return C;
 }
 
-// pair slot p = agent * M + j  ->  (agent lane a, neighbour slot j, world_local wl, agent slot sl)
-struct PairIdx {
-    int a, j, wl, sl;
+// OtherAgentsStates row p = agent * (M - 1) + jj  ->  (agent lane a, world_local wl, agent slot sl, other slot j = the jj-th slot
+// that is not sl).  The workgroup's wpw M (M - 1) rows are dense in p: no lane stands for a self pair.
+// Compile-time M divides by constants; run-time M by inv_m = 2^32 / M + 1 and inv_k = 2^32 / (M - 1) + 1, exact for p < 2^16
+// (M - 1 == 1 has no such 32-bit constant: a = p).
+struct RowIdx {
+    int a, jj, j, wl, sl;
 };
-__device__ __forceinline__ PairIdx pair_of(int p, int M, uint32_t inv_m) {
-    PairIdx q;
-    q.a = (int)__umulhi((uint32_t)p, inv_m);  // p / M for p < 2^16 (inv_m = 2^32 / M + 1)
-    q.j = p - q.a * M;
-    q.wl = (int)__umulhi((uint32_t)q.a, inv_m);
-    q.sl = q.a - q.wl * M;
+template <int MT>
+__device__ __forceinline__ RowIdx row_of(int p, int M, int K, uint32_t inv_m, uint32_t inv_k) {
+    RowIdx q;
+    if (MT > 0) {
+        constexpr uint32_t MM = MT > 0 ? MT : 1, KK = MT > 1 ? MT - 1 : 1;
+        q.a = (int)((uint32_t)p / KK);
+        q.jj = p - q.a * (int)KK;
+        q.wl = (int)((uint32_t)q.a / MM);
+        q.sl = q.a - q.wl * (int)MM;
+    } else {
+        q.a = K == 1 ? p : (int)__umulhi((uint32_t)p, inv_k);
+        q.jj = p - q.a * K;
+        q.wl = (int)__umulhi((uint32_t)q.a, inv_m);
+        q.sl = q.a - q.wl * M;
+    }
+    q.j = q.jj + (q.jj >= q.sl ? 1 : 0);
     return q;
 }
+__host__ __device__ inline uint32_t cagym_inv_k(int M) { return M > 2 ? (uint32_t)(0x100000000ull / (uint32_t)(M - 1)) + 1u : 0u; }
 
 // Unordered pairs of M slots by circular difference: (i, i+k mod M) for k = 1..(M-1)/2, plus the M/2 diameters
 // when M is even.  p -> (world of the workgroup, i, j) with compile-time divisors only.
@@ -861,37 +876,56 @@ __device__ __forceinline__ void pair_phase3(const CagymDev& D, const Lds3& W, in
 }
 
 // ---- one 64-row chunk of the OtherAgentsStates table (sensors/OtherAgentsStatesSensor.py:11-77), straight to HBM ----------
-__device__ __forceinline__ void oas_row3(const Lds3& W, float* oas_out, int p, int npairs, int M, int MP, int K, int wpw,
-                                         int worlds_valid, uint32_t inv_m) {
+// (-DCAGYM_OAS_EXACT_RANK: A/B switch, the rank by the fp64 definition alone)
+#ifdef CAGYM_OAS_EXACT_RANK
+#define CAGYM_OAS_EXACT_V true
+#else
+#define CAGYM_OAS_EXACT_V false
+#endif
+template <int MT>
+__device__ __forceinline__ void oas_row3(const Lds3& W, float* oas_out, int p, int nrows, int M, int MP, int K, int wpw,
+                                         int worlds_valid, uint32_t inv_m, uint32_t inv_k) {
     PMARK("oas_begin");
-    if (p >= npairs) return;
-    const PairIdx q = pair_of(p, M, inv_m);
-    if (q.j == q.sl || q.wl >= worlds_valid) return;
-    const int n = W.wn[q.wl];
+    if (p >= nrows) return;
+    const RowIdx q = row_of<MT>(p, M, K, inv_m, inv_k);
+    if (q.wl >= worlds_valid) return;
     float* my = oas_out + ((size_t)blockIdx.x * wpw * M + q.a) * K * 10;
     const double kj = W.keys[q.a * MP + q.j];
-    if (!(kj > -INFINITY)) {  // unused row: zero (rows n-1 .. K-1 of an active agent, every row of an empty slot)
+    if (!(kj > -INFINITY)) {  // unused row: zero (rows n-1 .. K-1 of an active agent, every row of an empty slot; row jj in both)
         // (its own stores: merged with the live rows' values through a common array, the zeros cost ~20 register moves per chunk)
-        const int row = q.sl < n ? q.j - 1 : (q.j < q.sl ? q.j : q.j - 1);
-        float2* r2 = reinterpret_cast<float2*>(my + row * 10);
+        float2* r2 = reinterpret_cast<float2*>(my + q.jj * 10);
         const float2 z = make_float2(0.f, 0.f);
 #pragma unroll
         for (int c = 0; c < 5; c++) r2[c] = z;
         return;
     }
-    int before = 0;  // descending key, ties by descending index (stable sort, reversed: :28-34)
+    // descending key, ties by descending index (stable sort, reversed: :28-34): counted on the key bits, and by the fp64 definition
+    // on every lane of the wave when some lane's key is negative or tied (cagym_oas_rank.h)
     const double2* krow = reinterpret_cast<const double2*>(W.keys + q.a * MP);
+    const long long bj = oas_key_bits(kj);
+    OasRank r = {0, 0};
     for (int l2 = 0; l2 < M; l2 += 2) {  // keys beyond the world's slots (and the pad of an odd M) are -inf
         const double2 kk = krow[l2 >> 1];
-        before += (kk.x > kj) || (kk.x == kj && l2 + 0 > q.j);
-        before += (kk.y > kj) || (kk.y == kj && l2 + 1 > q.j);
+        oas_rank_add(r, kk.x, bj);
+        oas_rank_add(r, kk.y, bj);
     }
-    const int row = before;
-    PMARK("oas_ranked");
+    unsigned before = r.gt;
+    if (CAGYM_OAS_EXACT_V || __any(!oas_rank_covered(r, bj))) {
+        before = 0;
+        for (int l2 = 0; l2 < M; l2 += 2) {
+            const double2 kk = krow[l2 >> 1];
+            before += oas_before_exact(kk.x, kj, l2 + 0, q.j);
+            before += oas_before_exact(kk.y, kj, l2 + 1, q.j);
+        }
+    }
     const int b = q.a - q.sl + q.j;
-    const double dx = W.tpx[b] - W.tpx[q.a], dy = W.tpy[b] - W.tpy[q.a];
-    const double prx = W.tprx[q.a], pry = W.tpry[q.a], orx = -pry, ory = prx;
-    const double ovx = W.tvx[b], ovy = W.tvy[b], orad = W.tr[b];
+    const double epx = W.tpx[q.a], epy = W.tpy[q.a], prx = W.tprx[q.a], pry = W.tpry[q.a], erad = W.tr[q.a];
+    const double opx = W.tpx[b], opy = W.tpy[b], ovx = W.tvx[b], ovy = W.tvy[b], orad = W.tr[b];
+    const uint32_t ost = W.tst[b];
+    const unsigned row = before;
+    PMARK("oas_ranked");
+    const double dx = opx - epx, dy = opy - epy;
+    const double orx = -pry, ory = prx;
     float v[10];
     v[0] = (float)dx;
     v[1] = (float)dy;
@@ -900,9 +934,9 @@ __device__ __forceinline__ void oas_row3(const Lds3& W, float* oas_out, int p, i
     v[4] = (float)dot2(ovx, ovy, prx, pry);
     v[5] = (float)dot2(ovx, ovy, orx, ory);
     v[6] = (float)orad;
-    v[7] = (float)(W.tr[q.a] + orad);
+    v[7] = (float)(erad + orad);
     v[8] = (float)kj;
-    v[9] = ST_POLICY(W.tst[b]) == CAGYM_POL_STATIC ? 1.f : 2.f;
+    v[9] = ST_POLICY(ost) == CAGYM_POL_STATIC ? 1.f : 2.f;
     PMARK("oas_store");
     float2* r2 = reinterpret_cast<float2*>(my + row * 10);  // rows are 40 B: 8-byte aligned
 #pragma unroll
@@ -1123,22 +1157,22 @@ __device__ __forceinline__ void laser_scan3(const CagymDev& D, const Lds3& W, fl
     WGTRACE_W1(31);
 }
 
-// claim-and-process loop of the observation workers: chunks 0 .. nck-1 are 64 directed pairs each, chunk nck is the
-// scalar-observation store of the agent slots; the LaserScan (when asked for) follows behind them (laser_scan3 has its own
+// claim-and-process loop of the observation workers: chunks 0 .. nck-1 are 64 OtherAgentsStates rows each (row_of), chunk nck is
+// the scalar-observation store of the agent slots; the LaserScan (when asked for) follows behind them (laser_scan3 has its own
 // claim counters).  Every wave of the workgroup may call it; a wave leaves the chunk loop when the counter has run past the
 // last chunk (every wave reaches that: the counter only grows).
-template <bool OBST, int BATCH = 8>
-__device__ __forceinline__ void observation_chunks3(const CagymDev& D, const Lds3& W, const CagymOut& o, int npairs, int M, int MP,
-                                                    int K, int wpw, int worlds_valid, uint32_t inv_m, int ko = 0, int AS = 0) {
+template <int MT, bool OBST, int BATCH = 8>
+__device__ __forceinline__ void observation_chunks3(const CagymDev& D, const Lds3& W, const CagymOut& o, int nrows, int M, int MP,
+                                                    int K, int wpw, int worlds_valid, uint32_t inv_m, uint32_t inv_k, int ko = 0, int AS = 0) {
     const int lane = threadIdx.x & (CAGYM_WAVE - 1);
-    const int nck = (npairs + CAGYM_WAVE - 1) / CAGYM_WAVE;
+    const int nck = (nrows + CAGYM_WAVE - 1) / CAGYM_WAVE;
     for (;;) {
         int c = 0;
         if (lane == 0) c = __hip_atomic_fetch_add(&W.flag[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         c = __builtin_amdgcn_readlane(c, 0);
         if (c > nck) break;
         if (c < nck) {
-            if (o.obs_oas) oas_row3(W, o.obs_oas, c * CAGYM_WAVE + lane, npairs, M, MP, K, wpw, worlds_valid, inv_m);
+            if (o.obs_oas) oas_row3<MT>(W, o.obs_oas, c * CAGYM_WAVE + lane, nrows, M, MP, K, wpw, worlds_valid, inv_m, inv_k);
         } else {
             ego_obs3(D, W, o.obs_ego, lane, M, wpw, inv_m);
         }
@@ -1196,7 +1230,8 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
     LaneCtx C = make_ctx2(D, M, WPWT ? WPWT : CAGYM_WAVE / M);
     const uint32_t inv_m = (uint32_t)(0x100000000ull / (uint32_t)M) + 1u;
     const int nagents = C.wpw * M;               // agent slots of this workgroup (<= 64: wave 0)
-    const int npairs = C.wpw * M * M;            // directed pair slots
+    const uint32_t inv_k = cagym_inv_k(M);
+    const int nrows = C.wpw * M * K;             // OtherAgentsStates rows (directed pairs without the self pairs)
     const int nup = C.wpw * (M * (M - 1) / 2);   // unordered pairs
     const size_t NM = (size_t)D.N * M;
     float ep_ret = 0.f;
@@ -1417,13 +1452,15 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
             PMARK("D_s1_end");
             STAMP(3);
             WAVETRACE(t, 4);
+            XTRACE_ARRIVE(t);
         } else if (t > 0) {
             prio_rows3();
             PMARK("D_rows_begin");
             const CagymOut o_prev = out_rows_slice3(out, t - 1, NM, M);  // rows of step t-1
-            observation_chunks3<OBST, (ONE ? 8 : CAGYM_LASER_BATCH_ROLLOUT)>(D, W, o_prev, npairs, M, MP, K, C.wpw, C.worlds_valid, inv_m, ko, AS);
+            observation_chunks3<MT, OBST, (ONE ? 8 : CAGYM_LASER_BATCH_ROLLOUT)>(D, W, o_prev, nrows, M, MP, K, C.wpw, C.worlds_valid, inv_m, inv_k, ko, AS);
             prio_chain3(lagging);
             WAVETRACE(t, 4);
+            XTRACE_ARRIVE(t);
         }
         PMARK("D_end_barrierX");
         // (the other waves are long here when wave 0 arrives: the barrier releases it at once.  An arrival count that only wave 0 waits
@@ -1431,6 +1468,7 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
         __syncthreads();  // rows of step t-1 are out: the moved state may replace the old one
         WGTRACE1(25);
         WAVETRACE(t, 5);
+        XTRACE_BEHIND(t);
         if (s1_lane) {
             lds3_store_s1(W, A, tid);
             W.tmoved[tid] = moved ? 1 : 0;
@@ -1669,7 +1707,7 @@ __device__ inline void run_steps3(const CagymDev& D, unsigned char* smem, const 
     {
         CagymOut o_last = out_slice3(out, n_steps - 1, (size_t)D.N, NM, M);
         if (OBST && ONE && !W.flag[0]) o_last.laserscan = nullptr;  // scanned beside S2 (phase B); again only after a restart
-        observation_chunks3<OBST, (ONE ? 8 : CAGYM_LASER_BATCH_ROLLOUT)>(D, W, o_last, npairs, M, MP, K, C.wpw, C.worlds_valid, inv_m, ko, AS);
+        observation_chunks3<MT, OBST, (ONE ? 8 : CAGYM_LASER_BATCH_ROLLOUT)>(D, W, o_last, nrows, M, MP, K, C.wpw, C.worlds_valid, inv_m, inv_k, ko, AS);
         if (C.valid) {
             const Agent A = lds3_load_agent(W, threadIdx.x);  // own lane's record, written by this lane
             store_agent(D, A, (size_t)C.world * M + C.slot, true);

@@ -8,6 +8,8 @@
 //                      tools/cfg4_timeline.py use slots 20.. for the sub-phases of a ONE-step launch)
 //   -DCAGYM_WAVETRACE  lane 0 of EVERY WAVE of one workgroup stamps s_memtime at the marked points of the first 24 steps:
 //                      which wave arrives last at each barrier = the critical chain (tools/wave_trace.py, slow_wg_trace.py)
+//   -DCAGYM_XTRACE     lane 0 of every wave of 8 workgroups stamps its arrival at barrier X, wave 0 also the release, for 512 steps
+//                      (tools/barrier_x.py)
 //   -DCAGYM_PMARK      named comments in the ISA at the phase boundaries (tools/isa_phases.py, tools/isa_budget.py)
 #pragma once
 
@@ -146,6 +148,28 @@ __device__ unsigned long long g_wavetrace[CAGYM_WT_STEPS * CAGYM_WT_POINTS * 8];
 #define WAVETRACE(t, point) do { } while (0)
 #define LPWT_ROWS(t, base) nullptr
 #define LPWT(wt, k) do { } while (0)
+#endif
+
+// ---- XTRACE: who is last at barrier X (-DCAGYM_XTRACE, tools/barrier_x.py) ---------------------------------------------------
+// The lightest trace of the step's barrier X: lane 0 of every wave of 8 workgroups (every 128th) stamps s_memtime when it arrives
+// there - wave 0 with S1 done, the others with the rows of step t-1 written - and wave 0 once more behind it, for the 512 steps
+// of a launch.  Two stamps per wave and step (WAVETRACE: up to 16), so that the order of the arrivals is nearly the untraced one.
+#ifdef CAGYM_XTRACE
+#define CAGYM_XT_STEPS 512
+#define CAGYM_XT_WGS 8
+#define CAGYM_XT_STRIDE 128
+__device__ unsigned long long g_xtrace[CAGYM_XT_WGS * CAGYM_XT_STEPS * 8];
+#define XTRACE(t, slot)                                                                                                     \
+    do {                                                                                                                    \
+        if ((threadIdx.x & 63) == 0 && (blockIdx.x % CAGYM_XT_STRIDE) == 0 && blockIdx.x / CAGYM_XT_STRIDE < CAGYM_XT_WGS && \
+            (t) < CAGYM_XT_STEPS)                                                                                           \
+            g_xtrace[((blockIdx.x / CAGYM_XT_STRIDE) * CAGYM_XT_STEPS + (t)) * 8 + (slot)] = __builtin_amdgcn_s_memtime();  \
+    } while (0)
+#define XTRACE_ARRIVE(t) XTRACE(t, (threadIdx.x >> 6) & 3)
+#define XTRACE_BEHIND(t) do { if (threadIdx.x < 64) XTRACE(t, 4); } while (0)
+#else
+#define XTRACE_ARRIVE(t) do { } while (0)
+#define XTRACE_BEHIND(t) do { } while (0)
 #endif
 
 // ---- PMARK -------------------------------------------------------------------------------------------------------------------
