@@ -136,6 +136,9 @@ class GreedyParams(C.Structure):
 SNAP_MAGIC, SNAP_VERSION, SNAP_CORE, SNAP_IG = 0x43475331, 1, 1, 2  # CAGYM_SNAP_*
 
 
+CKPT_SECTIONS = ("host", "state", "pool", "stream", "log", "replay")  # CAGYM_CKPT_*: the entries of cagym_checkpoint_sizes
+
+
 class CagymSnapshotLayout(C.Structure):
     """cagym_snapshot_layout (include/cagym.h)."""
     _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("n_worlds", C.c_int32), ("max_agents", C.c_int32),
@@ -247,6 +250,9 @@ _ARGTYPES = {
     "cagym_trajectory_init": [_vp, _int, _vp],
     "cagym_trajectory_restart": [_vp, _vp, _int, _vp],
     "cagym_trajectory_get": [_vp, _P(CagymTrajectoryPtrs)],
+    "cagym_checkpoint_sizes": [_vp, _P(C.c_uint64)],
+    "cagym_checkpoint_save": [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp],
+    "cagym_checkpoint_load": [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp],
 }
 # exports of the diagnostic builds only (CAGYM_STAMPS / CAGYM_WAVETRACE / CAGYM_WGTRACE; csrc/cagym_trace.h), declared when present
 _DEBUG_ARGTYPES = {"cagym_debug_stamps": [_vp, _int], "cagym_debug_wavetrace_select": [_int], "cagym_debug_wavetrace": [_vp],

@@ -6,7 +6,8 @@ envs/wrappers.py:101-106): step(actions[N, M, 2]) -> (obs, rewards[N, M], game_o
 observations and outputs are PyTorch-ROCm tensors that the kernels write in place (zero-copy).
 
 Here: construction and plumbing, the gym surface, the attached policies, the state views and the parity accessors; the scenario pool
-is in _pool.py, the step consumers and the terminal observations in _consumers.py, snapshot / restore / fork in _snapshot.py.
+is in _pool.py, the step consumers and the terminal observations in _consumers.py, snapshot / restore / fork in _snapshot.py,
+checkpoint / load_checkpoint in _checkpoint.py.
 """
 import ctypes as C
 
@@ -15,6 +16,7 @@ import torch
 
 from . import _lib
 from . import scenarios as sc
+from ._checkpoint import EnvCheckpoint, _CheckpointMixin  # noqa: F401  (EnvCheckpoint is re-exported)
 from ._consumers import _ConsumersMixin
 from ._lib import _DevArray  # noqa: F401  (re-exported)
 from ._pool import _PoolMixin
@@ -35,7 +37,7 @@ _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game
 GAME_OVER_MODES = {"agent0": _lib.GO_AGENT0, "all": _lib.GO_ALL, "learning": _lib.GO_LEARNING}
 
 
-class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin):
+class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, _CheckpointMixin):
     def __init__(self, n_worlds, max_agents=10, n_scenarios=None, max_obstacles=0, game_over_mode="agent0",
                  collide_with_static=False, laserscan=False, device="cuda:0", dt=0.1, rvo_max_neighbors=0):
         self.L = _lib.load()

@@ -33,6 +33,7 @@
 #include "cagym_explore.h"
 #include "cagym_replay.h"
 #include "cagym_terminal.h"
+#include "cagym_checkpoint.h"
 
 namespace {
 
@@ -420,6 +421,211 @@ inline cagym_snapshot_layout snap_layout(const Env* e) {
 inline int snap_launch(Env* e, const SnapTable& T, const int32_t* ids, const int32_t* ids2, void* blob, int n, hipStream_t st) {
     if (n == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_snapshot_copy, dim3((unsigned)n), dim3(SNAP_NT), 0, st, T, ids, ids2, reinterpret_cast<unsigned char*>(blob));
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- the allocations of the stream, the episode log and the replay buffer: their *_init calls and cagym_checkpoint_load ---------------
+// the stream's device words, once per handle: {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
+inline int stream_alloc(Env* e) {
+    const int N = e->cfg.n_worlds;
+    if (!e->stream.next_episode) {
+        unsigned char* buf = nullptr;
+        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
+        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
+        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
+        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
+        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
+    }
+    e->stream.episode = e->D.episode;
+    e->stream.map_bits = const_cast<uint32_t*>(e->D.map_bits);
+    e->stream.N = N;
+    e->stream.depth = e->cfg.n_scenarios / N;
+    return CAGYM_OK;
+}
+// the log's running block (once per handle) and its ring (once per capacity); e->elog is complete afterwards
+inline int eplog_alloc(Env* e, int capacity) {
+    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
+    EpLog G = e->elog;
+    if (!G.run.t_run) {  // the running block: once per handle
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, 8 * (N * M + 2 * N + 2) + 4 * (4 * N + 2))) return rc;
+        G.run.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
+        G.run.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
+        G.pos = reinterpret_cast<unsigned long long*>(b); b += 8 * N;
+        G.seq = reinterpret_cast<unsigned long long*>(b); b += 8;
+        G.head = reinterpret_cast<unsigned long long*>(b); b += 8;
+        G.run.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.run.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
+        G.run.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.cnt = reinterpret_cast<int32_t*>(b); b += 4 * N;
+        G.run.desync = reinterpret_cast<int32_t*>(b);
+        e->elog = G;  // kept whatever becomes of the ring's allocation
+    }
+    if (!e->elog_ring || G.capacity != capacity) {  // the ring: once per capacity (8-byte columns first, then 4-byte ones, then bytes)
+        if (int rc = ring_alloc(e, &e->elog_ring, "elog_ring", L * (8 * (2 + 2 * M) + 4 * 7 + M), false)) return rc;
+        unsigned char* b = static_cast<unsigned char*>(e->elog_ring);
+        G.slice = reinterpret_cast<long long*>(b); b += 8 * L;
+        G.ret = reinterpret_cast<double*>(b); b += 8 * L;
+        G.t = reinterpret_cast<double*>(b); b += 8 * L * M;
+        G.extra_t = reinterpret_cast<double*>(b); b += 8 * L * M;
+        G.key = reinterpret_cast<uint32_t*>(b); b += 4 * L;
+        G.world = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.episode = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.steps = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.outcome = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.n_agents = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.n_obst = reinterpret_cast<int32_t*>(b); b += 4 * L;
+        G.flags = b;
+        G.capacity = capacity;
+    }
+    e->elog = G;
+    return CAGYM_OK;
+}
+// the replay's words and per-slot tables (once per handle) and its buffer (once per capacity); e->replay is complete afterwards
+inline int replay_alloc(Env* e, int capacity) {
+    const size_t S = (size_t)e->cfg.n_scenarios;
+    ReplayDev R = e->replay;
+    if (!R.words) {  // once per handle: the words (u64), buf_gen and a pad word, then the two per-slot tables
+        unsigned char* b = nullptr;
+        if (int rc = dalloc(e, &b, 8 * (size_t)RPW_WORDS + 8 + 8 * S)) return rc;
+        R.words = reinterpret_cast<unsigned long long*>(b); b += 8 * (size_t)RPW_WORDS;
+        R.buf_gen = reinterpret_cast<uint32_t*>(b); b += 8;
+        R.slot_key = reinterpret_cast<uint32_t*>(b); b += 4 * S;
+        R.slot_gen = reinterpret_cast<uint32_t*>(b);
+        e->replay = R;  // kept whatever becomes of the buffer's allocation
+    }
+    if (!e->replay_ring || R.Q != capacity) {
+        if (int rc = ring_alloc(e, &e->replay_ring, "replay_ring", 4 * (size_t)capacity, false)) return rc;
+        R.buf_key = static_cast<uint32_t*>(e->replay_ring);
+        R.Q = capacity;
+    }
+    e->replay = R;
+    return CAGYM_OK;
+}
+
+// ---- whole-handle checkpoint (csrc/cagym_checkpoint.h) -----------------------------------------------------------------------------------
+// The host header of a checkpoint: opaque to the caller, plain words to the library.  Every member is written (the struct has no
+// padding: static_assert below), so two saves of the same state give the same bytes.
+struct CkptHost {
+    uint32_t magic, version;
+    uint64_t sizes[CAGYM_CKPT_SECTIONS];
+    // cagym_config without `device`
+    int32_t n_worlds, max_agents, n_scenarios, max_obstacles, game_over_mode, collide_with_static, laserscan, rvo_max_neighbors;
+    double dt;
+    int32_t cfg_reserved;
+    // the pool's host state (cagym_set_scenarios / cagym_generate_*)
+    int32_t scenarios_set, heading0_set, any_rvo, obst_rvo, n_ig;
+    // cagym_stream_scenarios / cagym_stream_set_params
+    int32_t streaming;
+    uint32_t stream_gen;
+    int32_t log_ready, log_capacity;  // cagym_episode_log_init
+    // cagym_stream_replay_init / _set
+    int32_t replay_on, replay_capacity;
+    uint32_t replay_mask, reserved;
+    double replay_p;
+    uint64_t replay_seed;
+    cagym_gen2_params stream_P;
+};
+static_assert(sizeof(CkptHost) == 8 + 8 * CAGYM_CKPT_SECTIONS + 8 * 4 + 8 + 4 + 5 * 4 + 2 * 4 + 2 * 4 + 4 * 4 + 8 + 8 + sizeof(cagym_gen2_params) &&
+                  sizeof(cagym_gen2_params) == 64,
+              "CkptHost has no padding");
+
+// what a checkpoint does not carry
+inline int ckpt_refuse(Env* e, const char* what) {
+    const std::string w(what);
+    if (e->streaming && e->explore_stream)
+        return fail(e, CAGYM_E_UNSUPPORTED, w + " on an exploration stream: the per-slot distance fields are not part of a checkpoint");
+    if (e->ig_ready)
+        return fail(e, CAGYM_E_UNSUPPORTED, w + " after cagym_ig_init: per-slot distance fields and planner workspaces are not part of a checkpoint");
+    if (e->traj_ready) return fail(e, CAGYM_E_STATE, w + " with a trajectory ring initialised: its slices are not part of a checkpoint");
+    if (e->rec_ready) return fail(e, CAGYM_E_STATE, w + " with episode records initialised: their table is not part of a checkpoint");
+    return CAGYM_OK;
+}
+
+// the pool rows of a checkpoint: snap_pool_table's fields without the rasters
+inline SnapTable ckpt_pool_table(const Env* e, int mode) {
+    const SnapTable P = snap_pool_table(e);
+    SnapTable T = P;
+    T.mode = mode;
+    T.n_fields = 0;
+    uint64_t off = SNAP_HEADER_BYTES;
+    for (int k = 0; k < P.n_fields; k++) {
+        if (P.f[k].base == reinterpret_cast<const unsigned char*>(e->D.map_bits)) continue;
+        T.f[T.n_fields++] = {P.f[k].base, P.f[k].bytes, (uint32_t)off};
+        off += ((uint64_t)P.f[k].bytes + 15) & ~(uint64_t)15;
+    }
+    T.row_bytes = off;
+    return T;
+}
+
+// The flat sections of a handle whose stream / log / replay state is (streaming, log capacity or 0, replay capacity or 0): sizes
+// alone while the arrays are not allocated (with_pointers = false), else the table of k_checkpoint_flat as well.
+inline CkptTable ckpt_flat_table(const Env* e, bool streaming, int log_capacity, int replay_capacity, uint64_t* sizes, bool with_pointers) {
+    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, S = e->cfg.n_scenarios;
+    CkptTable T{};
+    uint64_t off = 0;
+    auto add = [&](const void* base, size_t bytes) {
+        T.f[T.n_fields++] = {with_pointers ? reinterpret_cast<unsigned char*>(const_cast<void*>(base)) : nullptr, (uint64_t)bytes, off};
+        off += ((uint64_t)bytes + 15) & ~(uint64_t)15;
+    };
+    if (streaming) {
+        const StreamDev& W = e->stream;
+        add(W.generated, 16);  // generated, n_failed, n_lapped: one allocation (stream_alloc)
+        add(W.next_episode, 4 * N);
+    }
+    sizes[CAGYM_CKPT_STREAM] = off;
+    if (log_capacity > 0) {
+        const EpLog& G = e->elog;
+        const size_t L = (size_t)log_capacity;
+        add(G.slice, 8 * L); add(G.ret, 8 * L); add(G.t, 8 * L * M); add(G.extra_t, 8 * L * M);
+        add(G.key, 4 * L); add(G.world, 4 * L); add(G.episode, 4 * L); add(G.steps, 4 * L); add(G.outcome, 4 * L); add(G.n_agents, 4 * L);
+        add(G.n_obst, 4 * L); add(G.flags, L * M);
+        add(G.run.t_run, 8 * N * M); add(G.run.ret_run, 8 * N); add(G.run.steps_run, 4 * N); add(G.run.atgoal_run, 4 * N); add(G.run.cursor, 4 * N);
+        add(G.run.desync, 4); add(G.seq, 8); add(G.head, 8);
+    }
+    sizes[CAGYM_CKPT_LOG] = off - sizes[CAGYM_CKPT_STREAM];
+    if (replay_capacity > 0) {
+        const ReplayDev& R = e->replay;
+        add(R.buf_key, 4 * (size_t)replay_capacity); add(R.words, 8 * (size_t)RPW_WORDS); add(R.buf_gen, 4); add(R.slot_key, 4 * S);
+        add(R.slot_gen, 4 * S);
+    }
+    sizes[CAGYM_CKPT_REPLAY] = off - sizes[CAGYM_CKPT_STREAM] - sizes[CAGYM_CKPT_LOG];
+    T.bytes = off;
+    return T;
+}
+static_assert(2 + 20 + 5 <= CKPT_MAX_FIELDS, "CkptTable holds every flat field");
+
+// every section size of a handle in the given stream / log / replay state
+inline void ckpt_sizes(const Env* e, bool streaming, int log_capacity, int replay_capacity, uint64_t* sizes) {
+    sizes[CAGYM_CKPT_HOST] = sizeof(CkptHost);
+    sizes[CAGYM_CKPT_STATE] = (uint64_t)e->cfg.n_worlds * snap_state_table(e, SNAP_GATHER).row_bytes;
+    sizes[CAGYM_CKPT_POOL] = (uint64_t)e->cfg.n_scenarios * ckpt_pool_table(e, SNAP_SLOT_GATHER).row_bytes;
+    (void)ckpt_flat_table(e, streaming, log_capacity, replay_capacity, sizes, false);
+}
+inline void ckpt_sizes(const Env* e, uint64_t* sizes) {
+    ckpt_sizes(e, e->streaming, e->log_ready ? e->elog.capacity : 0, e->replay_on ? e->replay.Q : 0, sizes);
+}
+inline uint64_t ckpt_blob_bytes(const uint64_t* sizes) {
+    uint64_t b = 0;
+    for (int k = CAGYM_CKPT_STATE; k < CAGYM_CKPT_SECTIONS; k++) b += sizes[k];
+    return b;
+}
+
+// the three copy launches of a save (to_blob) or a load, for a blob whose flat sections are those of (streaming, log_capacity, replay_capacity)
+inline int ckpt_copy(Env* e, bool to_blob, unsigned char* blob, bool streaming, int log_capacity, int replay_capacity, hipStream_t st) {
+    uint64_t sizes[CAGYM_CKPT_SECTIONS];
+    ckpt_sizes(e, streaming, log_capacity, replay_capacity, sizes);
+    if (int rc = snap_launch(e, snap_state_table(e, to_blob ? SNAP_GATHER : SNAP_SCATTER), nullptr, nullptr, blob, e->cfg.n_worlds, st)) return rc;
+    blob += sizes[CAGYM_CKPT_STATE];
+    if (int rc = snap_launch(e, ckpt_pool_table(e, to_blob ? SNAP_SLOT_GATHER : SNAP_SLOT_SCATTER), nullptr, nullptr, blob, e->cfg.n_scenarios, st))
+        return rc;
+    blob += sizes[CAGYM_CKPT_POOL];
+    CkptTable T = ckpt_flat_table(e, streaming, log_capacity, replay_capacity, sizes, true);
+    T.to_blob = to_blob ? 1 : 0;
+    if (T.bytes == 0) return CAGYM_OK;
+    const unsigned grid = (unsigned)std::min<uint64_t>((T.bytes / 16 + CKPT_NT - 1) / CKPT_NT, CKPT_MAX_GRID);
+    hipLaunchKernelGGL(k_checkpoint_flat, dim3(grid), dim3(CKPT_NT), 0, st, T, blob);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
@@ -924,19 +1130,8 @@ int cagym_stream_scenarios(void* env, const cagym_gen2_params* params, int32_t* 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ON_DEVICE(e);
     const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
-    if (!e->stream.next_episode) {  // {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
-        unsigned char* buf = nullptr;
-        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
-        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
-        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
-        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
-        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
-    }
+    if (int rc = stream_alloc(e)) return rc;
     StreamDev& T = e->stream;
-    T.episode = e->D.episode;
-    T.map_bits = const_cast<uint32_t*>(e->D.map_bits);
-    T.N = N;
-    T.depth = S / N;
     // the first fill counts: generated = S, n_failed = its failures
     HIPCHK(e, hipMemsetAsync(T.generated, 0, 16, st));
     HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.generated), S, 1, st));
@@ -1013,22 +1208,8 @@ int cagym_stream_replay_init(void* env, int capacity, uint64_t seed, void* strea
     ON_DEVICE(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t S = (size_t)e->cfg.n_scenarios;
-    ReplayDev R = e->replay;
-    if (!R.words) {  // once per handle: the words (u64), buf_gen and a pad word, then the two per-slot tables
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, 8 * (size_t)RPW_WORDS + 8 + 8 * S)) return rc;
-        R.words = reinterpret_cast<unsigned long long*>(b); b += 8 * (size_t)RPW_WORDS;
-        R.buf_gen = reinterpret_cast<uint32_t*>(b); b += 8;
-        R.slot_key = reinterpret_cast<uint32_t*>(b); b += 4 * S;
-        R.slot_gen = reinterpret_cast<uint32_t*>(b);
-        e->replay = R;  // kept whatever becomes of the buffer's allocation
-    }
-    if (!e->replay_ring || R.Q != capacity) {
-        if (int rc = ring_alloc(e, &e->replay_ring, "replay_ring", 4 * (size_t)capacity, false)) return rc;
-        R.buf_key = static_cast<uint32_t*>(e->replay_ring);
-        R.Q = capacity;
-    }
-    e->replay = R;
+    if (int rc = replay_alloc(e, capacity)) return rc;
+    const ReplayDev R = e->replay;
     e->replay_seed = seed;
     // a handle that is armed already keeps its tables (they name replayed keys): only the buffer and the counters are cleared
     const unsigned grid = (unsigned)((e->cfg.n_worlds + CAGYM_WAVE - 1) / CAGYM_WAVE);
@@ -1994,41 +2175,7 @@ int cagym_episode_log_init(void* env, int capacity, void* stream) {
     ENTRY_POOL(e, env, "cagym_episode_log_init");
     if (capacity < 1) return fail(e, CAGYM_E_INVALID, "cagym_episode_log_init: capacity must be >= 1");
     ON_DEVICE(e);
-    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
-    EpLog G = e->elog;
-    if (!G.run.t_run) {  // the running block: once per handle
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, 8 * (N * M + 2 * N + 2) + 4 * (4 * N + 2))) return rc;
-        G.run.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
-        G.run.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
-        G.pos = reinterpret_cast<unsigned long long*>(b); b += 8 * N;
-        G.seq = reinterpret_cast<unsigned long long*>(b); b += 8;
-        G.head = reinterpret_cast<unsigned long long*>(b); b += 8;
-        G.run.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.run.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
-        G.run.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.cnt = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.run.desync = reinterpret_cast<int32_t*>(b);
-        e->elog = G;  // kept whatever becomes of the ring's allocation
-    }
-    if (!e->elog_ring || G.capacity != capacity) {  // the ring: once per capacity (8-byte columns first, then 4-byte ones, then bytes)
-        if (int rc = ring_alloc(e, &e->elog_ring, "elog_ring", L * (8 * (2 + 2 * M) + 4 * 7 + M), false)) return rc;
-        unsigned char* b = static_cast<unsigned char*>(e->elog_ring);
-        G.slice = reinterpret_cast<long long*>(b); b += 8 * L;
-        G.ret = reinterpret_cast<double*>(b); b += 8 * L;
-        G.t = reinterpret_cast<double*>(b); b += 8 * L * M;
-        G.extra_t = reinterpret_cast<double*>(b); b += 8 * L * M;
-        G.key = reinterpret_cast<uint32_t*>(b); b += 4 * L;
-        G.world = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.episode = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.steps = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.outcome = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.n_agents = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.n_obst = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.flags = b;
-        G.capacity = capacity;
-    }
-    e->elog = G;
+    if (int rc = eplog_alloc(e, capacity)) return rc;
     e->log_ready = true;
     return eplog_restart(e, nullptr, true, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2135,6 +2282,120 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (int rc = snap_launch(e, snap_state_table(e, SNAP_FORK, true), src, dst, nullptr, n, st)) return rc;
     return snap_launch(e, snap_pool_table(e), src, dst, nullptr, n, st);
+}
+
+// ---- whole-handle checkpoint (csrc/cagym_checkpoint.h) -----------------------------------------------------------------------------------
+int cagym_checkpoint_sizes(void* env, uint64_t* sizes) {
+    ENTRY_POOL(e, env, "cagym_checkpoint_sizes");
+    if (int rc = ckpt_refuse(e, "cagym_checkpoint_sizes")) return rc;
+    if (!sizes) return fail(e, CAGYM_E_INVALID, "cagym_checkpoint_sizes: null sizes");
+    ckpt_sizes(e, sizes);
+    return CAGYM_OK;
+}
+
+// the buffer checks save and load share; sizes: what the buffers must hold
+static int ckpt_check_buffers(Env* e, const char* what, const void* host_words, uint64_t host_bytes, const void* blob, uint64_t blob_bytes,
+                              const uint64_t* sizes) {
+    const std::string w(what);
+    if (!host_words || host_bytes < sizes[CAGYM_CKPT_HOST]) return fail(e, CAGYM_E_INVALID, w + ": host_words is NULL or shorter than the host header");
+    if (!blob || (reinterpret_cast<uintptr_t>(blob) & 15)) return fail(e, CAGYM_E_INVALID, w + ": the blob must be a 16-byte aligned device buffer");
+    if (blob_bytes < ckpt_blob_bytes(sizes)) return fail(e, CAGYM_E_INVALID, w + ": blob_bytes is smaller than the sum of the device sections");
+    return CAGYM_OK;
+}
+
+int cagym_checkpoint_save(void* env, void* host_words, uint64_t host_bytes, void* blob, uint64_t blob_bytes, void* stream) {
+    ENTRY_POOL(e, env, "cagym_checkpoint_save");
+    if (int rc = ckpt_refuse(e, "cagym_checkpoint_save")) return rc;
+    CkptHost H{};
+    ckpt_sizes(e, H.sizes);
+    if (int rc = ckpt_check_buffers(e, "cagym_checkpoint_save", host_words, host_bytes, blob, blob_bytes, H.sizes)) return rc;
+    ON_DEVICE(e);  // a pending cagym_step_begin stays valid: nothing moves
+    const cagym_config& c = e->cfg;
+    H.magic = CAGYM_CKPT_MAGIC; H.version = CAGYM_CKPT_VERSION;
+    H.n_worlds = c.n_worlds; H.max_agents = c.max_agents; H.n_scenarios = c.n_scenarios; H.max_obstacles = c.max_obstacles;
+    H.game_over_mode = c.game_over_mode; H.collide_with_static = c.collide_with_static; H.laserscan = c.laserscan;
+    H.rvo_max_neighbors = c.rvo_max_neighbors; H.dt = c.dt; H.cfg_reserved = c.reserved;
+    H.scenarios_set = 1; H.heading0_set = e->D.sc_heading0 ? 1 : 0; H.any_rvo = e->any_rvo; H.obst_rvo = e->obst_rvo; H.n_ig = e->n_ig;
+    H.streaming = e->streaming ? 1 : 0; H.stream_gen = e->stream_gen;
+    if (e->streaming) H.stream_P = e->stream_P;
+    H.log_ready = e->log_ready ? 1 : 0; H.log_capacity = e->log_ready ? e->elog.capacity : 0;
+    H.replay_on = e->replay_on ? 1 : 0; H.replay_capacity = e->replay_on ? e->replay.Q : 0;
+    if (e->replay_on) {
+        H.replay_mask = e->replay_mask; H.replay_p = e->replay_p; H.replay_seed = e->replay_seed;
+    }
+    if (int rc = ckpt_copy(e, true, reinterpret_cast<unsigned char*>(blob), e->streaming, H.log_capacity, H.replay_capacity, reinterpret_cast<hipStream_t>(stream)))
+        return rc;
+    memcpy(host_words, &H, sizeof(H));
+    return CAGYM_OK;
+}
+
+int cagym_checkpoint_load(void* env, const void* host_words, uint64_t host_bytes, const void* blob, uint64_t blob_bytes, void* stream) {
+    ENTRY(e, env);
+    if (int rc = ckpt_refuse(e, "cagym_checkpoint_load")) return rc;
+    const char* const bad = "cagym_checkpoint_load: ";
+    if (!host_words || host_bytes < sizeof(CkptHost)) return fail(e, CAGYM_E_INVALID, std::string(bad) + "host_words is NULL or shorter than the host header");
+    CkptHost H;
+    memcpy(&H, host_words, sizeof(H));
+    if (H.magic != CAGYM_CKPT_MAGIC || H.version != CAGYM_CKPT_VERSION) return fail(e, CAGYM_E_INVALID, std::string(bad) + "not a checkpoint header of this version (magic, version)");
+    const cagym_config& c = e->cfg;
+    if (H.n_worlds != c.n_worlds || H.max_agents != c.max_agents || H.n_scenarios != c.n_scenarios || H.max_obstacles != c.max_obstacles ||
+        H.game_over_mode != c.game_over_mode || H.collide_with_static != c.collide_with_static || H.laserscan != c.laserscan ||
+        H.rvo_max_neighbors != c.rvo_max_neighbors || memcmp(&H.dt, &c.dt, sizeof(double)) != 0 || H.cfg_reserved != c.reserved)
+        return fail(e, CAGYM_E_INVALID, std::string(bad) + "the checkpoint's configuration is not this handle's (every cagym_config field except device must match)");
+    // the members, as the calls that set them check them
+    const int K = c.max_obstacles;
+    auto flag = [](int32_t v) { return v == 0 || v == 1; };
+    const bool flags01 = H.scenarios_set == 1 && flag(H.heading0_set) && flag(H.any_rvo) && flag(H.obst_rvo) && flag(H.streaming) &&
+                         flag(H.log_ready) && flag(H.replay_on) && H.reserved == 0;
+    if (!flags01 || H.n_ig < N_IG_RANDOM || H.n_ig > c.max_agents || (H.obst_rvo && !(H.any_rvo && K > 0)))
+        return fail(e, CAGYM_E_INVALID, std::string(bad) + "the header's pool flags are not ones a pool setter leaves");
+    if ((H.log_ready != 0) != (H.log_capacity >= 1) || H.log_capacity < 0 || (H.replay_on != 0) != (H.replay_capacity >= 1) || H.replay_capacity < 0 ||
+        (H.replay_on && !H.streaming) || (H.replay_on && (!(H.replay_p >= 0.0 && H.replay_p <= 1.0) || (H.replay_mask & ~7u))) || H.stream_gen < 1)
+        return fail(e, CAGYM_E_INVALID, std::string(bad) + "the header's stream, log or replay members contradict each other");
+    if (H.obst_rvo && check_obst_rvo_capacity(e) != CAGYM_OK) return fail(e, CAGYM_E_INVALID, std::string(bad) + e->err);
+    if (H.streaming) {
+        Gen2Flags F;
+        if (stream_check(e, "cagym_checkpoint_load", &H.stream_P, F) != CAGYM_OK)
+            return fail(e, CAGYM_E_INVALID, std::string(bad) + "the stream's parameter set is refused: " + e->err);
+        if ((F.any_rvo && !H.any_rvo) || (F.obst_rvo && !H.obst_rvo))
+            return fail(e, CAGYM_E_INVALID, std::string(bad) + "the header's RVO flags do not cover the stream's parameter set");
+    }
+    uint64_t sizes[CAGYM_CKPT_SECTIONS];
+    ckpt_sizes(e, H.streaming != 0, H.log_capacity, H.replay_capacity, sizes);
+    if (memcmp(sizes, H.sizes, sizeof(sizes)) != 0)
+        return fail(e, CAGYM_E_INVALID, std::string(bad) + "the header's section sizes are not those of its own configuration and capacities");
+    if (int rc = ckpt_check_buffers(e, "cagym_checkpoint_load", host_words, host_bytes, blob, blob_bytes, sizes)) return rc;
+    ON_DEVICE(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every allocation before the first member changes
+    if (H.streaming)
+        if (int rc = stream_alloc(e)) return rc;
+    if (H.log_ready)
+        if (int rc = eplog_alloc(e, H.log_capacity)) return rc;
+    if (H.replay_on)
+        if (int rc = replay_alloc(e, H.replay_capacity)) return rc;
+    e->begun = false;
+    if (e->log_ready && !H.log_ready)  // a log the checkpoint lacks: emptied, and it stays initialised
+        if (int rc = eplog_restart(e, nullptr, true, st)) return rc;
+    e->log_ready = e->log_ready || H.log_ready;
+    e->scenarios_set = true;
+    e->D.sc_heading0 = H.heading0_set ? e->sc_heading_buf : nullptr;
+    e->any_rvo = H.any_rvo; e->obst_rvo = H.obst_rvo; e->n_ig = H.n_ig;
+    e->D.ko = H.obst_rvo ? 2 * K : 0;
+    e->streaming = H.streaming != 0; e->explore_stream = false;
+    if (H.streaming) e->stream_P = H.stream_P;
+    e->stream_gen = H.stream_gen;
+    e->replay_on = H.replay_on != 0;
+    if (H.replay_on) {
+        e->replay_p = H.replay_p; e->replay_mask = H.replay_mask; e->replay_seed = H.replay_seed;
+    }
+    if (int rc = ckpt_copy(e, false, reinterpret_cast<unsigned char*>(const_cast<void*>(blob)), H.streaming != 0, H.log_capacity, H.replay_capacity, st))
+        return rc;
+    if (K > 0) {  // the rasters: a pure function of the rectangles the pool rows brought
+        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)c.n_scenarios), dim3(256), 0, st, e->sc_obst, e->D.sc_nobst, K, const_cast<uint32_t*>(e->D.map_bits));
+        HIPCHK(e, hipGetLastError());
+    }
+    return CAGYM_OK;
 }
 
 }  // extern "C"

@@ -15,8 +15,10 @@
 //   SNAP_SCATTER  blob row ids[r] (null: r)                      -> SoA row of the origin world its header names
 //   SNAP_FORK     SoA row of world ids[r]                        -> SoA row of world ids2[r]
 //   SNAP_POOL     pool row of the scenario slot of world ids[r]  -> pool row of the scenario slot of world ids2[r]
-// Every id read from a caller's list (and the origin id read from a blob header) is checked against [0, N): a workgroup that
-// finds one outside returns before it touches anything else, so a wrong list cannot fault the device.
+//   SNAP_SLOT_GATHER   pool row of slot r                        -> blob row r, whose header takes the slot   (cagym_checkpoint_save)
+//   SNAP_SLOT_SCATTER  blob row r                                -> pool row of the slot its header names      (cagym_checkpoint_load)
+// Every id read from a caller's list (and the origin id read from a blob header) is checked against [0, N) - a slot against
+// [0, S) -: a workgroup that finds one outside returns before it touches anything else, so a wrong list cannot fault the device.
 //
 // A world's scenario slot is computed, not stored: (world + episode[world] * N) % S, as every kernel derives it
 // (cagym_sensors.h, cagym_ig.h).  SNAP_POOL reads `episode` of both worlds; cagym_fork leaves dst's episode as it is, so the two
@@ -28,7 +30,7 @@
 #define SNAP_NT 256
 #define SNAP_HEADER_BYTES 16 /* {origin world id, CAGYM_SNAP_MAGIC, 0, 0} */
 
-enum { SNAP_GATHER = 0, SNAP_SCATTER = 1, SNAP_FORK = 2, SNAP_POOL = 3 };
+enum { SNAP_GATHER = 0, SNAP_SCATTER = 1, SNAP_FORK = 2, SNAP_POOL = 3, SNAP_SLOT_GATHER = 4, SNAP_SLOT_SCATTER = 5 };
 
 struct SnapField {
     unsigned char* base;  // row r of the field starts at base + r * bytes
@@ -47,18 +49,22 @@ struct SnapTable {
 __global__ void __launch_bounds__(SNAP_NT) k_snapshot_copy(SnapTable T, const int32_t* __restrict__ ids, const int32_t* __restrict__ ids2,
                                                            unsigned char* blob) {
     const int r = blockIdx.x, tid = threadIdx.x;
+    const bool slots = T.mode >= SNAP_SLOT_GATHER;  // rows of the pool: ids and headers are slots, bounded by S
+    const bool gather = T.mode == SNAP_GATHER || T.mode == SNAP_SLOT_GATHER, scatter = T.mode == SNAP_SCATTER || T.mode == SNAP_SLOT_SCATTER;
+    const long long rows = slots ? T.S : T.N;
+    const uint32_t magic = slots ? CAGYM_CKPT_ROW_MAGIC : CAGYM_SNAP_MAGIC;
     const long long a = ids ? ids[r] : r;
-    if (a < 0 || a >= T.N) return;  // a world id, or a blob row id (a blob holds at most N rows)
+    if (a < 0 || a >= rows) return;  // a world id or a slot, or a blob row id (a blob holds at most N rows, of slots S)
     long long src_row = a, dst_row = a;
     unsigned char* brow = nullptr;
-    if (T.mode == SNAP_GATHER) {
+    if (gather) {
         brow = blob + (size_t)r * T.row_bytes;
-        if (tid == 0) *reinterpret_cast<uint4*>(brow) = make_uint4((uint32_t)a, CAGYM_SNAP_MAGIC, 0u, 0u);
-    } else if (T.mode == SNAP_SCATTER) {
+        if (tid == 0) *reinterpret_cast<uint4*>(brow) = make_uint4((uint32_t)a, magic, 0u, 0u);
+    } else if (scatter) {
         brow = blob + (size_t)a * T.row_bytes;
         const uint4 h = *reinterpret_cast<const uint4*>(brow);
         dst_row = (int32_t)h.x;
-        if (h.y != CAGYM_SNAP_MAGIC || dst_row < 0 || dst_row >= T.N) return;  // not a row cagym_snapshot wrote
+        if (h.y != magic || dst_row < 0 || dst_row >= rows) return;  // not a row cagym_snapshot / cagym_checkpoint_save wrote
     } else {
         const long long b = ids2[r];
         if (b < 0 || b >= T.N) return;
@@ -70,7 +76,6 @@ __global__ void __launch_bounds__(SNAP_NT) k_snapshot_copy(SnapTable T, const in
         }
         if (src_row == dst_row) return;
     }
-    const bool gather = T.mode == SNAP_GATHER, scatter = T.mode == SNAP_SCATTER;
     for (uint32_t c = SNAP_HEADER_BYTES + 16u * tid; c < (uint32_t)T.row_bytes; c += 16u * SNAP_NT) {
         // the field chunk c lies in: the last one that starts at or before it (offsets ascend; the first is SNAP_HEADER_BYTES)
         unsigned char* base = nullptr;

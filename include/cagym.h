@@ -856,6 +856,52 @@ int cagym_trajectory_init(void* env, int n_slices, void* stream);
 int cagym_trajectory_restart(void* env, const uint8_t* world_mask, int clear, void* stream);
 int cagym_trajectory_get(void* env, cagym_trajectory_ptrs* out);
 
+/* ---- Whole-handle checkpoint: state, pool, stream, episode log and replay buffer (csrc/cagym_checkpoint.h) ---------------------------
+ * cagym_restore / cagym_fork move SOME worlds onto another timeline and therefore refuse a streaming handle and an initialised log.
+ * A checkpoint moves the WHOLE handle: it carries everything a run of cagym_stream_scenarios + cagym_stream_set_params +
+ * cagym_episode_log_init + cagym_stream_replay_init depends on, and a load puts a fresh handle of the same configuration, or the same
+ * handle, back on the same timeline bit for bit (a slot is a pure function of parameter set and key, the replay draw of seed, key, p
+ * and buffer, the harvest works in row order, the counters are integer sums).  A handle that is not streaming may be checkpointed
+ * too: its pool then travels with the checkpoint instead of being installed again by hand.
+ * A checkpoint is two caller-owned buffers:
+ *   the HOST header, sizes[CAGYM_CKPT_HOST] bytes that begin {magic u32, version u32, sizes u64 [CAGYM_CKPT_SECTIONS]} and are opaque
+ *     from there on: every cagym_config field except `device`,
+ *     and the host-side members the pool setters, cagym_stream_scenarios, cagym_stream_set_params, cagym_stream_replay_init / _set and
+ *     cagym_episode_log_init set: pool installed, headings in use, the RVO / IG flags, streaming, the stream's parameter set and
+ *     parameter generation, replay armed with p, mask, seed and capacity, log initialised with its capacity;
+ *   the DEVICE blob, 16-byte aligned: the sections CAGYM_CKPT_STATE .. CAGYM_CKPT_REPLAY back to back in enum order, each a multiple
+ *     of 16 bytes (0: absent).  STATE: cagym_snapshot's rows of all N worlds.  POOL: one row per scenario slot, a header {slot,
+ *     CAGYM_CKPT_ROW_MAGIC, 0, 0} and the pool arrays cagym_fork copies except the raster (12 KB per slot, a pure function of the
+ *     rectangles: the load rasterizes again; the rectangles' prepared RVO form is copied).  STREAM (while streaming): generated,
+ *     n_failed, n_lapped, next_episode [N].  LOG (once initialised): every ring column, the running arrays, the slice counter and
+ *     head.  REPLAY (while armed): buf_key [Q], the counters and the harvest cursor, the buffer's generation, slot_key / slot_gen [S].
+ * cagym_checkpoint_sizes: sizes[CAGYM_CKPT_SECTIONS] of the handle as it is now; host only.
+ * cagym_checkpoint_save: writes the header into host_words before it returns and enqueues three copy launches into `blob` on `stream`
+ *   (rows of worlds, rows of slots, one flat copy of the other sections).  Nothing moves: a pending cagym_step_begin stays valid.
+ * cagym_checkpoint_load: validates the header on the host before anything is enqueued - magic, version, host_bytes, the section sizes
+ *   (against blob_bytes and against what this handle holds for the header's capacities), every config field except `device`, and the
+ *   header's members as the calls that set them do; any mismatch is CAGYM_E_INVALID and leaves the handle untouched.  Then the
+ *   handle's stream, log and replay state become the checkpoint's: streaming starts or ends, log and replay are initialised, a ring
+ *   whose capacity differs is allocated again (that synchronises the device, as a second cagym_episode_log_init does; nothing is
+ *   allocated where the capacities match), a log the checkpoint lacks is cleared as cagym_episode_log_restart(NULL, 1) clears it, and
+ *   the three copies and the raster launch are enqueued on `stream`.  A pending cagym_step_begin is void afterwards.  The caller's
+ *   output buffers are not part of a checkpoint.  The blob is trusted as cagym_restore trusts its own: a row without its magic, or
+ *   with an id out of range, is skipped on the device; the counters and keys are taken as they are.
+ *   After CAGYM_E_NOMEM / CAGYM_E_HIP from a load the handle's pool, log and replay contents are unspecified: load again or install a pool.
+ * Errors, in this order: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE for sizes / save before a pool is installed;
+ * CAGYM_E_UNSUPPORTED on an exploration stream and after cagym_ig_init (per-slot distance fields and planner workspaces are not
+ * carried); CAGYM_E_STATE with an initialised trajectory ring or initialised episode records; CAGYM_E_INVALID for a NULL sizes /
+ * host_words / blob, a blob that is not 16-byte aligned, buffers smaller than cagym_checkpoint_sizes says, and what load validates;
+ * CAGYM_E_DEVICE as every launching entry.  cagym_restore and cagym_fork keep their refusals. */
+#define CAGYM_CKPT_MAGIC 0x43474B31u     /* "CGK1" */
+#define CAGYM_CKPT_ROW_MAGIC 0x43475031u /* "CGP1": a pool row of the blob */
+#define CAGYM_CKPT_VERSION 1
+enum { CAGYM_CKPT_HOST = 0, CAGYM_CKPT_STATE = 1, CAGYM_CKPT_POOL = 2, CAGYM_CKPT_STREAM = 3, CAGYM_CKPT_LOG = 4, CAGYM_CKPT_REPLAY = 5,
+       CAGYM_CKPT_SECTIONS = 6 };
+int cagym_checkpoint_sizes(void* env, uint64_t* sizes);
+int cagym_checkpoint_save(void* env, void* host_words, uint64_t host_bytes, void* blob, uint64_t blob_bytes, void* stream);
+int cagym_checkpoint_load(void* env, const void* host_words, uint64_t host_bytes, const void* blob, uint64_t blob_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
