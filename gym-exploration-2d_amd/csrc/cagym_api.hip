@@ -34,6 +34,7 @@
 #include "cagym_replay.h"
 #include "cagym_terminal.h"
 #include "cagym_checkpoint.h"
+#include "cagym_layout.h"
 
 namespace {
 
@@ -88,7 +89,6 @@ struct Env {
     TrajRing traj{};                 // trajectory ring (cagym_trajectory_init allocates it: the running block once, the ring per n_slices)
     bool traj_ready = false;
     void* traj_ring = nullptr;       // the ring's one allocation (TrajRing's planes are carved from it)
-    size_t traj_ring_bytes = 0;
 };
 enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
@@ -287,7 +287,6 @@ inline int fill_empty_scan(Env* e, const CagymOut& o, hipStream_t st, int n_step
     return CAGYM_OK;
 }
 
-
 // the episode recorder's restart / clear launch (csrc/cagym_episode_records.h); a no-op for handles that never initialised it
 inline int eprec_restart(Env* e, const uint8_t* world_mask, bool clear_table, hipStream_t st) {
     if (!e->rec_ready) return CAGYM_OK;
@@ -313,9 +312,12 @@ inline int eplog_restart(Env* e, const uint8_t* world_mask, bool clear_rows, hip
 inline int traj_restart(Env* e, const uint8_t* world_mask, bool clear, hipStream_t st) {
     if (!e->traj_ready) return CAGYM_OK;
     const size_t NM = (size_t)e->cfg.n_worlds * e->cfg.max_agents;
-    if (clear) {  // every slice; head, desync and the workgroups' copies of head open the running block
-        HIPCHK(e, hipMemsetAsync(e->traj_ring, 0, e->traj_ring_bytes, st));
-        HIPCHK(e, hipMemsetAsync(e->traj.head, 0, 16 + 8 * (size_t)tcap_slice_wgs(e->cfg.n_worlds, e->cfg.max_agents), st));
+    if (clear) {  // every slice: `last` closes the ring; head, desync and the workgroups' copies of head open the running block (traj_*_members)
+        const TrajRing& R = e->traj;
+        const unsigned char* const ring_end = R.last + (size_t)e->cfg.n_worlds * R.L;
+        const unsigned char* const words_end = reinterpret_cast<const unsigned char*>(R.head_wg + tcap_slice_wgs(e->cfg.n_worlds, e->cfg.max_agents));
+        HIPCHK(e, hipMemsetAsync(e->traj_ring, 0, (size_t)(ring_end - static_cast<const unsigned char*>(e->traj_ring)), st));
+        HIPCHK(e, hipMemsetAsync(e->traj.head, 0, (size_t)(words_end - reinterpret_cast<const unsigned char*>(R.head)), st));
     }
     hipLaunchKernelGGL(k_trajectory_restart, dim3((unsigned)std::min<size_t>((NM + 255) / 256, 4096)), dim3(256), 0, st, e->D, e->traj, world_mask);
     HIPCHK(e, hipGetLastError());
@@ -329,22 +331,12 @@ inline int episodes_restart(Env* e, const uint8_t* world_mask, bool new_pool, hi
     if (int rc = eplog_restart(e, world_mask, false, st)) return rc;
     return traj_restart(e, world_mask, false, st);
 }
-// The one allocation of a ring (e->elog_ring, e->traj_ring: `name`), made again when its size changes: the new block first, and only
-// when there is one the old block goes, behind a device sync (no launch may still use it).  quiet: a refused allocation must not
-// surface as the next launch's error - the handle goes on as it was.
-inline int ring_alloc(Env* e, void** ring, const char* name, size_t bytes, bool quiet) {
-    unsigned char* b = nullptr;
-    if (int rc = dalloc(e, &b, bytes)) {
-        if (quiet) (void)hipGetLastError();
-        return rc;
-    }
-    if (*ring) {
-        HIPCHK(e, hipDeviceSynchronize());
-        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), *ring));
-        const hipError_t s = hipFree(*ring);
-        if (s != hipSuccess) return fail(e, CAGYM_E_HIP, std::string("hipFree(e->") + name + "): " + hipGetErrorString(s));
-    }
-    *ring = b;
+// every slot's raster from its rectangles (FIELD_RASTER); a handle without rectangles has none
+inline int rasterize_pool(Env* e, hipStream_t st) {
+    if (e->cfg.max_obstacles <= 0) return CAGYM_OK;
+    hipLaunchKernelGGL(k_rasterize, dim3((unsigned)e->cfg.n_scenarios), dim3(256), 0, st, e->sc_obst, e->D.sc_nobst, e->cfg.max_obstacles,
+                       const_cast<uint32_t*>(e->D.map_bits));
+    HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
 // the reset kernel as cagym_reset and cagym_step_autoreset_keep launch it
@@ -355,58 +347,75 @@ inline int launch_reset(Env* e, const uint8_t* world_mask, int advance_episode, 
     return CAGYM_OK;
 }
 
-// ---- the field tables of csrc/cagym_snapshot.h ----------------------------------------------------------------------------------------
-// A blob row: the header, then every per-world field alloc_state allocates except lp_vel (the split step's hand-over: restore and
-// fork void a pending begin), each at the next multiple of 16; after cagym_ig_init also the belief, its MI cache and the team
-// reward's accumulators.  fork_only: the table of cagym_fork's world -> world copy, which leaves dst its episode index and stat_*.
+// ---- the handle's per-world and per-slot arrays: ONE list each, walked by alloc_state and by the field tables of csrc/cagym_snapshot.h.
+// The order of a list is the order of its allocations and the order inside a blob row.  A new array is one new row here, and a
+// CAGYM_SNAP_VERSION / CAGYM_CKPT_VERSION bump if the row rides in a blob.
+enum {
+    FIELD_SNAP = 1,    // state: rides in a snapshot's blob row
+    FIELD_FORK = 2,    // cagym_fork copies it
+    FIELD_MAP = 4,     // pool: exists only on a handle with rectangles (max_obstacles > 0)
+    FIELD_RASTER = 8,  // pool: a pure function of the rectangles - a checkpoint's row leaves it out, the load rasterizes again
+    FIELD_SF = FIELD_SNAP | FIELD_FORK
+};
+// X(pointer, elements per world, flags), in terms of D (the handle's CagymDev) and M.  lp_vel is the split step's hand-over: restore
+// and fork void a pending begin.  cagym_fork leaves dst its episode index and stat_*.
+#define CAGYM_STATE_FIELDS(X) \
+    X(D.px, M, FIELD_SF) X(D.py, M, FIELD_SF) X(D.vx, M, FIELD_SF) X(D.vy, M, FIELD_SF) X(D.heading, M, FIELD_SF) X(D.heading_ego, M, FIELD_SF) \
+    X(D.dist_goal, M, FIELD_SF) X(D.time_rem, M, FIELD_SF) X(D.t, M, FIELD_SF) X(D.gx, M, FIELD_SF) X(D.gy, M, FIELD_SF) X(D.radius, M, FIELD_SF) \
+    X(D.pref, M, FIELD_SF) X(D.speed, M, FIELD_SF) X(D.dhead, M, FIELD_SF) X(D.aux0, M, FIELD_SF) X(D.aux1, M, FIELD_SF) X(D.coop, M, FIELD_SF) \
+    X(D.action, 2 * M, FIELD_SF) X(D.status, M, FIELD_SF) X(D.step_num, M, FIELD_SF) X(D.n_observed, M, FIELD_SF) X(D.lp_vel, M, 0) \
+    X(D.n_agents, 1, FIELD_SF) X(D.episode, 1, FIELD_SNAP) X(D.ep_len, 1, FIELD_SF) X(D.ep_return, 1, FIELD_SF) \
+    X(D.stat_return, 1, FIELD_SNAP) X(D.stat_episodes, 1, FIELD_SNAP) X(D.stat_steps, 1, FIELD_SNAP) X(D.stat_outcomes, 3, FIELD_SNAP)
+// the tail of a blob row after cagym_ig_init, which allocates them (there is no fork on such a handle); e is the Env
+#define CAGYM_IG_STATE_FIELDS(X) \
+    X(e->G.belief, IG_BEL * IG_BEL, FIELD_SNAP) X(e->G.mi, IG_BEL * IG_BEL, FIELD_SNAP) \
+    X(e->ig_ep.running, 1, FIELD_SNAP) X(e->ig_ep.sum, 1, FIELD_SNAP) X(e->ig_ep.last, 1, FIELD_SNAP) X(e->ig_ep.episodes, 1, FIELD_SNAP)
+// X(pointer, elements per scenario slot, flags), in terms of D, e, M and K = max_obstacles
+#define CAGYM_POOL_FIELDS(X) \
+    X(D.sc_agents6, 6 * M, FIELD_FORK) X(e->sc_heading_buf, M, FIELD_FORK) X(D.sc_coop, M, FIELD_FORK) X(D.sc_policy, M, FIELD_FORK) \
+    X(D.sc_dyn, M, FIELD_FORK) X(D.sc_nagents, 1, FIELD_FORK) X(D.sc_nobst, 1, FIELD_FORK) \
+    X(D.map_bits, CAGYM_MAPD * CAGYM_MAPW, FIELD_FORK | FIELD_MAP | FIELD_RASTER) \
+    X(e->sc_obst, 4 * K, FIELD_FORK | FIELD_MAP) X(e->sc_obst_prep, 4 * K, FIELD_FORK | FIELD_MAP)
+#define FIELD_COUNT(p, elems, flags) +1
+static_assert(0 CAGYM_STATE_FIELDS(FIELD_COUNT) CAGYM_IG_STATE_FIELDS(FIELD_COUNT) <= SNAP_MAX_FIELDS && 0 CAGYM_POOL_FIELDS(FIELD_COUNT) <= SNAP_MAX_FIELDS,
+              "SnapTable holds every field of a row");
+// alloc_state: one zero-filled array per row, `rows` worlds or slots long (the kernels read the pool through pointers to const)
+template <typename T>
+inline T*& field_mut(const T*& p) { return const_cast<T*&>(p); }
+template <typename T>
+inline T*& field_mut(T*& p) { return p; }
+#define FIELD_ALLOC(p, elems, flags) \
+    if (int rc = ((flags) & skip) ? CAGYM_OK : dalloc(e, &field_mut(p), rows * (elems))) return rc;
+
+// The table of k_snapshot_copy over the rows of a list that have the flag `need` (0: any) and none of `skip`: each field at the next
+// multiple of 16 behind the 16-byte header.  (SNAP_FORK / SNAP_POOL have no blob: the offsets only spread the lanes over the fields.)
+struct SnapBuilder {
+    SnapTable T;
+    int need, skip;
+    SnapBuilder(const Env* e, int mode, int need, int skip) : T{mode, 0, e->cfg.n_worlds, e->cfg.n_scenarios, e->D.episode, SNAP_HEADER_BYTES, {}}, need(need), skip(skip) {}
+    void operator()(const void* base, size_t bytes, int flags) {
+        if ((flags & need) != need || (flags & skip)) return;
+        T.f[T.n_fields++] = {reinterpret_cast<unsigned char*>(const_cast<void*>(base)), (uint32_t)bytes, (uint32_t)T.row_bytes};
+        T.row_bytes += layout_round16(bytes);
+    }
+};
+#define FIELD_ADD(p, elems, flags) add(p, (elems) * sizeof(*(p)), flags);
+// a snapshot's blob row (after cagym_ig_init with the IG tail), or with fork_only the table of cagym_fork's world -> world copy
 inline SnapTable snap_state_table(const Env* e, int mode, bool fork_only = false) {
     const CagymDev& D = e->D;
-    const uint32_t M = (uint32_t)e->cfg.max_agents;
-    SnapTable T{};
-    T.mode = mode; T.N = e->cfg.n_worlds; T.S = e->cfg.n_scenarios; T.episode = D.episode;
-    uint64_t off = SNAP_HEADER_BYTES;
-    auto add = [&](void* base, size_t bytes, bool in_fork = true) {
-        if (fork_only && !in_fork) return;  // (no blob in a fork: the fields it copies are packed without the gaps)
-        T.f[T.n_fields++] = {reinterpret_cast<unsigned char*>(base), (uint32_t)bytes, (uint32_t)off};
-        off += (bytes + 15) & ~(size_t)15;
-    };
-    double* const f64[] = {D.px, D.py, D.vx, D.vy, D.heading, D.heading_ego, D.dist_goal, D.time_rem, D.t,
-                           D.gx, D.gy, D.radius, D.pref, D.speed, D.dhead, D.aux0, D.aux1, D.coop};
-    for (double* p : f64) add(p, M * sizeof(double));
-    add(D.action, M * 2 * sizeof(float)); add(D.status, M * sizeof(uint32_t)); add(D.step_num, M * sizeof(int32_t));
-    add(D.n_observed, M * sizeof(int32_t));
-    add(D.n_agents, sizeof(int32_t)); add(D.episode, sizeof(int32_t), false); add(D.ep_len, sizeof(int32_t)); add(D.ep_return, sizeof(float));
-    add(D.stat_return, sizeof(float), false); add(D.stat_episodes, sizeof(int32_t), false); add(D.stat_steps, sizeof(int32_t), false);
-    add(D.stat_outcomes, 3 * sizeof(int32_t), false);
-    if (e->ig_ready) {
-        add(e->G.belief, (size_t)IG_BEL * IG_BEL * sizeof(double)); add(e->G.mi, (size_t)IG_BEL * IG_BEL * sizeof(double));
-        add(e->ig_ep.running, sizeof(double)); add(e->ig_ep.sum, sizeof(double)); add(e->ig_ep.last, sizeof(double));
-        add(e->ig_ep.episodes, sizeof(int32_t));
-    }
-    T.row_bytes = off;
-    return T;
+    const size_t M = (size_t)e->cfg.max_agents;
+    SnapBuilder add(e, mode, fork_only ? FIELD_FORK : FIELD_SNAP, 0);
+    CAGYM_STATE_FIELDS(FIELD_ADD)
+    if (e->ig_ready) { CAGYM_IG_STATE_FIELDS(FIELD_ADD) }
+    return add.T;
 }
-static_assert(18 + 4 + 8 + 6 <= SNAP_MAX_FIELDS, "SnapTable holds every field of a row");
-
-// the pool rows of one scenario slot (cagym_fork copies src's current slot over dst's)
-inline SnapTable snap_pool_table(const Env* e) {
+// the pool rows of one scenario slot: what cagym_fork copies (SNAP_POOL: src's current slot over dst's), or a checkpoint's row
+inline SnapTable snap_pool_table(const Env* e, int mode = SNAP_POOL) {
     const CagymDev& D = e->D;
     const size_t M = (size_t)e->cfg.max_agents, K = (size_t)e->cfg.max_obstacles;
-    SnapTable T{};
-    T.mode = SNAP_POOL; T.N = e->cfg.n_worlds; T.S = e->cfg.n_scenarios; T.episode = D.episode;
-    uint64_t off = SNAP_HEADER_BYTES;  // no blob here: the offsets only spread the lanes over the fields
-    auto add = [&](const void* base, size_t bytes) {
-        T.f[T.n_fields++] = {reinterpret_cast<unsigned char*>(const_cast<void*>(base)), (uint32_t)bytes, (uint32_t)off};
-        off += (bytes + 15) & ~(size_t)15;
-    };
-    add(D.sc_agents6, M * 6 * sizeof(double)); add(e->sc_heading_buf, M * sizeof(double)); add(D.sc_coop, M * sizeof(double));
-    add(D.sc_policy, M * sizeof(int32_t)); add(D.sc_dyn, M * sizeof(int32_t)); add(D.sc_nagents, sizeof(int32_t)); add(D.sc_nobst, sizeof(int32_t));
-    if (has_map(e)) {
-        add(D.map_bits, (size_t)CAGYM_MAPD * CAGYM_MAPW * sizeof(uint32_t)); add(e->sc_obst, K * 4 * sizeof(double));
-        add(e->sc_obst_prep, K * 4 * sizeof(float4));
-    }
-    T.row_bytes = off;
-    return T;
+    SnapBuilder add(e, mode, mode == SNAP_POOL ? FIELD_FORK : 0, (has_map(e) ? 0 : FIELD_MAP) | (mode == SNAP_POOL ? 0 : FIELD_RASTER));
+    CAGYM_POOL_FIELDS(FIELD_ADD)
+    return add.T;
 }
 
 inline cagym_snapshot_layout snap_layout(const Env* e) {
@@ -425,58 +434,90 @@ inline int snap_launch(Env* e, const SnapTable& T, const int32_t* ids, const int
     return CAGYM_OK;
 }
 
-// ---- the allocations of the stream, the episode log and the replay buffer: their *_init calls and cagym_checkpoint_load ---------------
-// the stream's device words, once per handle: {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
+// ---- the blocks of arrays that share one allocation (csrc/cagym_layout.h) ----------------------------------------------------------
+// Each block's members are listed ONCE, with their element counts.  The listing gives the allocation's size, the members' pointers
+// and - listing order is blob order - the entries of a checkpoint's flat sections (ckpt_flat_table).  A new member is one new v(...),
+// and a CAGYM_CKPT_VERSION bump unless it is LAYOUT_SCRATCH or its block is in no checkpoint.
+// the stream's words: `generated` with n_failed and n_lapped behind it is ONE 16-byte member (one memset, one field of a checkpoint)
+template <class V> constexpr void stream_members(StreamDev& W, size_t N, V& v) { v(W.generated, 2); v(W.next_episode, N); }
+// the exploration stream's field refresh: `fields_built` with n_list behind it (one memset), then field_next and the slot list
+template <class V> constexpr void explore_members(ExploreDev& X, size_t N, size_t S, V& v) { v(X.fields_built, 2); v(X.field_next, N); v(X.list, S - N); }
+// the episode log's ring of L rows, and its running block (pos and cnt live between the launches of one update)
+template <class V> constexpr void eplog_ring_members(EpLog& G, size_t L, size_t M, V& v) {
+    v(G.slice, L); v(G.ret, L); v(G.t, L * M); v(G.extra_t, L * M); v(G.key, L); v(G.world, L); v(G.episode, L); v(G.steps, L);
+    v(G.outcome, L); v(G.n_agents, L); v(G.n_obst, L); v(G.flags, L * M);
+}
+template <class V> constexpr void eplog_run_members(EpLog& G, size_t N, size_t M, V& v) {
+    v(G.run.t_run, N * M); v(G.run.ret_run, N); v(G.run.steps_run, N); v(G.run.atgoal_run, N); v(G.run.cursor, N); v(G.run.desync, 1);
+    v(G.seq, 1); v(G.head, 1); v(G.pos, N, LAYOUT_SCRATCH); v(G.cnt, N, LAYOUT_SCRATCH);
+}
+// the replay's buffer of Q keys, and its words and per-slot tables
+template <class V> constexpr void replay_ring_members(ReplayDev& R, size_t Q, V& v) { v(R.buf_key, Q); }
+template <class V> constexpr void replay_table_members(ReplayDev& R, size_t S, V& v) { v(R.words, RPW_WORDS); v(R.buf_gen, 1); v(R.slot_key, S); v(R.slot_gen, S); }
+// the trajectory ring's running block and its ring of L slices (in no checkpoint).  traj_restart clears head, desync and head_wg with
+// one memset - they stay first and adjacent - and the ring up to the end of `last`, which stays its last member
+template <class V> constexpr void traj_run_members(TrajRing& R, size_t NM, size_t n_wg, V& v) { v(R.head, 1); v(R.desync, 1); v(R.head_wg, n_wg); v(R.t_prev, NM); v(R.seen, NM); }
+template <class V> constexpr void traj_ring_members(TrajRing& R, size_t N, size_t NM, size_t L, V& v) {
+    v(R.rows, TRAJ_COLS * NM * L); v(R.episode, N * L); v(R.moved, NM * L); v(R.last, N * L);
+}
+
+// members: a block's listing with its sizes bound, [&](auto& v) { ..._members(G, ..., v); }
+template <class F> inline size_t block_bytes(F members) {
+    LayoutBytes b;
+    members(b);
+    return b.bytes;
+}
+// a zero-filled allocation of its own for the block, once per handle; the members point into it afterwards
+template <class F> inline int block_alloc(Env* e, F members) {
+    LayoutCarve carve{nullptr};
+    if (int rc = dalloc(e, &carve.base, block_bytes(members))) return rc;
+    members(carve);
+    return CAGYM_OK;
+}
+// The one allocation of a ring's block (e->elog_ring, e->replay_ring, e->traj_ring: `name`), made again when its size changes: the
+// new block first, and only when there is one the old block goes, behind a device sync (no launch may still use it).  quiet: a
+// refused allocation must not surface as the next launch's error - the handle goes on as it was.
+template <class F> inline int ring_alloc(Env* e, void** ring, const char* name, bool quiet, F members) {
+    LayoutCarve carve{nullptr};
+    if (int rc = dalloc(e, &carve.base, block_bytes(members))) {
+        if (quiet) (void)hipGetLastError();
+        return rc;
+    }
+    if (*ring) {
+        HIPCHK(e, hipDeviceSynchronize());
+        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), *ring));
+        const hipError_t s = hipFree(*ring);
+        if (s != hipSuccess) return fail(e, CAGYM_E_HIP, std::string("hipFree(e->") + name + "): " + hipGetErrorString(s));
+    }
+    *ring = carve.base;
+    members(carve);
+    return CAGYM_OK;
+}
+
+// the stream's device words, once per handle
 inline int stream_alloc(Env* e) {
     const int N = e->cfg.n_worlds;
-    if (!e->stream.next_episode) {
-        unsigned char* buf = nullptr;
-        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
-        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
-        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
-        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
-        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
+    StreamDev& W = e->stream;
+    if (!W.next_episode) {
+        if (int rc = block_alloc(e, [&](auto& v) { stream_members(W, N, v); })) return rc;
+        W.n_failed = reinterpret_cast<int32_t*>(W.generated + 1); W.n_lapped = W.n_failed + 1;
     }
-    e->stream.episode = e->D.episode;
-    e->stream.map_bits = const_cast<uint32_t*>(e->D.map_bits);
-    e->stream.N = N;
-    e->stream.depth = e->cfg.n_scenarios / N;
+    W.episode = e->D.episode;
+    W.map_bits = const_cast<uint32_t*>(e->D.map_bits);
+    W.N = N;
+    W.depth = e->cfg.n_scenarios / N;
     return CAGYM_OK;
 }
 // the log's running block (once per handle) and its ring (once per capacity); e->elog is complete afterwards
 inline int eplog_alloc(Env* e, int capacity) {
     const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
     EpLog G = e->elog;
-    if (!G.run.t_run) {  // the running block: once per handle
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, 8 * (N * M + 2 * N + 2) + 4 * (4 * N + 2))) return rc;
-        G.run.t_run = reinterpret_cast<double*>(b); b += 8 * N * M;
-        G.run.ret_run = reinterpret_cast<double*>(b); b += 8 * N;
-        G.pos = reinterpret_cast<unsigned long long*>(b); b += 8 * N;
-        G.seq = reinterpret_cast<unsigned long long*>(b); b += 8;
-        G.head = reinterpret_cast<unsigned long long*>(b); b += 8;
-        G.run.steps_run = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.run.atgoal_run = reinterpret_cast<uint32_t*>(b); b += 4 * N;
-        G.run.cursor = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.cnt = reinterpret_cast<int32_t*>(b); b += 4 * N;
-        G.run.desync = reinterpret_cast<int32_t*>(b);
+    if (!G.run.t_run) {
+        if (int rc = block_alloc(e, [&](auto& v) { eplog_run_members(G, N, M, v); })) return rc;
         e->elog = G;  // kept whatever becomes of the ring's allocation
     }
-    if (!e->elog_ring || G.capacity != capacity) {  // the ring: once per capacity (8-byte columns first, then 4-byte ones, then bytes)
-        if (int rc = ring_alloc(e, &e->elog_ring, "elog_ring", L * (8 * (2 + 2 * M) + 4 * 7 + M), false)) return rc;
-        unsigned char* b = static_cast<unsigned char*>(e->elog_ring);
-        G.slice = reinterpret_cast<long long*>(b); b += 8 * L;
-        G.ret = reinterpret_cast<double*>(b); b += 8 * L;
-        G.t = reinterpret_cast<double*>(b); b += 8 * L * M;
-        G.extra_t = reinterpret_cast<double*>(b); b += 8 * L * M;
-        G.key = reinterpret_cast<uint32_t*>(b); b += 4 * L;
-        G.world = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.episode = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.steps = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.outcome = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.n_agents = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.n_obst = reinterpret_cast<int32_t*>(b); b += 4 * L;
-        G.flags = b;
+    if (!e->elog_ring || G.capacity != capacity) {
+        if (int rc = ring_alloc(e, &e->elog_ring, "elog_ring", false, [&](auto& v) { eplog_ring_members(G, L, M, v); })) return rc;
         G.capacity = capacity;
     }
     e->elog = G;
@@ -486,18 +527,12 @@ inline int eplog_alloc(Env* e, int capacity) {
 inline int replay_alloc(Env* e, int capacity) {
     const size_t S = (size_t)e->cfg.n_scenarios;
     ReplayDev R = e->replay;
-    if (!R.words) {  // once per handle: the words (u64), buf_gen and a pad word, then the two per-slot tables
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, 8 * (size_t)RPW_WORDS + 8 + 8 * S)) return rc;
-        R.words = reinterpret_cast<unsigned long long*>(b); b += 8 * (size_t)RPW_WORDS;
-        R.buf_gen = reinterpret_cast<uint32_t*>(b); b += 8;
-        R.slot_key = reinterpret_cast<uint32_t*>(b); b += 4 * S;
-        R.slot_gen = reinterpret_cast<uint32_t*>(b);
+    if (!R.words) {
+        if (int rc = block_alloc(e, [&](auto& v) { replay_table_members(R, S, v); })) return rc;
         e->replay = R;  // kept whatever becomes of the buffer's allocation
     }
     if (!e->replay_ring || R.Q != capacity) {
-        if (int rc = ring_alloc(e, &e->replay_ring, "replay_ring", 4 * (size_t)capacity, false)) return rc;
-        R.buf_key = static_cast<uint32_t*>(e->replay_ring);
+        if (int rc = ring_alloc(e, &e->replay_ring, "replay_ring", false, [&](auto& v) { replay_ring_members(R, (size_t)capacity, v); })) return rc;
         R.Q = capacity;
     }
     e->replay = R;
@@ -543,64 +578,39 @@ inline int ckpt_refuse(Env* e, const char* what) {
     return CAGYM_OK;
 }
 
-// the pool rows of a checkpoint: snap_pool_table's fields without the rasters
-inline SnapTable ckpt_pool_table(const Env* e, int mode) {
-    const SnapTable P = snap_pool_table(e);
-    SnapTable T = P;
-    T.mode = mode;
-    T.n_fields = 0;
-    uint64_t off = SNAP_HEADER_BYTES;
-    for (int k = 0; k < P.n_fields; k++) {
-        if (P.f[k].base == reinterpret_cast<const unsigned char*>(e->D.map_bits)) continue;
-        T.f[T.n_fields++] = {P.f[k].base, P.f[k].bytes, (uint32_t)off};
-        off += ((uint64_t)P.f[k].bytes + 15) & ~(uint64_t)15;
-    }
-    T.row_bytes = off;
-    return T;
-}
-
-// The flat sections of a handle whose stream / log / replay state is (streaming, log capacity or 0, replay capacity or 0): sizes
-// alone while the arrays are not allocated (with_pointers = false), else the table of k_checkpoint_flat as well.
+// The flat sections of a handle whose stream / log / replay state is (streaming, log capacity or 0, replay capacity or 0): the
+// listings of their blocks, ring before running block, in blob order.  with_pointers = false: sizes alone, while the arrays are not
+// allocated (or not at these capacities) - the listings applied to empty structs; else the table of k_checkpoint_flat as well.
 inline CkptTable ckpt_flat_table(const Env* e, bool streaming, int log_capacity, int replay_capacity, uint64_t* sizes, bool with_pointers) {
     const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, S = e->cfg.n_scenarios;
     CkptTable T{};
     uint64_t off = 0;
-    auto add = [&](const void* base, size_t bytes) {
-        T.f[T.n_fields++] = {with_pointers ? reinterpret_cast<unsigned char*>(const_cast<void*>(base)) : nullptr, (uint64_t)bytes, off};
-        off += ((uint64_t)bytes + 15) & ~(uint64_t)15;
-    };
-    if (streaming) {
-        const StreamDev& W = e->stream;
-        add(W.generated, 16);  // generated, n_failed, n_lapped: one allocation (stream_alloc)
-        add(W.next_episode, 4 * N);
-    }
+    LayoutCkpt<CkptTable> v{T, off};
+    StreamDev W = with_pointers ? e->stream : StreamDev{};
+    EpLog G = with_pointers ? e->elog : EpLog{};
+    ReplayDev R = with_pointers ? e->replay : ReplayDev{};
+    if (streaming) stream_members(W, N, v);
     sizes[CAGYM_CKPT_STREAM] = off;
-    if (log_capacity > 0) {
-        const EpLog& G = e->elog;
-        const size_t L = (size_t)log_capacity;
-        add(G.slice, 8 * L); add(G.ret, 8 * L); add(G.t, 8 * L * M); add(G.extra_t, 8 * L * M);
-        add(G.key, 4 * L); add(G.world, 4 * L); add(G.episode, 4 * L); add(G.steps, 4 * L); add(G.outcome, 4 * L); add(G.n_agents, 4 * L);
-        add(G.n_obst, 4 * L); add(G.flags, L * M);
-        add(G.run.t_run, 8 * N * M); add(G.run.ret_run, 8 * N); add(G.run.steps_run, 4 * N); add(G.run.atgoal_run, 4 * N); add(G.run.cursor, 4 * N);
-        add(G.run.desync, 4); add(G.seq, 8); add(G.head, 8);
-    }
+    if (log_capacity > 0) { eplog_ring_members(G, (size_t)log_capacity, M, v); eplog_run_members(G, N, M, v); }
     sizes[CAGYM_CKPT_LOG] = off - sizes[CAGYM_CKPT_STREAM];
-    if (replay_capacity > 0) {
-        const ReplayDev& R = e->replay;
-        add(R.buf_key, 4 * (size_t)replay_capacity); add(R.words, 8 * (size_t)RPW_WORDS); add(R.buf_gen, 4); add(R.slot_key, 4 * S);
-        add(R.slot_gen, 4 * S);
-    }
+    if (replay_capacity > 0) { replay_ring_members(R, (size_t)replay_capacity, v); replay_table_members(R, S, v); }
     sizes[CAGYM_CKPT_REPLAY] = off - sizes[CAGYM_CKPT_STREAM] - sizes[CAGYM_CKPT_LOG];
     T.bytes = off;
     return T;
 }
-static_assert(2 + 20 + 5 <= CKPT_MAX_FIELDS, "CkptTable holds every flat field");
+constexpr int ckpt_flat_fields() {
+    LayoutCount n;
+    StreamDev W{}; EpLog G{}; ReplayDev R{};
+    stream_members(W, 1, n); eplog_ring_members(G, 1, 1, n); eplog_run_members(G, 1, 1, n); replay_ring_members(R, 1, n); replay_table_members(R, 1, n);
+    return n.n;
+}
+static_assert(ckpt_flat_fields() <= CKPT_MAX_FIELDS, "CkptTable holds every flat field");
 
 // every section size of a handle in the given stream / log / replay state
 inline void ckpt_sizes(const Env* e, bool streaming, int log_capacity, int replay_capacity, uint64_t* sizes) {
     sizes[CAGYM_CKPT_HOST] = sizeof(CkptHost);
     sizes[CAGYM_CKPT_STATE] = (uint64_t)e->cfg.n_worlds * snap_state_table(e, SNAP_GATHER).row_bytes;
-    sizes[CAGYM_CKPT_POOL] = (uint64_t)e->cfg.n_scenarios * ckpt_pool_table(e, SNAP_SLOT_GATHER).row_bytes;
+    sizes[CAGYM_CKPT_POOL] = (uint64_t)e->cfg.n_scenarios * snap_pool_table(e, SNAP_SLOT_GATHER).row_bytes;
     (void)ckpt_flat_table(e, streaming, log_capacity, replay_capacity, sizes, false);
 }
 inline void ckpt_sizes(const Env* e, uint64_t* sizes) {
@@ -618,7 +628,7 @@ inline int ckpt_copy(Env* e, bool to_blob, unsigned char* blob, bool streaming, 
     ckpt_sizes(e, streaming, log_capacity, replay_capacity, sizes);
     if (int rc = snap_launch(e, snap_state_table(e, to_blob ? SNAP_GATHER : SNAP_SCATTER), nullptr, nullptr, blob, e->cfg.n_worlds, st)) return rc;
     blob += sizes[CAGYM_CKPT_STATE];
-    if (int rc = snap_launch(e, ckpt_pool_table(e, to_blob ? SNAP_SLOT_GATHER : SNAP_SLOT_SCATTER), nullptr, nullptr, blob, e->cfg.n_scenarios, st))
+    if (int rc = snap_launch(e, snap_pool_table(e, to_blob ? SNAP_SLOT_GATHER : SNAP_SLOT_SCATTER), nullptr, nullptr, blob, e->cfg.n_scenarios, st))
         return rc;
     blob += sizes[CAGYM_CKPT_POOL];
     CkptTable T = ckpt_flat_table(e, streaming, log_capacity, replay_capacity, sizes, true);
@@ -663,42 +673,23 @@ static int alloc_state(Env* e) {
     const cagym_config* cfg = &e->cfg;
     CagymDev& D = e->D;
     memset(&D, 0, sizeof(D));
-    const size_t N = cfg->n_worlds, M = cfg->max_agents, S = cfg->n_scenarios, NM = N * M, SM = S * M;
+    const size_t N = cfg->n_worlds, M = cfg->max_agents, S = cfg->n_scenarios, K = cfg->max_obstacles;
     D.N = (int)N; D.M = (int)M; D.S = (int)S; D.Kobs = cfg->max_obstacles;
     D.go_mode = cfg->game_over_mode; D.collide_static = cfg->collide_with_static; D.laserscan = cfg->laserscan;
     D.dt = cfg->dt;
     D.inv_dt = 1.0 / cfg->dt;
     D.maxnb = cfg->rvo_max_neighbors > 0 ? cfg->rvo_max_neighbors : (int)M;  // RVOPolicy.py:15: Config.MAX_NUM_AGENTS_IN_ENVIRONMENT
     if (D.maxnb > (int)M - 1) D.maxnb = (int)M - 1;                            // there are at most M - 1 other agents
-    double* d6 = nullptr; double* dcoop = nullptr;
-    int32_t *dpol = nullptr, *ddyn = nullptr, *dna = nullptr, *dno = nullptr;
-    uint32_t* dmap = nullptr;
-#define A(call) if (int rc = (call)) return rc;
-    A(dalloc(e, &d6, SM * 6)); A(dalloc(e, &e->sc_heading_buf, SM)); A(dalloc(e, &dcoop, SM));
-    A(dalloc(e, &dpol, SM)); A(dalloc(e, &ddyn, SM)); A(dalloc(e, &dna, S)); A(dalloc(e, &dno, S));
-    if (cfg->max_obstacles > 0) {
-        A(dalloc(e, &dmap, S * CAGYM_MAPD * CAGYM_MAPW));
-        A(dalloc(e, &e->sc_obst, S * (size_t)cfg->max_obstacles * 4));
-        A(dalloc(e, &e->sc_obst_prep, S * (size_t)cfg->max_obstacles * 4));
-    }
-    D.sc_agents6 = d6; D.sc_heading0 = nullptr; D.sc_coop = dcoop; D.sc_policy = dpol; D.sc_dyn = ddyn;
-    D.sc_nagents = dna; D.sc_nobst = dno; D.map_bits = dmap; D.sc_obst = e->sc_obst; D.sc_obst_prep = e->sc_obst_prep;
-    A(dalloc(e, &D.px, NM)); A(dalloc(e, &D.py, NM)); A(dalloc(e, &D.vx, NM)); A(dalloc(e, &D.vy, NM));
-    A(dalloc(e, &D.heading, NM)); A(dalloc(e, &D.heading_ego, NM)); A(dalloc(e, &D.dist_goal, NM));
-    A(dalloc(e, &D.time_rem, NM)); A(dalloc(e, &D.t, NM)); A(dalloc(e, &D.gx, NM)); A(dalloc(e, &D.gy, NM));
-    A(dalloc(e, &D.radius, NM)); A(dalloc(e, &D.pref, NM)); A(dalloc(e, &D.speed, NM)); A(dalloc(e, &D.dhead, NM));
-    A(dalloc(e, &D.aux0, NM)); A(dalloc(e, &D.aux1, NM)); A(dalloc(e, &D.coop, NM));
-    A(dalloc(e, &D.action, NM * 2)); A(dalloc(e, &D.status, NM)); A(dalloc(e, &D.step_num, NM));
-    A(dalloc(e, &D.n_observed, NM));
-    A(dalloc(e, &D.lp_vel, NM));
-    A(dalloc(e, &D.n_agents, N)); A(dalloc(e, &D.episode, N)); A(dalloc(e, &D.ep_len, N));
-    A(dalloc(e, &D.ep_return, N)); A(dalloc(e, &D.stat_return, N)); A(dalloc(e, &D.stat_episodes, N));
-    A(dalloc(e, &D.stat_steps, N)); A(dalloc(e, &D.stat_outcomes, N * 3));
-    A(dalloc(e, &e->ga3c_ctr, 4));  // at creation: cagym_ga3c_act may run inside a stream capture (no allocation there)
-    A(dalloc(e, &e->ga3c_packed, GA16_PACKED_BYTES));
-    A(dalloc(e, &e->go_scratch, N));  // at creation, as the GA3C words: cagym_step_autoreset_keep may run inside a stream capture
-#undef A
-    return CAGYM_OK;
+    // the pool first, then the state: one allocation per row of the lists, in their order (sc_heading0 stays null: no headings yet)
+    size_t rows = S;
+    int skip = K > 0 ? 0 : FIELD_MAP;
+    CAGYM_POOL_FIELDS(FIELD_ALLOC)
+    D.sc_obst = e->sc_obst; D.sc_obst_prep = e->sc_obst_prep;
+    rows = N; skip = 0;
+    CAGYM_STATE_FIELDS(FIELD_ALLOC)
+    if (int rc = dalloc(e, &e->ga3c_ctr, 4)) return rc;  // at creation: cagym_ga3c_act may run inside a stream capture (no allocation there)
+    if (int rc = dalloc(e, &e->ga3c_packed, GA16_PACKED_BYTES)) return rc;
+    return dalloc(e, &e->go_scratch, N);  // at creation, as the GA3C words: cagym_step_autoreset_keep may run inside a stream capture
 }
 
 // the kernels' status word: pinned host memory mapped into the device's address space (written only when a bounded wait expires)
@@ -920,10 +911,8 @@ int cagym_set_scenarios(void* env, const double* agents6, const double* heading0
             }
             HIPCHK(e, hipMemcpyAsync(e->sc_obst_prep, prep.data(), prep.size() * sizeof(float), hipMemcpyHostToDevice, st));
         }
-        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)S), dim3(256), 0, st, e->sc_obst, D.sc_nobst, e->cfg.max_obstacles,
-                           const_cast<uint32_t*>(D.map_bits));
-        HIPCHK(e, hipGetLastError());
     }
+    if (int rc = rasterize_pool(e, st)) return rc;
     // host staging vectors die at return: the copies above must have consumed them
     HIPCHK(e, hipStreamSynchronize(st));
     // a new pool restarts the episode numbering
@@ -981,11 +970,7 @@ int cagym_generate_scenarios(void* env, const cagym_gen_params* params, int32_t*
     e->n_ig = (P.ego_policy == CAGYM_POL_IGMCTS || P.policy_a == CAGYM_POL_IGMCTS || P.policy_b == CAGYM_POL_IGMCTS) ? N_IG_RANDOM : 0;
     e->obst_rvo = 0;  // the generator draws free-space worlds
     e->D.ko = 0;
-    if (e->cfg.max_obstacles > 0) {  // free space: empty rasters
-        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)G.S), dim3(256), 0, st, e->sc_obst, D.sc_nobst, e->cfg.max_obstacles,
-                           const_cast<uint32_t*>(D.map_bits));
-        HIPCHK(e, hipGetLastError());
-    }
+    if (int rc = rasterize_pool(e, st)) return rc;  // free space: empty rasters
     if (n_failed_host) {
         HIPCHK(e, hipMemcpyAsync(n_failed_host, d_failed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
@@ -1075,11 +1060,7 @@ static int gen2_fill(Env* e, const cagym_gen2_params& P, const Gen2Flags& F, int
     else
         hipLaunchKernelGGL(k_generate_reference_scenarios, dim3((G.G.S + 63) / 64), dim3(64), 0, st, G, P, d_failed);
     HIPCHK(e, hipGetLastError());
-    if (K > 0) {
-        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)G.G.S), dim3(256), 0, st, e->sc_obst, D.sc_nobst, K,
-                           const_cast<uint32_t*>(D.map_bits));
-        HIPCHK(e, hipGetLastError());
-    }
+    if (int rc = rasterize_pool(e, st)) return rc;
     HIPCHK(e, hipMemsetAsync(D.episode, 0, e->cfg.n_worlds * sizeof(int32_t), st));  // a new pool restarts the episode numbering
     if (n_failed_host) {
         HIPCHK(e, hipMemcpyAsync(n_failed_host, d_failed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1341,28 +1322,13 @@ int cagym_stream_exploration_scenarios(void* env, const cagym_explore_params* pa
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ON_DEVICE(e);
     const int N = e->cfg.n_worlds, S = e->cfg.n_scenarios;
-    if (!e->stream.next_episode) {  // as cagym_stream_scenarios: {generated u64, n_failed i32, n_lapped i32} then next_episode [N]
-        unsigned char* buf = nullptr;
-        if (int rc = dalloc(e, &buf, 16 + (size_t)N * sizeof(int32_t))) return rc;
-        e->stream.generated = reinterpret_cast<unsigned long long*>(buf);
-        e->stream.n_failed = reinterpret_cast<int32_t*>(buf + 8);
-        e->stream.n_lapped = reinterpret_cast<int32_t*>(buf + 12);
-        e->stream.next_episode = reinterpret_cast<int32_t*>(buf + 16);
-    }
-    if (!e->explore.field_next) {  // {fields_built u64, n_list i32, pad} then field_next [N] then list [S - N]
-        unsigned char* buf = nullptr;
-        if (int rc = dalloc(e, &buf, 16 + ((size_t)N + (size_t)(S - N)) * sizeof(int32_t))) return rc;
-        e->explore.fields_built = reinterpret_cast<unsigned long long*>(buf);
-        e->explore.n_list = reinterpret_cast<int32_t*>(buf + 8);
-        e->explore.field_next = reinterpret_cast<int32_t*>(buf + 16);
-        e->explore.list = e->explore.field_next + N;
-        e->explore.cap = S - N;
+    if (int rc = stream_alloc(e)) return rc;  // as cagym_stream_scenarios
+    ExploreDev& X = e->explore;
+    if (!X.field_next) {
+        if (int rc = block_alloc(e, [&](auto& v) { explore_members(X, (size_t)N, (size_t)S, v); })) return rc;
+        X.n_list = reinterpret_cast<int32_t*>(X.fields_built + 1); X.cap = S - N;
     }
     StreamDev& T = e->stream;
-    T.episode = e->D.episode;
-    T.map_bits = const_cast<uint32_t*>(e->D.map_bits);
-    T.N = N;
-    T.depth = S / N;
     HIPCHK(e, hipMemsetAsync(T.generated, 0, 16, st));
     HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.generated), S, 1, st));
     HIPCHK(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.next_episode), T.depth, (size_t)N, st));
@@ -1489,26 +1455,14 @@ int cagym_trajectory_init(void* env, int n_slices, void* stream) {
     ON_DEVICE(e);
     const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, NM = N * M, L = (size_t)n_slices, n_wg = tcap_slice_wgs((int)N, (int)M);
     TrajRing R = e->traj;
-    if (!R.t_prev) {  // the running block: once per handle (8-byte words first)
-        unsigned char* b = nullptr;
-        if (int rc = dalloc(e, &b, 16 + 8 * n_wg + 8 * NM + 4 * NM)) return rc;
-        R.head = reinterpret_cast<unsigned long long*>(b); b += 8;
-        R.desync = reinterpret_cast<int32_t*>(b); b += 8;
-        R.head_wg = reinterpret_cast<unsigned long long*>(b); b += 8 * n_wg;
-        R.t_prev = reinterpret_cast<double*>(b); b += 8 * NM;
-        R.seen = reinterpret_cast<int32_t*>(b);
+    if (!R.t_prev) {  // the running block: once per handle
+        if (int rc = block_alloc(e, [&](auto& v) { traj_run_members(R, NM, n_wg, v); })) return rc;
         e->traj = R;  // kept whatever becomes of the ring's allocation
     }
-    if (!e->traj_ring || R.L != n_slices) {  // the ring: once per n_slices (8-byte plane first, then the 4-byte one, then bytes)
-        const size_t per_slice = 8 * TRAJ_COLS * NM + 4 * N + NM + N;
+    if (!e->traj_ring || R.L != n_slices) {  // the ring: once per n_slices
+        const size_t per_slice = block_bytes([&](auto& v) { traj_ring_members(R, N, NM, 1, v); });
         if (L > ((size_t)1 << 46) / per_slice) return fail(e, CAGYM_E_NOMEM, "cagym_trajectory_init: the ring does not fit");
-        if (int rc = ring_alloc(e, &e->traj_ring, "traj_ring", L * per_slice, true)) return rc;
-        unsigned char* b = static_cast<unsigned char*>(e->traj_ring);
-        e->traj_ring_bytes = L * per_slice;
-        R.rows = reinterpret_cast<double*>(b); b += 8 * TRAJ_COLS * NM * L;
-        R.episode = reinterpret_cast<int32_t*>(b); b += 4 * N * L;
-        R.moved = b; b += NM * L;
-        R.last = b;
+        if (int rc = ring_alloc(e, &e->traj_ring, "traj_ring", true, [&](auto& v) { traj_ring_members(R, N, NM, L, v); })) return rc;
         R.L = n_slices;
     }
     e->traj = R;
@@ -2391,11 +2345,7 @@ int cagym_checkpoint_load(void* env, const void* host_words, uint64_t host_bytes
     }
     if (int rc = ckpt_copy(e, false, reinterpret_cast<unsigned char*>(const_cast<void*>(blob)), H.streaming != 0, H.log_capacity, H.replay_capacity, st))
         return rc;
-    if (K > 0) {  // the rasters: a pure function of the rectangles the pool rows brought
-        hipLaunchKernelGGL(k_rasterize, dim3((unsigned)c.n_scenarios), dim3(256), 0, st, e->sc_obst, e->D.sc_nobst, K, const_cast<uint32_t*>(e->D.map_bits));
-        HIPCHK(e, hipGetLastError());
-    }
-    return CAGYM_OK;
+    return rasterize_pool(e, st);  // a pure function of the rectangles the pool rows brought
 }
 
 }  // extern "C"
