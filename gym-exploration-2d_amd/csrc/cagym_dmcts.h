@@ -224,8 +224,7 @@ __device__ inline void dm_visible_wave(const uint32_t* d2, double px, double py,
     ye = min(ye, IG_BEL);
     const int w = xe - xs, h = ye - ys;
     const int total = (w > 0 && h > 0) ? w * h : 0;
-    const bool fast = cone.fast;  // the cone test by products where the margin allows (see ig_visible_block); the tangents: once per kernel
-    const double t_in = cone.t_in, t_out = cone.t_out;
+    // the cone test by products where the margin allows (ig_in_cone); the tangents: once per kernel
     const double r2_in = range * range * (1.0 - 1e-12), r2_out = range * range * (1.0 + 1e-12);
     constexpr int CAP = IG_BEL * IG_BEL / 4;  // list entries of a wave; a larger window is worked off in slices of CAP cells
     for (int base = 0; base < total; base += CAP) {
@@ -241,14 +240,7 @@ __device__ inline void dm_visible_wave(const uint32_t* d2, double px, double py,
                 double cxp = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cyp = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
                 double r0, r1;
                 mat2vec(c, s, cxp - px, cyp - py, r0, r1);
-                const double rn2 = r0 * r0 + r1 * r1, a1 = fabs(r1);
-                if (fast && (rn2 > r2_out || !(r0 > 0.0) || a1 > r0 * t_out)) inside = false;
-                else if (fast && rn2 < r2_in && a1 < r0 * t_in) inside = true;
-                else {
-                    double dphi = atan2(r1, r0);
-                    double rn = sqrt(rn2);
-                    inside = rn < range && fabs(dphi) < fov / 2;
-                }
+                inside = ig_in_cone(r0, r1, cone, r2_in, r2_out, fov, range);
             }
             const unsigned long long m = __ballot(inside);
             if (inside) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)((i << 8) | j);  // i, j < 60

@@ -124,6 +124,22 @@ __device__ __forceinline__ IgCone ig_cone(double fov) {
     return c;
 }
 
+// The cone test `rn < range and |atan2(r1, r0)| < fov / 2` (targetMap.py:76-79) of a window cell at r = (r0, r1) in the robot's
+// frame costs an fp64 atan2 and a square root, and two cells in three fail it.  A cell that is inside or outside by a margin far
+// above the rounding of either side is decided by products alone (|r1| against r0 tan(fov/2 -+ 1e-9), rn^2 against range^2
+// (1 -+ 1e-12), r2_in / r2_out); only a cell within those margins evaluates the reference's own expressions.  Same set, bit for bit.
+// r0 = +-0 is such a cell when r1 = 0 too: a robot on a belief-cell centre looking at its own cell.  The reference's np.dot adds the
+// row's sum to a zeroed vector, so its zeros are +0 whatever the signs of sine and cosine, atan2(+0, +0) = +0 and the own cell is
+// inside the cone at every heading (`+ 0.0` below; the test `!(r0 > 0)` that stood here put it outside at every heading).
+__device__ __forceinline__ bool ig_in_cone(double r0, double r1, const IgCone& cn, double r2_in, double r2_out, double fov, double range) {
+    const double rn2 = r0 * r0 + r1 * r1, a1 = fabs(r1);
+    if (cn.fast && (rn2 > r2_out || r0 < 0.0 || a1 > r0 * cn.t_out)) return false;
+    if (cn.fast && rn2 < r2_in && a1 < r0 * cn.t_in) return true;
+    const double dphi = atan2(r1 + 0.0, r0 + 0.0);
+    const double rn = sqrt(rn2);
+    return rn < range && fabs(dphi) < fov / 2;
+}
+
 // targetMap.getVisibleCells (targetMap.py:43-84), computed by all `nthreads` threads of a block into the
 // LDS mask `vis[60]` (zeroed here).  Ends with a barrier.
 __device__ inline void ig_visible_block(const uint32_t* d2, double px, double py, double phi, double fov, double range,
@@ -147,29 +163,14 @@ __device__ inline void ig_visible_block(const uint32_t* d2, double px, double py
     ye = min(ye, IG_BEL);
     const int w = xe - xs, h = ye - ys;
     const int total = (w > 0 && h > 0) ? w * h : 0;
-    // The cone test `rn < range and |atan2(r1, r0)| < fov / 2` (targetMap.py:66-70) costs an fp64 atan2 and a square root per
-    // window cell, and two cells in three fail it.  A cell that is inside or outside by a margin far above the rounding of
-    // either side is decided by products alone (|r1| against r0 tan(fov/2 -+ 1e-9), rn^2 against range^2 (1 -+ 1e-12)); only
-    // a cell within those margins evaluates the reference's own expressions.  Same set, bit for bit.
     const IgCone cn = cone ? *cone : ig_cone(fov);
-    const bool fast = cn.fast;
-    const double t_in = cn.t_in, t_out = cn.t_out;
     const double r2_in = range * range * (1.0 - 1e-12), r2_out = range * range * (1.0 + 1e-12);
     for (int q = tid; q < total; q += nthreads) {
         int i = xs + q / h, j = ys + q % h;
         double cxp = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cyp = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
         double r0, r1;
         mat2vec(c, s, cxp - px, cyp - py, r0, r1);
-        const double rn2 = r0 * r0 + r1 * r1, a1 = fabs(r1);
-        bool inside;
-        if (fast && (rn2 > r2_out || !(r0 > 0.0) || a1 > r0 * t_out)) inside = false;
-        else if (fast && rn2 < r2_in && a1 < r0 * t_in) inside = true;
-        else {
-            double dphi = atan2(r1, r0);
-            double rn = sqrt(rn2);
-            inside = rn < range && fabs(dphi) < fov / 2;
-        }
-        if (inside) {
+        if (ig_in_cone(r0, r1, cn, r2_in, r2_out, fov, range)) {
             if (ig_check_visibility(d2, px, py, cxp, cyp)) atomicOr(&vis[j], 1ull << i);
         }
     }
