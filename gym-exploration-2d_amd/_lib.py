@@ -133,6 +133,15 @@ class GreedyParams(C.Structure):
                [(n, C.c_double) for n in ("dt", "radius", "fov_rad", "range")] + [("v", C.c_double * 3), ("w", C.c_double * 3)]
 
 
+class IgObserveParams(C.Structure):
+    """cagym_ig_observe_params (include/cagym_ig_observe.h; not in STRUCTS, which mirrors the structs cagym.h itself defines)."""
+    _fields_ = [("n_robots", C.c_int32), ("window", C.c_int32), ("rotate", C.c_int32), ("flags", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("detect_range", "fov_rad", "range")]
+
+
+IG_OBSERVE_ONLY_RESTARTED = 4  # CAGYM_IG_OBSERVE_ONLY_RESTARTED
+
+
 SNAP_MAGIC, SNAP_VERSION, SNAP_CORE, SNAP_IG = 0x43475331, 1, 1, 2  # CAGYM_SNAP_*
 
 
@@ -218,6 +227,7 @@ _ARGTYPES = {
     "cagym_ig_robot_actions": [_vp, _int, _vp, _vp, _vp],
     "cagym_ig_episode_boundary": [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_size_t, _vp],
     "cagym_ig_greedy_plan": [_vp, _P(GreedyParams), _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_observe": [_vp, _P(IgObserveParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],
     "cagym_dmcts_plan": [_vp, _P(DmctsParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     "cagym_episode_records_init": [_vp, _int, _vp],

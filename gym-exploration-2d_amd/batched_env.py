@@ -23,14 +23,15 @@ from ._pool import _PoolMixin
 from ._snapshot import _SNAP_OUT, EnvSnapshot, _SnapshotMixin  # noqa: F401  (EnvSnapshot and _SNAP_OUT are re-exported)
 from .dmcts import DeviceDecMCTSPlanner
 from .ga3c import GA3CCADRLPolicy
-from .ig import EPISODE_FOLD, GreedyPlanner, InfoGain
+from .ig import EPISODE_FOLD, OBSERVE_ONLY_RESTARTED, GreedyPlanner, InfoGain
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> hipStream_t as an int
 
 
 class _IgState(object):
     """What step() needs of an attached IG policy, whichever it is: the primitives, the planner and the robots' input buffers."""
-    __slots__ = ("kind", "ig", "R", "range", "episodic", "poses", "det", "n_det", "world", "planner")
+    __slots__ = ("kind", "ig", "R", "range", "episodic", "poses", "det", "n_det", "world", "planner",
+                 "window", "rotate", "team_reward", "gain", "observed", "belief_window")  # (second row: attach_ig_learner's)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -151,7 +152,14 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         if self._streaming and advance_episode:
             self._refill()
         g = self._igm
-        if g is not None and g.episodic and m is not None:
+        if g is not None and g.kind == "ig_learner":
+            if m is None:  # a new episode everywhere: prior beliefs, no running return, then the first observation of every world
+                g.ig.reset_belief(None)
+                g.ig.episode_stats["running"].zero_()
+                self._ig_observe(None, 0)
+            else:  # a manual restart of the masked worlds alone, inside the launch; not a finished episode, so nothing is folded
+                self._ig_observe(m, OBSERVE_ONLY_RESTARTED)
+        elif g is not None and g.episodic and m is not None:
             # a manual restart of the masked worlds only: prior belief, no communicated plans, running team return zeroed; it is
             # not a finished episode, so nothing is folded into the episode statistics (cagym_ig_episode_boundary without FOLD)
             g.ig.episode_boundary(g.planner.P, g.planner.workspace, None, m, 0)
@@ -227,6 +235,45 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         return self._attach_ig("ig_greedy", detect_fov, detect_range, 1, episodic,
                                lambda g: GreedyPlanner(g.ig, g.R, radius=radius, coordinate=coordinate))
 
+    def attach_ig_learner(self, detect_fov=60.0, detect_range=5.0, window=24, rotate=True):
+        """From now on the IG robots are the CALLER's to move - their rows of step()'s `actions` are their (v, omega), as for any
+        externally driven agent - and the env keeps what a learner needs around them: one belief per world, the team's MI reward,
+        the episode accumulators of ig_episode_stats(), and the belief as each robot sees it.  Every step() and reset() is followed,
+        on the same stream, by ONE cagym_ig_observe launch on the state it left (the observation follows the move: the learner's
+        next action is chosen from it).  It writes, in place, self.team_reward [N] f64 and three more entries of step()'s info:
+          "belief_window" [N, R, 3, window, window] f32 - robot k's ego-centred view of the world's belief, rows forward along its
+              heading (along +x with rotate=False), columns to its left, 0.5 m cells: P(occupied), cell mutual information, 1
+              inside the map (ig.belief_window_spec states the layout);
+          "gain" [N] f64 - the MI sum over the cells the team just observed, on the updated belief;
+          "observed" [N, 60] i64 - those cells (bit i of word j <=> cell (i, j)).
+        team_reward is gain, except for a world that step(auto_reset=True) just restarted: its gain is the first observation of
+        the new episode (on a prior belief, from the new start poses), which counts toward the new episode's return and is no
+        reward for the action that ended the old one - team_reward is 0 there, and the old episode's return is folded into
+        ig_episode_stats() before the new one starts.  reset() restarts every world and makes the first observation of each;
+        reset(world_mask=m) does both for the masked worlds alone, without counting an episode, and leaves the other worlds'
+        entries of the four tensors as they were.  Call reset() after attaching.  With attach_ga3c the GA3C agents' rows are the
+        network's and every other row, the robots' included, the caller's.  Replaces attach_ig_mcts / attach_ig_greedy and is
+        replaced by them; detach_ig_mcts() clears it.  rollout() is refused (it takes no external actions), and so is whatever an
+        attached planner refuses: snapshot / restore / fork, checkpoint, terminal observations, the trajectory ring, the split step."""
+        window = int(window)
+        if window < 4 or window > 64 or window % 2:
+            raise ValueError("attach_ig_learner: window must be even and within 4..64, got %d" % window)
+        if self._n_ig is not None and self._n_ig > 8:
+            raise ValueError("attach_ig_learner: at most 8 IG robots per world (cagym_ig_observe), the pool has %d" % self._n_ig)
+        self._attach_ig("ig_learner", detect_fov, detect_range, 1, True, lambda g: None)
+        g, N, dev = self._igm, self.N, self.device
+        g.window, g.rotate = window, bool(rotate)
+        g.team_reward = torch.zeros((N,), dtype=torch.float64, device=dev)
+        g.gain = torch.zeros((N,), dtype=torch.float64, device=dev)
+        g.observed = torch.zeros((N, 60), dtype=torch.int64, device=dev)
+        g.belief_window = torch.zeros((N, g.R, 3, window, window), dtype=torch.float32, device=dev)
+        self.team_reward = g.team_reward
+        return g.ig
+
+    def _ig_observe(self, restart_mask, flags):
+        g = self._igm
+        g.ig.observe(g.R, g.range, self.obs_oas, g.window, g.rotate, restart_mask, flags, g.team_reward, g.gain, g.observed, g.belief_window)
+
     def detach_ig_mcts(self):
         self._igm = None
         self.team_reward = None
@@ -243,7 +290,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         running [N] f64 team return of the episode in progress, sum [N] f64 over the finished episodes, last [N] f64 return of
         the last finished one, episodes [N] i32 finished episodes."""
         if self._igm is None:
-            raise RuntimeError("ig_episode_stats() needs attach_ig_mcts or attach_ig_greedy")
+            raise RuntimeError("ig_episode_stats() needs attach_ig_mcts, attach_ig_greedy or attach_ig_learner")
         return dict(self._igm.ig.episode_stats)
 
     def _internal_actions(self, a, team_reward_out=None, oas=None):
@@ -251,7 +298,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         team_reward_out: where the team reward of this step goes (rollout: slice t of its buffer); oas: the OtherAgentsStates
         table the last step wrote, when that is not self.obs_oas (rollout: slice t - 1)."""
         ga3c = self._drives_ga3c()
-        if not ga3c and self._igm is None:
+        plans = self._igm is not None and self._igm.kind != "ig_learner"  # (a learner's robots are driven by the caller's rows)
+        if not ga3c and not plans:
             return a
         table = self._act
         if ga3c:
@@ -260,7 +308,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             table.zero_()
         else:
             table.copy_(a)
-        if self._igm is not None:
+        if plans:
             g = self._igm
             g.ig.robot_inputs(g.R, g.range, self.obs_oas if oas is None else oas, g.poses, g.det, g.n_det)
             observed = g.ig.update_belief(g.poses, g.det, g.n_det)
@@ -283,14 +331,17 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         if rc:
             _lib.check(self.L, self.h, rc, "cagym_step")
         g = self._igm
-        if g is not None and g.episodic:
+        if g is not None and g.kind == "ig_learner":  # the observation of the state the step left; restarted worlds fold and start anew
+            self._ig_observe(restart, EPISODE_FOLD if restart is not None else 0)
+        elif g is not None and g.episodic:
             g.ig.episode_boundary(g.planner.P, g.planner.workspace, self.team_reward, restart, EPISODE_FOLD)
 
     def step(self, actions=None, auto_reset=False):
         """One env.step() of every world.  auto_reset=True: finished worlds restart inside the same launch
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
-        itself is only read."""
+        itself is only read.  With attach_ig_learner the robots' rows are the learner's (v, omega), and info also carries
+        "belief_window", "gain" and "observed" of the state the step left."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
             raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
@@ -300,6 +351,9 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         self._chained_step(self._actions(actions), self._out, auto_reset, self.game_over if auto_reset else None, term=True)
         self._after_steps(auto_reset, self.flags, self.reward, self.game_over, 1)
         info = {"flags": self.flags}
+        g = self._igm
+        if g is not None and g.kind == "ig_learner":
+            info.update(belief_window=g.belief_window, gain=g.gain, observed=g.observed)
         if auto_reset and self._term is not None:
             info["terminal"] = dict(self._term, valid=self.game_over)
         return self._obs(), self.reward, self.game_over, info
@@ -380,6 +434,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         with keep_terminal_observations() alone it stays the single launch."""
         self._records_contract(auto_reset, "rollout")
         T, g = int(n_steps), self._igm
+        if g is not None and g.kind == "ig_learner":
+            raise RuntimeError("rollout() with ig_learner attached: the learner's robots need the caller's actions at every step; use step()")
         if g is not None and not g.episodic:
             raise RuntimeError("rollout() with %s attached is not implemented for this attach (the planner needs per-world "
                                "restarts): attach_%s(episodic=True)" % (g.kind, g.kind))

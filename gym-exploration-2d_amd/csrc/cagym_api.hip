@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cagym.h"
+#include "../../include/cagym_ig_observe.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
 #include "cagym_kernels3.h"  // LDS layout helpers; the kernels themselves are instantiated in the cagym_k3_tu.hip units
@@ -26,6 +27,7 @@
 #include "cagym_dmcts.h"
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
+#include "cagym_ig_observe.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
 #include "cagym_snapshot.h"
@@ -2060,6 +2062,30 @@ int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const 
     hipLaunchKernelGGL(k_ig_greedy, dim3((unsigned)(p.coordinate ? N : N * p.n_robots)), dim3(IGG_THREADS), 0,
                        reinterpret_cast<hipStream_t>(stream), e->G, P, poses, actions, choice, mi,
                        reinterpret_cast<unsigned long long*>(claimed));
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_observe(void* env, const cagym_ig_observe_params* params, const float* obs_oas, const uint8_t* restart_mask,
+                     double* team_reward, double* gain, uint64_t* observed, float* belief_window, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_observe");
+    if (!params || !obs_oas) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: null argument");
+    const cagym_ig_observe_params& p = *params;
+    if (p.n_robots < 1 || p.n_robots > IGO_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: n_robots must be 1..8");
+    if (p.window < 4 || p.window > 64 || (p.window & 1)) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: window must be even and within 4..64");
+    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: rotate must be 0 or 1");
+    if (p.flags & ~(uint32_t)(CAGYM_IG_EPISODE_FOLD | CAGYM_IG_OBSERVE_ONLY_RESTARTED))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: unknown flags");
+    // (the negated comparison refuses NaN)
+    if (!(p.fov_rad > 0.0 && p.range > 0.0 && p.detect_range > 0.0) || !std::isfinite(p.fov_rad) || !std::isfinite(p.range) ||
+        !std::isfinite(p.detect_range))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: fov_rad, range and detect_range must be finite and positive");
+    if (int rc = ig_robots_check(e, p.n_robots, "cagym_ig_observe")) return rc;
+    ON_DEVICE(e);
+    IgObserveParams P;
+    P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.det_range = (float)p.detect_range; P.fov = p.fov_rad; P.range = p.range;
+    hipLaunchKernelGGL(k_ig_observe, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G, e->ig_ep,
+                       P, obs_oas, restart_mask, team_reward, gain, reinterpret_cast<unsigned long long*>(observed), belief_window);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

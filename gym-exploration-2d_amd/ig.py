@@ -13,6 +13,7 @@ import torch
 from . import _lib
 
 EPISODE_FOLD, EPISODE_PLANS_ONLY = 1, 2  # CAGYM_IG_EPISODE_* (include/cagym.h)
+OBSERVE_ONLY_RESTARTED = _lib.IG_OBSERVE_ONLY_RESTARTED  # cagym_ig_observe's second flag, beside EPISODE_FOLD
 FOV_DEG60 = 60.0 * np.pi / 180  # detect_fov=60.0 -> targetMap.sensFOV (ig_mcts.py:67)
 PRIMITIVES = np.array([[v, w] for v in (0.0, 2.0, 4.0) for w in (-0.5 * np.pi, 0.0, 0.5 * np.pi)])  # ig_mcts.py:247-253
 GREEDY_V, GREEDY_W = (0.0, 2.0, 4.0), (-np.pi, 0.0, np.pi)  # ig_greedy.py:65-66: candidate c = 3 a + b is (v[a], w[b])
@@ -66,6 +67,17 @@ class InfoGain(object):
             team_reward = self._t(team_reward, torch.float64, (self.b.N,))
         _lib.call(self.L, self.b.h, "cagym_ig_episode_boundary", C.byref(params), _lib.ptr(team_reward), _lib.ptr(restart_mask), int(flags),
                   workspace.data_ptr(), workspace.numel(), self.b._stream())
+
+    def observe(self, n_robots, detect_range, obs_oas, window=24, rotate=True, restart_mask=None, flags=0, team_reward=None, gain=None,
+                observed=None, belief_window=None):
+        """cagym_ig_observe: ONE launch on the current stream behind the step or reset that wrote obs_oas - the restart of the worlds
+        of the DEVICE mask restart_mask [N] u8 (EPISODE_FOLD folds their running return, OBSERVE_ONLY_RESTARTED skips every other
+        world), the robots' poses and detections, the belief update, the MI sum over the observed cells and the robots' belief
+        windows.  Every output is a contiguous device tensor to write into, or None: team_reward / gain [N] f64, observed [N,60]
+        i64, belief_window [N,R,3,G,G] f32."""
+        P = _lib.IgObserveParams(int(n_robots), int(window), int(rotate), int(flags), float(detect_range), self.fov, self.range)
+        _lib.call(self.L, self.b.h, "cagym_ig_observe", C.byref(P), obs_oas.data_ptr(), _lib.ptr(restart_mask), _lib.ptr(team_reward),
+                  _lib.ptr(gain), _lib.ptr(observed), _lib.ptr(belief_window), self.b._stream())
 
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
@@ -178,6 +190,45 @@ class GreedyPlanner(object):
         o = self._out
         self.actions, self.choice, self.mi, self.claimed = o["actions"], o["choice"], o["mi"], o["claimed"]
         return self.actions, self.choice
+
+
+def belief_window_spec(belief, mi, poses, G, rotate):
+    """The belief windows of cagym_ig_observe in plain numpy - the executable statement of their layout.  belief, mi: [60, 60] f64
+    odds ratios and cached cell MI of one world, indexed [j, i] (j along y); poses [R, 3] f64 (x, y, heading).  Returns
+    (window [R, 3, G, G] f32, i [R, G, G], j [R, G, G] int64 source cells, qx, qy [R, G, G] f64 sample points).  Out cell (a, b):
+    a forward, b left; channel 0 = odds / (odds + 1), channel 1 = cell MI, channel 2 = 1 inside the map; outside all three are 0.
+    Every product and sum is a separate fp64 operation in the order written (numpy fuses nothing); with rotate the sine and cosine
+    are numpy's, which may differ from the library's in the last bit."""
+    belief, mi = np.asarray(belief, dtype=np.float64), np.asarray(mi, dtype=np.float64)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    G, c = int(G), 0.5
+    e = (np.arange(G, dtype=np.float64) - G // 2 + 0.5) * c
+    ex, ey = e[None, :, None], e[None, None, :]
+    px, py, th = (poses[:, k][:, None, None] for k in range(3))
+    s, cs = (np.sin(th), np.cos(th)) if rotate else (np.zeros_like(th), np.ones_like(th))
+    qx = px + cs * ex - s * ey
+    qy = py + s * ex + cs * ey
+    i = np.floor((qx + 15.0) / c).astype(np.int64)
+    j = np.floor((qy + 15.0) / c).astype(np.int64)
+    inside = (i >= 0) & (i < 60) & (j >= 0) & (j < 60)
+    ic, jc = np.clip(i, 0, 59), np.clip(j, 0, 59)
+    odds = belief[jc, ic]
+    out = np.zeros((poses.shape[0], 3, G, G), dtype=np.float32)
+    out[:, 0] = np.where(inside, odds / (odds + 1), 0.0).astype(np.float32)
+    out[:, 1] = np.where(inside, mi[jc, ic], 0.0).astype(np.float32)
+    out[:, 2] = inside.astype(np.float32)
+    return out, i, j, qx, qy
+
+
+def cell_mi(r):
+    """ig_cell_mi of csrc/cagym_ig.h (targetMap's per-cell mutual information of an odds ratio r) in numpy: what the library's MI
+    cache holds, up to the last bits of the logarithm."""
+    r = np.asarray(r, dtype=np.float64)
+    rO, rE, fn, fp = 1.5, 0.66, 0.1, 0.05
+    p = r / (r + 1)
+    f_p = np.log((r + 1) / (r + (1 / rO))) - np.log(rO) / (r * rO + 1)
+    f_n = np.log((r + 1) / (r + (1 / rE))) - np.log(rE) / (r * rE + 1)
+    return (p * (1 - fn) + (1 - p) * fp) * f_p + (p * fn + (1 - p) * (1 - fp)) * f_n
 
 
 def find_targets_in_obs(other_agents_states, detect_range=5.0):

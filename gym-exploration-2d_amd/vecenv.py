@@ -110,6 +110,8 @@ class CagymVecEnv(object):
         infos = {"flags": info["flags"]}
         if getattr(b, "_igm", None) is not None:  # an episodic attach_ig_mcts: the team's MI reward of this step, [N] f64
             infos["team_reward"] = b.team_reward
+            if "belief_window" in info:  # attach_ig_learner: the robots' belief windows, an image beside the flat observation
+                infos["belief_window"], infos["gain"] = info["belief_window"], info["gain"]
         if self.terminal_observation:
             infos["terminal_observation"] = self.flat(info["terminal"])
         return self.flat(), rews, go.bool(), infos

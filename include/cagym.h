@@ -469,6 +469,39 @@ typedef struct cagym_ig_greedy_params {
 int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const double* poses, double* actions, uint8_t* choice,
                          double* mi, uint64_t* claimed, void* stream);
 
+/* ---- The learner's end of a step: restart, robot inputs, belief update, team reward, accumulators and belief windows, fused ----
+ * For an exploration policy that is none of the built-in planners: it moves the CAGYM_POL_IGMCTS robots through the step's action
+ * table and calls this behind every step or reset.  ONE launch on `stream` (one workgroup of 256 threads per world), no host
+ * synchronisation, no atomics, barriers only.  params: cagym_ig_observe_params, defined in include/cagym_ig_observe.h (n_robots
+ * 1..8, window = G, rotate, flags, detect_range, fov_rad, range).  obs_oas DEVICE [N,M,M-1,10] f32: the table the step or reset just
+ * wrote.  restart_mask DEVICE [N] u8 or NULL - in a stepping loop the game_over output of the auto-resetting step.  Outputs, DEVICE,
+ * each may be NULL: team_reward [N] f64, gain [N] f64, observed [N,60] u64, belief_window [N,R,3,G,G] f32.
+ * For every world w, in this order:
+ *   restarted = restart_mask && restart_mask[w].  With CAGYM_IG_OBSERVE_ONLY_RESTARTED a world that is not restarted is skipped:
+ *     nothing of it is read or written (a manual restart of some worlds).
+ *   if restarted: with CAGYM_IG_EPISODE_FOLD sum[w] += running[w], last[w] = running[w], episodes[w] += 1 (the accumulators of
+ *     cagym_ig_get_episode_stats); running[w] = 0; belief and MI cache return to the prior, as cagym_ig_reset_belief leaves them.
+ *   poses and detections of the world's n_robots robots as cagym_ig_robot_inputs computes them (kept on chip);
+ *   the belief update of cagym_ig_update_belief with those poses in slot order (P = n_robots); the union of the visible cells goes
+ *     to observed, and the MI cache is refreshed on that union;
+ *   r = the MI sum over the union on the updated belief - bit for bit what cagym_ig_mi_reward returns for (observed[w], w);
+ *   running[w] += r; gain[w] = r; team_reward[w] = restarted ? 0 : r  (the first observation of a new episode counts toward that
+ *     episode's return; it is no reward for the action that ended the old one);
+ *   belief_window[w, k] for robot k at pose (px, py, heading): out cell (a, b), a forward, b left (b fastest in memory), cell size
+ *     c = 0.5; ex = (a - G/2 + 0.5) c, ey = (b - G/2 + 0.5) c; (s, cs) = (sin, cos)(heading) with rotate = 1, else (0, 1);
+ *     qx = px + cs ex - s ey, qy = py + s ex + cs ey (fp64, separate products and sums in this order); belief cell
+ *     i = floor((qx + 15) / c), j = floor((qy + 15) / c) (getCellsFromPose).  Inside 0..59 on both axes: channel 0 =
+ *     (float)(odds / (odds + 1)) of belief[w, j, i], channel 1 = (float) that cell's cached MI, channel 2 = 1; outside: 0, 0, 0.
+ * Belief, observed and gain are those of the chain cagym_ig_reset_belief(mask) -> cagym_ig_robot_inputs -> cagym_ig_update_belief
+ * -> cagym_ig_mi_reward, bit for bit.
+ * Errors: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params / obs_oas, n_robots outside 1..8, window odd or
+ * outside 4..64, rotate outside {0, 1}, unknown flags, a non-finite or non-positive fov_rad, range or detect_range; the robot-count
+ * errors of cagym_ig_robot_inputs; CAGYM_E_DEVICE as every launching entry.  A refused call leaves the handle untouched. */
+enum { CAGYM_IG_OBSERVE_ONLY_RESTARTED = 4 }; /* beside CAGYM_IG_EPISODE_FOLD = 1 in cagym_ig_observe_params.flags */
+typedef struct cagym_ig_observe_params cagym_ig_observe_params;
+int cagym_ig_observe(void* env, const cagym_ig_observe_params* params, const float* obs_oas, const uint8_t* restart_mask,
+                     double* team_reward, double* gain, uint64_t* observed, float* belief_window, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
