@@ -1,6 +1,6 @@
 """The consumers of BatchedCollisionAvoidanceEnv's step outputs - per-scenario episode records, the append-only episode log, the
-trajectory ring - and the terminal observations.  The three share one contract (include/cagym.h): fed by auto-reset stepping
-only, every step once and in order, a desync word that counts what went past them, a restart with reset()."""
+trajectory ring, the IG team's episode log - and the terminal observations.  They share one contract (include/cagym.h): fed by
+auto-reset stepping only, every step once and in order, a desync word that counts what went past them, a restart with reset()."""
 import collections
 
 import torch
@@ -26,7 +26,12 @@ _REC = _Consumer(
     None,
     "episode records are out of step with the env in %d world-launches (desync): the recorder was fed a step twice, skipped one, "
     "or saw a step without auto-reset")
-_CONSUMERS = (_RING, _LOG, _REC)  # the order in which their auto_reset=False refusals compete
+_IGLOG = _Consumer(
+    "_iglog", "an IG episode log", "detach_ig_episode_log", "cagym_ig_episode_log_update goes behind the auto-resetting step only",
+    None,
+    "the IG episode log is out of step with the env in %d world-launches (desync): it was fed a step twice, skipped one, or saw a "
+    "step without auto-reset")
+_CONSUMERS = (_RING, _LOG, _REC, _IGLOG)  # the order in which their auto_reset=False refusals compete
 
 
 class _ConsumersMixin(object):
@@ -42,9 +47,12 @@ class _ConsumersMixin(object):
         self._term_c = None       # ... as the cagym_terminal_outputs step() passes
         self._traj = None         # n_slices of attach_trajectory_ring, None while detached
         self._traj_views = None
+        self._iglog_fn = L.cagym_ig_episode_log_update
+        self._iglog = None        # capacity of attach_ig_episode_log, None while detached
+        self._iglog_views = None
 
     def _records_contract(self, auto_reset, what):
-        if not auto_reset and (self._traj is not None or self._log is not None or self._rec is not None):
+        if not auto_reset and any(getattr(self, c.attr) is not None for c in _CONSUMERS):
             c = next(c for c in _CONSUMERS if getattr(self, c.attr) is not None)
             raise RuntimeError("%s(auto_reset=False) with %s attached: %s, every step exactly once and in order (include/cagym.h); "
                                "%s() first" % (what, c.noun, c.fed, c.detach))
@@ -191,6 +199,78 @@ class _ConsumersMixin(object):
             order = torch.argsort(rows["slice"] * self.N + rows["world"].to(torch.int64), stable=True)
             rows = {k: t.index_select(0, order) for k, t in rows.items()}
         rows["count"] = torch.ones((n,), dtype=torch.int32, device=self.device)
+        return rows
+
+    # ---- the IG team's episode log (include/cagym.h: cagym_ig_episode_log_*) ---------------------------------------------------
+    def attach_ig_episode_log(self, capacity=65536, p_found=0.75):
+        """From now on every auto-resetting step of an IG team is followed, on the same stream and BEFORE the launch that restarts a
+        finished world's belief, by one cagym_ig_episode_log_update: ONE ROW PER FINISHED TEAM EPISODE in a device ring of
+        `capacity` rows (the newest overwrite the oldest), with what a target search is judged by.  A row names its episode by
+        key = (uint32)(world + episode * N), the stream key its world was drawn for - the same key on every handle of the same
+        stream seed, whatever policy drives it (stats.paired_by_key) - and carries world, episode, slice, steps, ret (the team
+        return, bit for bit ig_episode_stats()["last"]), n_targets, n_found, found_at [M] (-2: the slot is no target, -1: a target
+        never found, else the 1-based step at which the odds of its belief cell first reached p_found / (1 - p_found)), entropy
+        (nats, over the 3600 cells), residual_mi (the MI still to be gained) and n_touched (cells off the prior), all of the
+        belief the episode ended on.  The targets are the STATIC agents of the episode's pool slot.  ig.episode_log_spec states
+        the belief columns in numpy, stats.exploration_statistics summarises a log.
+        Needs an IG attach that restarts per world - attach_ig_learner, or attach_ig_mcts / attach_ig_greedy with episodic=True -
+        and stays attached when one such attach replaces another.  step() and rollout() feed it through the same chain;
+        CagymVecEnv inherits it.  reset() restarts every world's running values (rows kept), reset(world_mask=m) the masked
+        worlds'.  step(auto_reset=False) and rollout(auto_reset=False) are refused while attached; the library refuses restore /
+        fork while the log is initialised.  A world that lapped its ring inside a rollout logs the scenario that actually ran
+        under the key of the one it should have met: stream_stats()["n_lapped"] tells.  Attaching again clears the log and may
+        change capacity and p_found."""
+        capacity, p_found = int(capacity), float(p_found)
+        if capacity < 1:
+            raise ValueError("attach_ig_episode_log: capacity must be >= 1, got %d" % capacity)
+        if not 0.0 < p_found < 1.0:
+            raise ValueError("attach_ig_episode_log: p_found must lie inside (0, 1), got %r" % (p_found,))
+        if self._igm is None or not self._igm.episodic:
+            raise RuntimeError("attach_ig_episode_log() needs an IG attach that restarts per world: attach_ig_learner(), or "
+                               "attach_ig_mcts / attach_ig_greedy with episodic=True")
+        _lib.call(self.L, self.h, "cagym_ig_episode_log_init", capacity, p_found / (1.0 - p_found), self._stream())
+        self._iglog, self._iglog_views = capacity, None
+        return self
+
+    def detach_ig_episode_log(self):
+        """Stop feeding the log (the library keeps it, and keeps refusing restore / fork; attach again to clear and resume)."""
+        self._iglog = None
+
+    def clear_ig_episode_log(self):
+        """Empty the log: every row, head, the call counter and desync; every world forgets the episode in progress."""
+        self._refuse_without("clear_ig_episode_log", _IGLOG)
+        _lib.call(self.L, self.h, "cagym_ig_episode_log_restart", None, 1, self._stream())
+
+    def _ig_log_update(self, game_over, team_reward):
+        """Behind the step launch that wrote game_over, before the team's boundary / observe launch; team_reward: what that
+        boundary launch is given (None behind a learner's step)."""
+        rc = self._iglog_fn(self.h, game_over.data_ptr(), _lib.ptr(team_reward), self._stream())
+        if rc:
+            _lib.check(self.L, self.h, rc, "cagym_ig_episode_log_update")
+
+    def ig_episode_log_views(self):
+        """Zero-copy device views of the ring and its words, no synchronisation: key (u32 bits as int32), world, episode, steps,
+        n_targets, n_found, n_touched [L] i32, slice [L] i64, ret, entropy, residual_mi [L] f64, found_at [L, M] i32, the running
+        steps_run, cursor [N], found_run [N, M] i32, head [1] i64 (rows ever appended; row i lives at index i % L), desync [1]."""
+        self._refuse_without("ig_episode_log_views", _IGLOG)
+        if self._iglog_views is None:
+            self._iglog_views = self._get_views("cagym_ig_episode_log_get", _lib.CagymIgEpisodeLogPtrs(), _lib.IGLOG_FIELDS, "capacity")
+        return dict(self._iglog_views)
+
+    def ig_episode_log(self, last=None, check=True):
+        """The valid rows in append order, oldest first, as device tensors (copies): the ring columns of ig_episode_log_views()
+        with key as int64 in [0, 2^32).  One synchronisation, to read head.  last=K: the newest K rows only; check: raise
+        RuntimeError when the log saw a skipped, doubled or non-auto-reset step (desync != 0)."""
+        v = self.ig_episode_log_views()
+        L = self._iglog
+        head, d = torch.cat([v["head"], v["desync"].to(torch.int64)]).tolist()
+        self._check_desync(_IGLOG, d, check)
+        n = min(head, L)
+        if last is not None:
+            n = min(n, max(int(last), 0))
+        idx = (torch.arange(head - n, head, dtype=torch.int64, device=self.device) % L)
+        rows = {k: v[k].index_select(0, idx) for k, _, shape in _lib.IGLOG_FIELDS if shape in ("L", "LM")}
+        rows["key"] = rows["key"].to(torch.int64) & 0xFFFFFFFF
         return rows
 
     # ---- terminal observations and the trajectory ring (include/cagym.h: cagym_step_autoreset_keep, cagym_trajectory_*) ---------

@@ -141,6 +141,17 @@ class IgObserveParams(C.Structure):
 
 IG_OBSERVE_ONLY_RESTARTED = 4  # CAGYM_IG_OBSERVE_ONLY_RESTARTED
 
+# cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
+IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
+                ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
+                ("residual_mi", "f8", "L"), ("n_touched", "i4", "L"), ("steps_run", "i4", "N"), ("found_run", "i4", "NM"),
+                ("cursor", "i4", "N"), ("head", "u8", "1"), ("desync", "i4", "1")]
+
+
+class CagymIgEpisodeLogPtrs(C.Structure):
+    """cagym_ig_episode_log_ptrs (not in STRUCTS, which mirrors the structs cagym.h itself defines)."""
+    _fields_ = [(n, C.c_void_p) for n, _, _ in IGLOG_FIELDS] + [("capacity", C.c_int32)]
+
 
 SNAP_MAGIC, SNAP_VERSION, SNAP_CORE, SNAP_IG = 0x43475331, 1, 1, 2  # CAGYM_SNAP_*
 
@@ -238,6 +249,10 @@ _ARGTYPES = {
     "cagym_episode_log_update": [_vp, _vp, _vp, _vp, _int, _vp],
     "cagym_episode_log_restart": [_vp, _vp, _int, _vp],
     "cagym_episode_log_get": [_vp, _P(CagymEpisodeLogPtrs)],
+    "cagym_ig_episode_log_init": [_vp, _int, _dbl, _vp],
+    "cagym_ig_episode_log_update": [_vp, _vp, _vp, _vp],
+    "cagym_ig_episode_log_restart": [_vp, _vp, _int, _vp],
+    "cagym_ig_episode_log_get": [_vp, _P(CagymIgEpisodeLogPtrs)],
     "cagym_snapshot_layout_of": [_vp, _P(CagymSnapshotLayout)],
     "cagym_snapshot": [_vp, _vp, _int, _vp, _vp],
     "cagym_restore": [_vp, _P(CagymSnapshotLayout), _vp, _vp, _int, _vp],

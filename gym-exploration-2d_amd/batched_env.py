@@ -319,8 +319,9 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
 
     def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None, term=False):
         """One step with whatever is attached, three parts in stream order: the internal actions (_internal_actions), the step
-        launch into the CagymOutputs `o`, and the episodic IG team's end of the step - its running return and the restart of the
-        worlds of `restart` (under auto_reset the game_over tensor `o` points at, else None).  term: hand the env's terminal buffers
+        launch into the CagymOutputs `o`, and the episodic IG team's end of the step - its episode log's update
+        (attach_ig_episode_log), then its running return and the restart of the worlds of `restart` (under auto_reset the
+        game_over tensor `o` points at, else None).  term: hand the env's terminal buffers
         to the step (step() does, rollout() does not).  (No torch.cuda.device context
         here or anywhere else around the C ABI: every launching entry makes the handle's device current itself.)"""
         a = self._internal_actions(a, team_reward_out, oas)
@@ -331,6 +332,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         if rc:
             _lib.check(self.L, self.h, rc, "cagym_step")
         g = self._igm
+        if self._iglog is not None and g is not None and restart is not None:  # rows of the finished worlds, before their beliefs restart
+            self._ig_log_update(restart, None if g.kind == "ig_learner" else self.team_reward)
         if g is not None and g.kind == "ig_learner":  # the observation of the state the step left; restarted worlds fold and start anew
             self._ig_observe(restart, EPISODE_FOLD if restart is not None else 0)
         elif g is not None and g.episodic:

@@ -11,6 +11,7 @@
 
 #include "../../include/cagym.h"
 #include "../../include/cagym_ig_observe.h"
+#include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
 #include "cagym_kernels3.h"  // LDS layout helpers; the kernels themselves are instantiated in the cagym_k3_tu.hip units
@@ -28,6 +29,7 @@
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
 #include "cagym_ig_observe.h"
+#include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
 #include "cagym_snapshot.h"
@@ -91,6 +93,9 @@ struct Env {
     TrajRing traj{};                 // trajectory ring (cagym_trajectory_init allocates it: the running block once, the ring per n_slices)
     bool traj_ready = false;
     void* traj_ring = nullptr;       // the ring's one allocation (TrajRing's planes are carved from it)
+    IgEpLog iglog{};                 // the IG team's episode log (cagym_ig_episode_log_init allocates it: the running block once, the ring per capacity)
+    bool iglog_ready = false;
+    void* iglog_ring = nullptr;      // the ring's one allocation (IgEpLog's row columns are carved from it)
 };
 enum { N_IG_UNEQUAL = -1, N_IG_RANDOM = -2 };
 
@@ -325,12 +330,22 @@ inline int traj_restart(Env* e, const uint8_t* world_mask, bool clear, hipStream
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }
+// the IG team's episode log's restart / clear launch (csrc/cagym_ig_episode_log.h); a no-op for handles that never initialised it
+inline int iglog_restart(Env* e, const uint8_t* world_mask, bool clear_rows, hipStream_t st) {
+    if (!e->iglog_ready) return CAGYM_OK;
+    const size_t rows = (size_t)std::max(e->cfg.n_worlds, clear_rows ? e->iglog.capacity : 0) * e->cfg.max_agents;
+    const unsigned grid = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_ig_episode_log_restart, dim3(grid), dim3(256), 0, st, e->D, e->iglog, world_mask, clear_rows ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
 // The three behind cagym_reset - the episode the masked worlds abandon leaves no record, no row, and its rows in the ring without a
 // `last` slice - and behind a new pool (every world): the records describe the pool (cleared); the log and the ring are history (their
 // rows stay, the running values go)
 inline int episodes_restart(Env* e, const uint8_t* world_mask, bool new_pool, hipStream_t st) {
     if (int rc = eprec_restart(e, world_mask, new_pool, st)) return rc;
     if (int rc = eplog_restart(e, world_mask, false, st)) return rc;
+    if (int rc = iglog_restart(e, world_mask, false, st)) return rc;  // (the IG team's log: history too)
     return traj_restart(e, world_mask, false, st);
 }
 // every slot's raster from its rectangles (FIELD_RASTER); a handle without rectangles has none
@@ -453,6 +468,14 @@ template <class V> constexpr void eplog_run_members(EpLog& G, size_t N, size_t M
     v(G.run.t_run, N * M); v(G.run.ret_run, N); v(G.run.steps_run, N); v(G.run.atgoal_run, N); v(G.run.cursor, N); v(G.run.desync, 1);
     v(G.seq, 1); v(G.head, 1); v(G.pos, N, LAYOUT_SCRATCH); v(G.cnt, N, LAYOUT_SCRATCH);
 }
+// the IG team's episode log (in no checkpoint): its ring of L rows, and its running block (pos lives between the launches of one update)
+template <class V> constexpr void iglog_ring_members(IgEpLog& G, size_t L, size_t M, V& v) {
+    v(G.slice, L); v(G.ret, L); v(G.entropy, L); v(G.residual_mi, L); v(G.key, L); v(G.world, L); v(G.episode, L); v(G.steps, L);
+    v(G.n_targets, L); v(G.n_found, L); v(G.n_touched, L); v(G.found_at, L * M);
+}
+template <class V> constexpr void iglog_run_members(IgEpLog& G, size_t N, size_t M, V& v) {
+    v(G.head, 1); v(G.seq, 1); v(G.desync, 1); v(G.steps_run, N); v(G.cursor, N); v(G.found_run, N * M); v(G.pos, N, LAYOUT_SCRATCH);
+}
 // the replay's buffer of Q keys, and its words and per-slot tables
 template <class V> constexpr void replay_ring_members(ReplayDev& R, size_t Q, V& v) { v(R.buf_key, Q); }
 template <class V> constexpr void replay_table_members(ReplayDev& R, size_t S, V& v) { v(R.words, RPW_WORDS); v(R.buf_gen, 1); v(R.slot_key, S); v(R.slot_gen, S); }
@@ -523,6 +546,21 @@ inline int eplog_alloc(Env* e, int capacity) {
         G.capacity = capacity;
     }
     e->elog = G;
+    return CAGYM_OK;
+}
+// the IG team's log: the running block (once per handle) and the ring (once per capacity); e->iglog is complete afterwards
+inline int iglog_alloc(Env* e, int capacity) {
+    const size_t N = e->cfg.n_worlds, M = e->cfg.max_agents, L = (size_t)capacity;
+    IgEpLog G = e->iglog;
+    if (!G.steps_run) {
+        if (int rc = block_alloc(e, [&](auto& v) { iglog_run_members(G, N, M, v); })) return rc;
+        e->iglog = G;  // kept whatever becomes of the ring's allocation
+    }
+    if (!e->iglog_ring || G.capacity != capacity) {
+        if (int rc = ring_alloc(e, &e->iglog_ring, "iglog_ring", false, [&](auto& v) { iglog_ring_members(G, L, M, v); })) return rc;
+        G.capacity = capacity;
+    }
+    e->iglog = G;
     return CAGYM_OK;
 }
 // the replay's words and per-slot tables (once per handle) and its buffer (once per capacity); e->replay is complete afterwards
@@ -2200,6 +2238,51 @@ int cagym_episode_log_get(void* env, cagym_episode_log_ptrs* out) {
     return CAGYM_OK;
 }
 
+// ---- the IG team's episode log (csrc/cagym_ig_episode_log.h) --------------------------------------------------------------------------
+int cagym_ig_episode_log_init(void* env, int capacity, double odds_found, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_episode_log_init");
+    if (capacity < 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_episode_log_init: capacity must be >= 1");
+    if (!(odds_found > 0.0) || !std::isfinite(odds_found))  // (the negated comparison refuses NaN)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_episode_log_init: odds_found must be finite and positive");
+    ON_DEVICE(e);
+    if (int rc = iglog_alloc(e, capacity)) return rc;
+    e->iglog.odds_found = odds_found;
+    e->iglog_ready = true;
+    return iglog_restart(e, nullptr, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_ig_episode_log_update(void* env, const uint8_t* game_over, const double* team_reward, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_episode_log_update");
+    REQUIRE(e, e->iglog_ready, "cagym_ig_episode_log_update", "cagym_ig_episode_log_init");
+    if (!game_over) return fail(e, CAGYM_E_INVALID, "cagym_ig_episode_log_update: game_over is required");
+    ON_DEVICE(e);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int N = e->cfg.n_worlds;
+    hipLaunchKernelGGL(k_ig_episode_log_scan, dim3(1), dim3(IGLOG_NT_SCAN), 0, st, e->iglog, N, e->D.episode, game_over);
+    hipLaunchKernelGGL(k_ig_episode_log_update, dim3((unsigned)N), dim3(IGLOG_NT), 0, st, e->D, e->G, e->ig_ep, e->iglog, team_reward);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_episode_log_restart");
+    REQUIRE(e, e->iglog_ready, "cagym_ig_episode_log_restart", "cagym_ig_episode_log_init");
+    ON_DEVICE(e);
+    return iglog_restart(e, world_mask, clear_rows != 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cagym_ig_episode_log_get(void* env, cagym_ig_episode_log_ptrs* out) {
+    ENTRY_IG(e, env, "cagym_ig_episode_log_get");
+    REQUIRE(e, e->iglog_ready, "cagym_ig_episode_log_get", "cagym_ig_episode_log_init");
+    if (!out) return fail(e, CAGYM_E_INVALID, "null out");
+    const IgEpLog& G = e->iglog;
+    out->key = G.key; out->world = G.world; out->episode = G.episode; out->slice = reinterpret_cast<const int64_t*>(G.slice); out->steps = G.steps;
+    out->ret = G.ret; out->n_targets = G.n_targets; out->n_found = G.n_found; out->found_at = G.found_at; out->entropy = G.entropy;
+    out->residual_mi = G.residual_mi; out->n_touched = G.n_touched; out->steps_run = G.steps_run; out->found_run = G.found_run;
+    out->cursor = G.cursor; out->head = reinterpret_cast<const uint64_t*>(G.head); out->desync = G.desync; out->capacity = G.capacity;
+    return CAGYM_OK;
+}
+
 // ---- per-world snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------------
 int cagym_snapshot_layout_of(void* env, cagym_snapshot_layout* out) {
     ENTRY(e, env);
@@ -2225,6 +2308,12 @@ static int refuse_other_timeline(Env* e, const char* what) {
     if (e->traj_ready) return fail(e, CAGYM_E_STATE, w + " with a trajectory ring initialised: its running values would describe another timeline");
     return CAGYM_OK;
 }
+// ... and, behind every refusal the two calls made before it existed, the IG team's episode log
+static int refuse_iglog_timeline(Env* e, const char* what) {
+    if (e->iglog_ready)
+        return fail(e, CAGYM_E_STATE, std::string(what) + " with an IG episode log initialised: its running values would describe another timeline");
+    return CAGYM_OK;
+}
 
 int cagym_snapshot(void* env, const int32_t* worlds, int n, void* blob, void* stream) {
     ENTRY_POOL(e, env, "cagym_snapshot");
@@ -2245,6 +2334,7 @@ int cagym_restore(void* env, const cagym_snapshot_layout* layout, const void* bl
         return fail(e, CAGYM_E_INVALID, "cagym_restore: the blob's layout is not this handle's (n_worlds, max_agents, n_scenarios, max_obstacles, "
                                         "cagym_ig_init done or not, magic and version must all match)");
     if (int rc = refuse_other_timeline(e, "cagym_restore")) return rc;
+    if (int rc = refuse_iglog_timeline(e, "cagym_restore")) return rc;
     ON_DEVICE_VOIDS_BEGUN(e);
     return snap_launch(e, snap_state_table(e, SNAP_SCATTER), rows, nullptr, const_cast<void*>(blob), n, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2257,6 +2347,8 @@ int cagym_fork(void* env, const int32_t* src, const int32_t* dst, int n, void* s
     if (e->cfg.n_scenarios % e->cfg.n_worlds != 0)
         return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork needs n_scenarios to be a multiple of n_worlds: otherwise two worlds can share a scenario "
                                             "slot and the copy of src's slot over dst's could hit a third world");
+    // (in front of the refusal after cagym_ig_init, which every handle that holds this log would meet: CAGYM_E_STATE names the log)
+    if (int rc = refuse_iglog_timeline(e, "cagym_fork")) return rc;
     if (e->ig_ready) return fail(e, CAGYM_E_UNSUPPORTED, "cagym_fork after cagym_ig_init: the per-slot distance field is not copied");
     ON_DEVICE_VOIDS_BEGUN(e);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -6,6 +6,7 @@ policies/pydecmcts/DecMCTS.py:233-271).  Visibility sets are [.., 60] int64 tens
 <=> belief cell (i, j)); the tree bookkeeping (UCT select / expand / back-propagate) stays with the caller.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -218,6 +219,32 @@ def belief_window_spec(belief, mi, poses, G, rotate):
     out[:, 1] = np.where(inside, mi[jc, ic], 0.0).astype(np.float32)
     out[:, 2] = inside.astype(np.float32)
     return out, i, j, qx, qy
+
+
+def episode_log_spec(belief, target_xy, odds_found):
+    """The belief columns of the IG team's episode log (cagym_ig_episode_log_update) in plain numpy - the executable statement of
+    what a row holds.  belief [60, 60] f64 odds ratios of one world, indexed [j, i] (j along y); target_xy [T, 2] f64 target
+    positions; odds_found: the threshold p_found / (1 - p_found), the double the library was given.  Returns a dict:
+      "entropy": sum over the cells of -(P ln P + (1 - P) ln(1 - P)), P = r / (r + 1), in nats (a side whose P or 1 - P is 0 in
+          fp64 contributes its limit, 0);
+      "residual_mi": sum over the cells of cell_mi(r);
+      "n_touched": cells whose odds differ from the prior 1.0;
+      "found" [T] bool: the odds of the cell that holds the target, i = floor((x + 15) / 0.5), j likewise of y, are >= odds_found
+          (False for a target outside the map); "cell" [T, 2] int64 those (i, j).
+    The two sums agree with the library's up to the last bits of the logarithms and the order of the additions."""
+    belief = np.asarray(belief, dtype=np.float64).reshape(60, 60)
+    xy = np.asarray(target_xy, dtype=np.float64).reshape(-1, 2)
+    p = belief / (belief + 1)
+    q = 1 - p
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = -(np.where(p > 0, p * np.log(p), 0.0) + np.where(q > 0, q * np.log(q), 0.0))
+    cell = np.floor((xy + 15.0) / 0.5).astype(np.int64)
+    inside = ((cell >= 0) & (cell < 60)).all(axis=1)
+    c = np.clip(cell, 0, 59)
+    found = inside & (belief[c[:, 1], c[:, 0]] >= float(odds_found))
+    # (math.fsum: the correctly rounded sum, whatever the order)
+    return {"entropy": math.fsum(h.ravel()), "residual_mi": math.fsum(cell_mi(belief).ravel()), "n_touched": int((belief != 1.0).sum()),
+            "found": found, "cell": cell}
 
 
 def cell_mi(r):

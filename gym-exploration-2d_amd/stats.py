@@ -121,3 +121,58 @@ def suite_statistics(records, first=0, count=None, include=None):
                                                                                          device=extra.device)
     return {"n_cases": n_cases, "n_run": int(run.sum()), "pct_collision": 100.0 * float(coll.sum()) / n_cases,
             "pct_stuck": 100.0 * float(stuck.sum()) / n_cases, "clean": clean, "extra_time_pctls": pct}
+
+
+# ---- a target search's table from the IG team's episode log (env.ig_episode_log()) --------------------------------------------------
+BELIEF_CELLS = 3600  # the 60 x 60 belief grid of a world
+
+
+def exploration_statistics(rows):
+    """One policy's summary of BatchedCollisionAvoidanceEnv.ig_episode_log() (torch tensors, on the device they live on; every row
+    is a finished team episode):
+      episodes; mean_return, median_return of `ret`;
+      found_share = sum(n_found) / sum(n_targets) (NaN when the log holds no target);
+      all_found_share: the share of episodes that found every one of their targets;
+      found_at_pctls: the 50 / 75 / 90th percentiles (linear interpolation) of found_at over the found targets, in steps (NaN
+        when nothing was found);
+      mean_entropy (nats) and mean_touched = mean of n_touched / 3600, of the beliefs the episodes ended on.
+    An empty log gives episodes 0 and NaN everywhere else."""
+    ret = torch.as_tensor(rows["ret"]).to(torch.float64)
+    n = int(ret.shape[0])
+    nan = float("nan")
+    dev = ret.device
+    fa = torch.as_tensor(rows["found_at"]).to(dev)
+    found = fa[fa >= 0].to(torch.float64)
+    q = torch.tensor([0.5, 0.75, 0.9], dtype=torch.float64, device=dev)
+    pct = torch.quantile(found, q, interpolation="linear") if found.numel() else torch.full((3,), nan, dtype=torch.float64, device=dev)
+    if n == 0:
+        return {"episodes": 0, "mean_return": nan, "median_return": nan, "found_share": nan, "all_found_share": nan,
+                "found_at_pctls": pct, "mean_entropy": nan, "mean_touched": nan}
+    n_t, n_f = torch.as_tensor(rows["n_targets"]).to(torch.int64), torch.as_tensor(rows["n_found"]).to(torch.int64)
+    targets = int(n_t.sum())
+    return {"episodes": n, "mean_return": float(ret.mean()), "median_return": float(torch.quantile(ret, 0.5, interpolation="linear")),
+            "found_share": float(n_f.sum()) / targets if targets else nan, "all_found_share": float((n_f == n_t).sum()) / n,
+            "found_at_pctls": pct, "mean_entropy": float(torch.as_tensor(rows["entropy"]).to(torch.float64).mean()),
+            "mean_touched": float(torch.as_tensor(rows["n_touched"]).to(torch.float64).mean()) / BELIEF_CELLS}
+
+
+def paired_by_key(a, b):
+    """The inner join of two episode logs on `key`: (ia, ib), two int64 index tensors of equal length with a["key"][ia] ==
+    b["key"][ib], ordered by key.  Two handles on one stream seed meet the same world under the same key whatever drives them, so
+    a["ret"][ia] - b["ret"][ib] is the paired return difference, episode by episode.  A key that a log holds more than once (a ring
+    that wrapped past 2^32 episodes) is paired by its first row."""
+    ka, kb = torch.as_tensor(a["key"]).to(torch.int64), torch.as_tensor(b["key"]).to(torch.int64).to(torch.as_tensor(a["key"]).device)
+    sa, oa = torch.sort(ka, stable=True)
+    sb, ob = torch.sort(kb, stable=True)
+    first_a = torch.ones_like(sa, dtype=torch.bool)
+    first_a[1:] = sa[1:] != sa[:-1]
+    sa, oa = sa[first_a], oa[first_a]
+    first_b = torch.ones_like(sb, dtype=torch.bool)
+    first_b[1:] = sb[1:] != sb[:-1]
+    sb, ob = sb[first_b], ob[first_b]
+    if sa.numel() == 0 or sb.numel() == 0:
+        e = torch.zeros((0,), dtype=torch.int64, device=ka.device)
+        return e, e.clone()
+    at = torch.searchsorted(sb, sa).clamp(max=sb.numel() - 1)
+    hit = sb[at] == sa
+    return oa[hit], ob[at[hit]]

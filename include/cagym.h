@@ -617,6 +617,60 @@ int cagym_episode_log_update(void* env, const uint8_t* flags, const float* rewar
 int cagym_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream);
 int cagym_episode_log_get(void* env, cagym_episode_log_ptrs* out);
 
+/* ---- Episode log of the information-gathering team: belief and target-search metrics (csrc/cagym_ig_episode_log.h) ---------------
+ * The log above rebuilds its rows from the step's outputs.  What a target search is judged by lives in the belief, and the chain puts
+ * a finished world's belief back to the prior in the launch that folds its return (cagym_ig_observe, cagym_ig_episode_boundary).
+ * This log goes BETWEEN the auto-resetting step and that launch: ONE ROW PER FINISHED TEAM EPISODE in a device ring of `capacity`
+ * rows.  No existing kernel knows of it; a handle that never called init runs none of its code.
+ * Row columns (structure of arrays, L = capacity rows):
+ *   key [L] u32 = (uint32_t)(w + e * N), the stream key of the episode that ended; world, episode [L] i32; slice [L] i64, the index
+ *   of the update call that appended the row, counted since init / clear; steps [L] i32, the env steps of the episode;
+ *   ret [L] f64, the team return: running[w] of cagym_ig_get_episode_stats, plus team_reward[w] when the update is given a
+ *     team-reward pointer - the one fp64 add cagym_ig_episode_boundary makes before it folds, so ret equals, bit for bit, the
+ *     `last` the boundary / observe launch behind the update leaves;
+ *   n_targets, n_found [L] i32 and found_at [L,M] i32 per agent slot: -2 the slot is no target, -1 a target never found, else the
+ *     1-based step of the episode at which the log first saw it found (below);
+ *   entropy [L] f64 = the sum over the 3600 belief cells of -(P ln P + (1 - P) ln(1 - P)), P = r / (r + 1), r the cell's odds, in
+ *     nats (a side whose P or 1 - P has reached 0 in fp64 contributes its limit, 0); residual_mi [L] f64 = the sum of the cells'
+ *     cached mutual information (what is left to gain); n_touched [L] i32 = the cells whose odds differ from the prior 1.0.
+ *     The three sums run in a fixed order: equal from run to run and between two handles that hold the same belief.
+ * Running, per world: steps_run [N] i32, found_run [N,M] i32 (-1 or the step), cursor [N] i32; head, one u64 word: rows ever
+ *   appended since init / clear; desync, one i32 word.
+ * TARGETS: the STATIC agents of the episode's pool slot s = (w + e * N) % S - slot i with policy[s][i] == CAGYM_POL_STATIC and
+ *   i < n_agents[s], at (agents6[s][i][0], agents6[s][i][1]); they are what cagym_ig_robot_inputs reports as detections.  Target i
+ *   is FOUND at the first update at which belief[w][j][i'] >= odds_found for the cell i' = floor((x + 15) / 0.5), j likewise of y
+ *   (the indexing of cagym_ig_update_belief); a target outside the map is never found.  found_run = steps_run then: exactly that
+ *   many belief updates of the episode have been applied, whether a planner updates before its move or a learner's
+ *   cagym_ig_observe behind the previous step (or behind the reset).
+ * ORDER as the log's above: the rows of one update are appended in ascending world order, updates in call order, row number i lives
+ *   at ring index i % capacity; an update that finishes more than `capacity` episodes writes its last `capacity` rows.
+ * cagym_ig_episode_log_init: allocate (the running values once, the ring once per capacity) and clear; a second call clears again
+ *   and may change capacity (that synchronises the device and frees the old ring) and odds_found = p / (1 - p), divided by the caller.
+ * cagym_ig_episode_log_update: two launches chained by stream order (one workgroup that decides every world's row number by an
+ *   exclusive count of the finished worlds before it and is the single writer of head and desync; one workgroup per world), no
+ *   atomics, no host synchronisation.  CONTRACT: once per cagym_step_autoreset, behind it, with the game_over [N] it wrote, and
+ *   BEFORE the cagym_ig_observe / cagym_ig_episode_boundary of that step and before cagym_stream_refill (which regenerates the slot of
+ *   the episode that ended).  team_reward [N] f64 DEVICE or NULL: the pointer that boundary launch gets.  For a finished world
+ *   (game_over[w] != 0) the handle's episode index must have advanced by one past the log's cursor, for any other world it must
+ *   equal it; a world where it does not - a skipped or doubled update, a step without auto-reset - counts into desync, logs
+ *   nothing in that call and takes the handle's episode index.  A world that lapped its ring inside a roll-out logs the scenario
+ *   that really ran under the key it should have met (cagym_stream_get's n_lapped tells).
+ * cagym_ig_episode_log_restart: the masked worlds (DEVICE [N] u8, NULL = all) forget the episode in progress and take the handle's
+ *   episode index; clear_rows != 0 also zeroes every row, head, the call counter and desync.  A successful cagym_reset enqueues it
+ *   for its mask, a new pool for every world (rows kept), as for the log above.
+ * cagym_ig_episode_log_get: zero-copy DEVICE views (cagym_ig_episode_log_ptrs, defined in include/cagym_ig_episode_log.h).
+ * The log is in no snapshot and no checkpoint.  While it is initialised cagym_restore and cagym_fork return CAGYM_E_STATE (its
+ * running values would describe another timeline): cagym_restore behind every other refusal it makes, cagym_fork behind every other
+ * but its CAGYM_E_UNSUPPORTED after cagym_ig_init, which every handle that holds this log would meet.
+ * Errors: CAGYM_E_INVALID for a NULL env; CAGYM_E_STATE before cagym_ig_init, and for update / restart / get before init;
+ * CAGYM_E_INVALID for capacity < 1, a non-finite or non-positive odds_found, a NULL game_over or out; CAGYM_E_DEVICE as every
+ * launching entry. */
+typedef struct cagym_ig_episode_log_ptrs cagym_ig_episode_log_ptrs;
+int cagym_ig_episode_log_init(void* env, int capacity, double odds_found, void* stream);
+int cagym_ig_episode_log_update(void* env, const uint8_t* game_over, const double* team_reward, void* stream);
+int cagym_ig_episode_log_restart(void* env, const uint8_t* world_mask, int clear_rows, void* stream);
+int cagym_ig_episode_log_get(void* env, cagym_ig_episode_log_ptrs* out);
+
 /* ---- Per-world state snapshot, restore and fork (csrc/cagym_snapshot.h) -------------------------------------------------------------
  * The env can be put back where it was (checkpoint / resume, rewind) and a world can continue as a copy of another one (look-ahead:
  * "try these K actions from this state").  One copy kernel beside the step kernels; no step, reset or roll-out kernel knows of it.
