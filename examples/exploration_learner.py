@@ -7,7 +7,10 @@ Two handles run on the same seed, hence on the same sequence of worlds: a "learn
 where a policy network would read the flat observation and the window - and the built-in ig_greedy baseline.  The script prints
 both mean episode returns from ig_episode_stats().
 
-    python examples/exploration_learner.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--window 24]
+--context adds the second image in the same frame, infos["context_window"] [N, R, 3, G, G]: obstacle clearance (what the built-in
+planners' feasibility test reads), the other moving agents and the cells the team's sensors covered in this update.
+
+    python examples/exploration_learner.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--window 24] [--context]
 """
 import argparse
 import importlib
@@ -47,11 +50,12 @@ def main():
     ap.add_argument("--window", type=int, default=24, help="cells per side of a robot's belief window (even, 4..64)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--pref-speed", type=float, default=10.0, help="sets the robots' time limit 3 (|p - g| - 0.75) / pref_speed")
+    ap.add_argument("--context", action="store_true", help="also keep infos['context_window']: clearance, agents, seen-now")
     a = ap.parse_args()
 
     # the learner: a VecEnv whose infos carry the windows beside the flat observation
     env, M = make(a)
-    env.attach_ig_learner(window=a.window, rotate=True)
+    env.attach_ig_learner(window=a.window, rotate=True, context=a.context)
     v = vec.CagymVecEnv(env, ["dist_to_goal", "heading_ego_frame", "other_agents_states"])
     obs = v.reset()
     gen = torch.Generator(device=env.device).manual_seed(a.seed)
@@ -66,6 +70,10 @@ def main():
     win = infos["belief_window"]
     print("learner    obs %s  belief_window %s  inside-map share %.3f  reward seen %.3f" % (
         tuple(obs.shape), tuple(win.shape), float(win[:, :, 2].mean()), seen))
+    if a.context:
+        ctx = infos["context_window"]
+        print("learner    context_window %s  mean clearance %.3f  seen-now share %.3f" % (
+            tuple(ctx.shape), float(ctx[:, :, 0].mean()), float(ctx[:, :, 2].mean())))
     report("random", env)
     env.close()
 

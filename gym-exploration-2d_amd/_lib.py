@@ -141,6 +141,14 @@ class IgObserveParams(C.Structure):
 
 IG_OBSERVE_ONLY_RESTARTED = 4  # CAGYM_IG_OBSERVE_ONLY_RESTARTED
 
+
+class IgContextParams(C.Structure):
+    """cagym_ig_context_params (include/cagym_ig_context.h; not in STRUCTS, as IgObserveParams)."""
+    _fields_ = [("n_robots", C.c_int32), ("window", C.c_int32), ("rotate", C.c_int32), ("flags", C.c_uint32), ("clear_max", C.c_double)]
+
+
+IG_CONTEXT_ONLY_MASKED = 1  # CAGYM_IG_CONTEXT_ONLY_MASKED
+
 # cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
 IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
                 ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
@@ -239,6 +247,7 @@ _ARGTYPES = {
     "cagym_ig_episode_boundary": [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_size_t, _vp],
     "cagym_ig_greedy_plan": [_vp, _P(GreedyParams), _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_observe": [_vp, _P(IgObserveParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_context_window": [_vp, _P(IgContextParams), _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],
     "cagym_dmcts_plan": [_vp, _P(DmctsParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     "cagym_episode_records_init": [_vp, _int, _vp],

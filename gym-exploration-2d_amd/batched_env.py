@@ -23,7 +23,7 @@ from ._pool import _PoolMixin
 from ._snapshot import _SNAP_OUT, EnvSnapshot, _SnapshotMixin  # noqa: F401  (EnvSnapshot and _SNAP_OUT are re-exported)
 from .dmcts import DeviceDecMCTSPlanner
 from .ga3c import GA3CCADRLPolicy
-from .ig import EPISODE_FOLD, OBSERVE_ONLY_RESTARTED, GreedyPlanner, InfoGain
+from .ig import CONTEXT_ONLY_MASKED, EPISODE_FOLD, OBSERVE_ONLY_RESTARTED, GreedyPlanner, InfoGain
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> hipStream_t as an int
 
@@ -31,7 +31,8 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device in
 class _IgState(object):
     """What step() needs of an attached IG policy, whichever it is: the primitives, the planner and the robots' input buffers."""
     __slots__ = ("kind", "ig", "R", "range", "episodic", "poses", "det", "n_det", "world", "planner",
-                 "window", "rotate", "team_reward", "gain", "observed", "belief_window")  # (second row: attach_ig_learner's)
+                 "window", "rotate", "team_reward", "gain", "observed", "belief_window",  # (second row: attach_ig_learner's,
+                 "context_window", "clear_max")  # third: its context=True)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -235,7 +236,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         return self._attach_ig("ig_greedy", detect_fov, detect_range, 1, episodic,
                                lambda g: GreedyPlanner(g.ig, g.R, radius=radius, coordinate=coordinate))
 
-    def attach_ig_learner(self, detect_fov=60.0, detect_range=5.0, window=24, rotate=True):
+    def attach_ig_learner(self, detect_fov=60.0, detect_range=5.0, window=24, rotate=True, context=False, clear_max=3.0):
         """From now on the IG robots are the CALLER's to move - their rows of step()'s `actions` are their (v, omega), as for any
         externally driven agent - and the env keeps what a learner needs around them: one belief per world, the team's MI reward,
         the episode accumulators of ig_episode_stats(), and the belief as each robot sees it.  Every step() and reset() is followed,
@@ -254,8 +255,17 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         entries of the four tensors as they were.  Call reset() after attaching.  With attach_ga3c the GA3C agents' rows are the
         network's and every other row, the robots' included, the caller's.  Replaces attach_ig_mcts / attach_ig_greedy and is
         replaced by them; detach_ig_mcts() clears it.  rollout() is refused (it takes no external actions), and so is whatever an
-        attached planner refuses: snapshot / restore / fork, checkpoint, terminal observations, the trajectory ring, the split step."""
+        attached planner refuses: snapshot / restore / fork, checkpoint, terminal observations, the trajectory ring, the split step.
+        context=True adds a second image in the same frame and on the same sample points, written by one more launch directly
+        behind the observe launch (cagym_ig_context_window, with the same mask: a world the observe skips keeps its bytes here too):
+          "context_window" [N, R, 3, window, window] f32 - what the built-in planners use and the belief does not show: the
+              clearance min(EDF, clear_max) / clear_max of the world's current map (0 outside it), the other moving agents (1.0 a
+              teammate's cell, 0.5 any other non-static agent's; the targets stay hidden) and 1 on the cells the team's sensors
+              covered in this update, i.e. "observed" in the window's frame (ig.context_window_spec states the three channels).
+        With the default context=False nothing is allocated, no launch runs and info has no such key."""
         window = int(window)
+        if context and not (float(clear_max) > 0.0 and np.isfinite(float(clear_max))):
+            raise ValueError("attach_ig_learner: clear_max must be finite and positive, got %r" % (clear_max,))
         if window < 4 or window > 64 or window % 2:
             raise ValueError("attach_ig_learner: window must be even and within 4..64, got %d" % window)
         if self._n_ig is not None and self._n_ig > 8:
@@ -267,12 +277,18 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         g.gain = torch.zeros((N,), dtype=torch.float64, device=dev)
         g.observed = torch.zeros((N, 60), dtype=torch.int64, device=dev)
         g.belief_window = torch.zeros((N, g.R, 3, window, window), dtype=torch.float32, device=dev)
+        g.context_window, g.clear_max = None, float(clear_max)
+        if context:
+            g.context_window = torch.zeros((N, g.R, 3, window, window), dtype=torch.float32, device=dev)
         self.team_reward = g.team_reward
         return g.ig
 
     def _ig_observe(self, restart_mask, flags):
         g = self._igm
         g.ig.observe(g.R, g.range, self.obs_oas, g.window, g.rotate, restart_mask, flags, g.team_reward, g.gain, g.observed, g.belief_window)
+        if g.context_window is not None:  # the second image, of the worlds the observe launch just wrote and of no other
+            g.ig.context_window(g.R, g.context_window, g.window, g.rotate, g.clear_max, g.observed, restart_mask,
+                                CONTEXT_ONLY_MASKED if flags & OBSERVE_ONLY_RESTARTED else 0)
 
     def detach_ig_mcts(self):
         self._igm = None
@@ -344,7 +360,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read.  With attach_ig_learner the robots' rows are the learner's (v, omega), and info also carries
-        "belief_window", "gain" and "observed" of the state the step left."""
+        "belief_window", "gain" and "observed" of the state the step left, and with context=True "context_window"."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
             raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
@@ -357,6 +373,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         g = self._igm
         if g is not None and g.kind == "ig_learner":
             info.update(belief_window=g.belief_window, gain=g.gain, observed=g.observed)
+            if g.context_window is not None:
+                info["context_window"] = g.context_window
         if auto_reset and self._term is not None:
             info["terminal"] = dict(self._term, valid=self.game_over)
         return self._obs(), self.reward, self.game_over, info

@@ -11,6 +11,7 @@
 
 #include "../../include/cagym.h"
 #include "../../include/cagym_ig_observe.h"
+#include "../../include/cagym_ig_context.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -29,6 +30,7 @@
 #include "cagym_ig_episode.h"
 #include "cagym_ig_greedy.h"
 #include "cagym_ig_observe.h"
+#include "cagym_ig_context.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2124,6 +2126,28 @@ int cagym_ig_observe(void* env, const cagym_ig_observe_params* params, const flo
     P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.det_range = (float)p.detect_range; P.fov = p.fov_rad; P.range = p.range;
     hipLaunchKernelGGL(k_ig_observe, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G, e->ig_ep,
                        P, obs_oas, restart_mask, team_reward, gain, reinterpret_cast<unsigned long long*>(observed), belief_window);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, const uint64_t* observed, const uint8_t* world_mask,
+                            float* context_window, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_context_window");
+    if (!params || !context_window) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: null argument");
+    const cagym_ig_context_params& p = *params;
+    if (p.n_robots < 1 || p.n_robots > IGC_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: n_robots must be 1..8");
+    if (p.window < 4 || p.window > 64 || (p.window & 1))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: window must be even and within 4..64");
+    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: rotate must be 0 or 1");
+    if (p.flags & ~(uint32_t)CAGYM_IG_CONTEXT_ONLY_MASKED) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: unknown flags");
+    if (!(p.clear_max > 0.0) || !std::isfinite(p.clear_max))  // (the negated comparison refuses NaN)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: clear_max must be finite and positive");
+    if (int rc = ig_robots_check(e, p.n_robots, "cagym_ig_context_window")) return rc;
+    ON_DEVICE(e);
+    IgContextParams P;
+    P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.clear_max = p.clear_max;
+    hipLaunchKernelGGL(k_ig_context_window, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G,
+                       P, reinterpret_cast<const unsigned long long*>(observed), world_mask, context_window);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

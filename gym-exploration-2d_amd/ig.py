@@ -15,6 +15,7 @@ from . import _lib
 
 EPISODE_FOLD, EPISODE_PLANS_ONLY = 1, 2  # CAGYM_IG_EPISODE_* (include/cagym.h)
 OBSERVE_ONLY_RESTARTED = _lib.IG_OBSERVE_ONLY_RESTARTED  # cagym_ig_observe's second flag, beside EPISODE_FOLD
+CONTEXT_ONLY_MASKED = _lib.IG_CONTEXT_ONLY_MASKED  # cagym_ig_context_window's flag
 FOV_DEG60 = 60.0 * np.pi / 180  # detect_fov=60.0 -> targetMap.sensFOV (ig_mcts.py:67)
 PRIMITIVES = np.array([[v, w] for v in (0.0, 2.0, 4.0) for w in (-0.5 * np.pi, 0.0, 0.5 * np.pi)])  # ig_mcts.py:247-253
 GREEDY_V, GREEDY_W = (0.0, 2.0, 4.0), (-np.pi, 0.0, np.pi)  # ig_greedy.py:65-66: candidate c = 3 a + b is (v[a], w[b])
@@ -79,6 +80,16 @@ class InfoGain(object):
         P = _lib.IgObserveParams(int(n_robots), int(window), int(rotate), int(flags), float(detect_range), self.fov, self.range)
         _lib.call(self.L, self.b.h, "cagym_ig_observe", C.byref(P), obs_oas.data_ptr(), _lib.ptr(restart_mask), _lib.ptr(team_reward),
                   _lib.ptr(gain), _lib.ptr(observed), _lib.ptr(belief_window), self.b._stream())
+
+    def context_window(self, n_robots, context_window, window=24, rotate=True, clear_max=3.0, observed=None, world_mask=None, flags=0):
+        """cagym_ig_context_window: ONE launch on the current stream, directly behind observe() - the robots' second image
+        context_window [N,R,3,G,G] f32 (a contiguous device tensor to write into) on the belief window's sample points: clearance
+        min(EDF, clear_max) / clear_max on the world's current scenario slot, the other non-static agents (1.0 a teammate, 0.5
+        anything else) and the cells of `observed` [N,60] i64 (the tensor observe() just wrote, or None: nothing seen).
+        CONTEXT_ONLY_MASKED in flags skips the worlds whose byte of the DEVICE mask world_mask [N] u8 is 0."""
+        P = _lib.IgContextParams(int(n_robots), int(window), int(rotate), int(flags), float(clear_max))
+        _lib.call(self.L, self.b.h, "cagym_ig_context_window", C.byref(P), _lib.ptr(observed), _lib.ptr(world_mask),
+                  context_window.data_ptr(), self.b._stream())
 
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
@@ -245,6 +256,49 @@ def episode_log_spec(belief, target_xy, odds_found):
     # (math.fsum: the correctly rounded sum, whatever the order)
     return {"entropy": math.fsum(h.ravel()), "residual_mi": math.fsum(cell_mi(belief).ravel()), "n_touched": int((belief != 1.0).sum()),
             "found": found, "cell": cell}
+
+
+def context_window_spec(edf, observed, poses, agents_xy, agents_value, G, rotate, clear_max):
+    """The context windows of cagym_ig_context_window in plain numpy - the executable statement of their three channels, on the
+    sample points and source cells of belief_window_spec.  edf: [300, 300] f64 distance field in metres of the world's current
+    scenario slot (InfoGain.edf()[slot]), indexed [row = y, column = x]; observed: [60] integer words of the world (bit i of word
+    j <=> belief cell (i, j)) or None; poses [R, 3] f64 (x, y, heading); agents_xy: per robot k the [n_k, 2] f64 positions of the
+    world's active non-static agents other than robot k itself, agents_value: per robot the matching [n_k] values (1.0 a
+    teammate, 0.5 anything else).  Returns (window [R, 3, G, G] f32, a_s, b_s: per robot the int64 window cells of its agents,
+    fx, fy: their fp64 offsets in its frame).  Channel 0 = min(edf, clear_max) / clear_max inside the map, 0 outside; channel 1 =
+    the largest value among the agents whose cell (a_s, b_s) = floor(f * 2) + G / 2 is the out cell, not masked by the map;
+    channel 2 = 1 where the source cell is inside and in observed.  Every product and sum is a separate fp64 operation in the
+    order written; with rotate the sine and cosine are numpy's, which may differ from the library's in the last bit."""
+    edf = np.asarray(edf, dtype=np.float64)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    R, G, cap = poses.shape[0], int(G), float(clear_max)
+    _, i, j, qx, qy = belief_window_spec(np.ones((60, 60)), np.zeros((60, 60)), poses, G, rotate)
+    inside = (i >= 0) & (i < 60) & (j >= 0) & (j < 60)
+    ic, jc = np.clip(i, 0, 59), np.clip(j, 0, 59)
+    # edfMap.get_edf_value_from_pose: column floor((x + 15) / 0.1), row floor((y + 15) / 0.1); inside the map both lie in 0..299
+    xi = np.clip(np.floor((qx + 15.0) / 0.1), 0, 299).astype(np.int64)
+    yi = np.clip(np.floor((qy + 15.0) / 0.1), 0, 299).astype(np.int64)
+    out = np.zeros((R, 3, G, G), dtype=np.float32)
+    out[:, 0] = np.where(inside, np.minimum(edf[yi, xi], cap) / cap, 0.0).astype(np.float32)
+    if observed is not None:
+        words = np.asarray(observed).astype(np.int64).view(np.uint64).reshape(60)
+        bit = (words[jc] >> ic.astype(np.uint64)) & np.uint64(1)
+        out[:, 2] = (inside & (bit == 1)).astype(np.float32)
+    a_s, b_s, fxs, fys = [], [], [], []
+    for k in range(R):
+        xy = np.asarray(agents_xy[k], dtype=np.float64).reshape(-1, 2)
+        val = np.asarray(agents_value[k], dtype=np.float32).reshape(-1)
+        px, py, th = poses[k]
+        s, cs = (np.sin(th), np.cos(th)) if rotate else (0.0, 1.0)
+        dx, dy = xy[:, 0] - px, xy[:, 1] - py
+        fx = cs * dx + s * dy
+        fy = cs * dy - s * dx
+        a = np.floor(fx * 2.0).astype(np.int64) + G // 2
+        b = np.floor(fy * 2.0).astype(np.int64) + G // 2
+        for n in np.flatnonzero((a >= 0) & (a < G) & (b >= 0) & (b < G)):
+            out[k, 1, a[n], b[n]] = max(out[k, 1, a[n], b[n]], val[n])
+        a_s.append(a), b_s.append(b), fxs.append(fx), fys.append(fy)
+    return out, a_s, b_s, fxs, fys
 
 
 def cell_mi(r):

@@ -112,6 +112,8 @@ class CagymVecEnv(object):
             infos["team_reward"] = b.team_reward
             if "belief_window" in info:  # attach_ig_learner: the robots' belief windows, an image beside the flat observation
                 infos["belief_window"], infos["gain"] = info["belief_window"], info["gain"]
+                if "context_window" in info:  # attach_ig_learner(context=True): the second image, same frame
+                    infos["context_window"] = info["context_window"]
         if self.terminal_observation:
             infos["terminal_observation"] = self.flat(info["terminal"])
         return self.flat(), rews, go.bool(), infos

@@ -502,6 +502,34 @@ typedef struct cagym_ig_observe_params cagym_ig_observe_params;
 int cagym_ig_observe(void* env, const cagym_ig_observe_params* params, const float* obs_oas, const uint8_t* restart_mask,
                      double* team_reward, double* gain, uint64_t* observed, float* belief_window, void* stream);
 
+/* ---- The learner's second image: obstacle clearance, other agents and the cells seen in this update, in the belief window's frame --
+ * The belief window of cagym_ig_observe shows the TARGET belief; the planners the learner is compared with also use the distance
+ * field (they reject a motion whose EDF(next) <= radius + 0.1 and cast their view cones through it).  This call writes, for the same
+ * robots on the same G x G sample points, what the belief window does not hold.  ONE launch on `stream` (one workgroup of 256 threads
+ * per world), to be enqueued directly behind cagym_ig_observe; no host synchronisation, no atomics, barriers only; it changes nothing
+ * of the handle.  params: cagym_ig_context_params, defined in include/cagym_ig_context.h (n_robots 1..8, window = G, rotate, flags,
+ * clear_max).  observed DEVICE [N,60] u64 or NULL: the union cagym_ig_observe just wrote.  world_mask DEVICE [N] u8 or NULL: with
+ * CAGYM_IG_CONTEXT_ONLY_MASKED a world whose mask byte is 0 (every world, for a NULL mask) is skipped - nothing of it is read or
+ * written; without the flag the mask is not looked at.  context_window DEVICE [N,R,3,G,G] f32.
+ * For robot k of world w (the active CAGYM_POL_IGMCTS slots in slot order) at pose (px, py, heading) and out cell (a, b), a forward,
+ * b left (b fastest in memory): the sample (qx, qy), the belief cell (i, j) and (s, cs) are EXACTLY those of belief_window above, and
+ * inside <=> 0 <= i, j < 60.
+ *   channel 0, clearance: inside: (float)(fmin(EDF(qx, qy), clear_max) / clear_max), fp64 until the conversion, EDF the value the
+ *     planners' clearance test reads from the field of the world's CURRENT scenario slot (w + episode[w] * N) % S, row = y, column = x;
+ *     outside: 0.
+ *   channel 1, agents: for every ACTIVE slot t of the world other than robot k's own whose policy is not CAGYM_POL_STATIC (the targets
+ *     stay hidden): dx = px_t - px, dy = py_t - py, fx = cs dx + s dy, fy = cs dy - s dx (fp64, separate products and sums in this
+ *     order), a_t = (int)floor(fx * 2.0) + G/2, b_t = (int)floor(fy * 2.0) + G/2; with both in 0..G-1 cell (a_t, b_t) takes
+ *     max(value, v), v = 1.0 for a CAGYM_POL_IGMCTS slot (a teammate), 0.5 for any other.  Every other cell is 0.  NOT masked by inside.
+ *   channel 2, seen now: 1 where inside and bit i of observed[w][j] is set, else 0; a NULL observed gives 0 everywhere.
+ * Errors: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params / context_window, n_robots outside 1..8, window odd
+ * or outside 4..64, rotate outside {0, 1}, unknown flags, a non-finite or non-positive clear_max; the robot-count errors of
+ * cagym_ig_robot_inputs; CAGYM_E_DEVICE as every launching entry.  A refused call touches nothing. */
+enum { CAGYM_IG_CONTEXT_ONLY_MASKED = 1 }; /* cagym_ig_context_params.flags */
+typedef struct cagym_ig_context_params cagym_ig_context_params;
+int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, const uint64_t* observed, const uint8_t* world_mask,
+                            float* context_window, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
