@@ -35,6 +35,11 @@ class _IgState(object):
                  "context_window", "clear_max")  # third: its context=True)
 
 
+class _IgGoals(object):
+    """attach_ig_goals' state: the parameter block of the three launches and the tensors they keep."""
+    __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice")
+
+
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
 GAME_OVER_MODES = {"agent0": _lib.GO_AGENT0, "all": _lib.GO_ALL, "learning": _lib.GO_LEARNING}
 
@@ -76,6 +81,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         # policies the env drives itself inside step() (attach_ga3c / attach_ig_mcts)
         self._ga3c = None
         self._igm = None
+        self._goals = None        # attach_ig_goals' state, with attach_ig_learner only
         self._act = None          # [N, M, 2] f32 action table of an internal step (the caller's buffer is only read)
         self.team_reward = None   # [N] f64: the team's MI reward of the last step with ig_mcts attached (policy.team_reward)
         self._init_pool()
@@ -158,8 +164,11 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
                 g.ig.reset_belief(None)
                 g.ig.episode_stats["running"].zero_()
                 self._ig_observe(None, 0)
+                if self._goals is not None:  # new maps everywhere: no goal survives
+                    self._goals.out["active"].zero_()
             else:  # a manual restart of the masked worlds alone, inside the launch; not a finished episode, so nothing is folded
                 self._ig_observe(m, OBSERVE_ONLY_RESTARTED)
+            self._ig_goal_status(m)
         elif g is not None and g.episodic and m is not None:
             # a manual restart of the masked worlds only: prior belief, no communicated plans, running team return zeroed; it is
             # not a finished episode, so nothing is folded into the episode statistics (cagym_ig_episode_boundary without FOLD)
@@ -206,7 +215,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         self._refuse_keep("attach_%s" % kind, "an attached IG planner's per-world restart reads the game_over of the auto-resetting launch; "
                           "the three-launch step has not been taken through it")
         R = self._n_ig if self._n_ig is not None else 0
-        self._igm = None
+        self._igm = self._goals = None
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
         N, K, dev = self.N, self.K, self.device
         g = _IgState()
@@ -290,8 +299,80 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             g.ig.context_window(g.R, g.context_window, g.window, g.rotate, g.clear_max, g.observed, restart_mask,
                                 CONTEXT_ONLY_MASKED if flags & OBSERVE_ONLY_RESTARTED else 0)
 
+    def attach_ig_goals(self, radius=0.5, v_max=2.0, w_max=np.pi, align_tol=np.pi / 4, goal_tol=0.25):
+        """Goal actions for the learner's robots (needs attach_ig_learner): from now on a robot may be given a PLACE to go to
+        (ig_set_goals) instead of a (v, omega) per step, and while it holds an active goal step() overwrites its row of the action
+        table with a controller's that descends the goal's geodesic field - the obstacle-aware shortest-path distance on the
+        belief's 60 x 60 grid of 0.5 m cells, a cell free when the distance field at its centre passes the planners' test
+        EDF > radius + 0.1 (ig.geodesic_spec; the controller: ig.goal_action_spec).  The controller turns at up to w_max towards
+        the next cell's centre, drives at v_max once the heading error left after the step's turn is within align_tol, and stops
+        within goal_tol of the goal point.  Robots without an active goal keep the caller's row: a team may mix both.  A world that
+        restarts - under auto-reset, reset() or reset(world_mask=) - loses its robots' goals: its map is gone.  step()'s info gains
+          "goal_distance" [N, R] f32 - the field at the robot's own cell, metres still to go along the grid (+inf: no active goal,
+              outside the map, or the goal cannot be reached), and
+          "goal_reached" [N, R] u8 - 1 when an active goal lies within goal_tol of the robot,
+        both of the state the step left, written by one launch behind the observe launch (cagym_ig_goal_status); one launch in front
+        of the step writes the rows (cagym_ig_goal_actions, on the env's own table: `actions` is only read).  Everything is
+        stream-ordered, nothing synchronises.  Attaching another IG policy, or detach_ig_mcts(), drops the goals."""
+        g = self._igm
+        if g is None or g.kind != "ig_learner":
+            raise RuntimeError("attach_ig_goals needs attach_ig_learner first: the goals drive the learner's robots")
+        for name, val in (("radius", radius), ("v_max", v_max), ("w_max", w_max), ("align_tol", align_tol), ("goal_tol", goal_tol)):
+            if not (float(val) > 0.0 and np.isfinite(float(val))):
+                raise ValueError("attach_ig_goals: %s must be finite and positive, got %r" % (name, val))
+        N, R, dev = self.N, g.R, self.device
+        q = _IgGoals()
+        q.P = g.ig.goal_params(R, g.window, g.rotate, radius, v_max, w_max, align_tol, goal_tol)
+        q.out = {"field": torch.full((N, R, 60, 60), float("inf"), dtype=torch.float32, device=dev),
+                 "goal_xy": torch.zeros((N, R, 2), dtype=torch.float64, device=dev),
+                 "active": torch.zeros((N, R), dtype=torch.uint8, device=dev)}
+        q.goal_distance = torch.full((N, R), float("inf"), dtype=torch.float32, device=dev)
+        q.goal_reached = torch.zeros((N, R), dtype=torch.uint8, device=dev)
+        q.choice = torch.full((N, R), 255, dtype=torch.uint8, device=dev)
+        self._goals = q
+        self._alloc_act()
+
+    def _need_goals(self, what):
+        if self._goals is None:
+            raise RuntimeError("%s needs attach_ig_goals" % what)
+        return self._goals
+
+    def ig_set_goals(self, goals, mask=None, frame="world"):
+        """Give the masked robots (mask [N, R], default: every robot) a goal each, in ONE geodesic launch on the current stream
+        followed by the status launch: goals [N, R, 2], with frame="world" points (x, y) in metres, with frame="window" cells (a, b)
+        of each robot's belief window as the state has it now (a forward, b left - e.g. the argmax of a channel of
+        info["belief_window"]).  A goal that is not finite or lies outside the map leaves its robot without an active goal.  Robots
+        outside the mask keep every byte of their field, goal and active flag."""
+        q = self._need_goals("ig_set_goals")
+        if frame not in ("world", "window"):
+            raise ValueError("ig_set_goals: frame must be 'world' or 'window', got %r" % (frame,))
+        ig = self._igm.ig
+        kw = {"points": goals} if frame == "world" else {"cells": goals}
+        ig.geodesic(mask=mask, radius=q.P.radius, window=q.P.window, rotate=bool(q.P.rotate), out=q.out, **kw)
+        self._ig_goal_status(None)
+
+    def ig_clear_goals(self, mask=None):
+        """Take the goals of the masked robots (mask [N, R], default: every robot) away: their rows are the caller's again."""
+        q = self._need_goals("ig_clear_goals")
+        if mask is None:
+            q.out["active"].zero_()
+        else:
+            q.out["active"].masked_fill_(torch.as_tensor(mask, device=self.device).reshape(self.N, -1).bool(), 0)
+        self._ig_goal_status(None)
+
+    def ig_goals(self):
+        """Zero-copy device views of the goal state: field [N, R, 60, 60] f32 (indexed [j, i]), goal_xy [N, R, 2] f64, active
+        [N, R] u8, goal_distance [N, R] f32, goal_reached [N, R] u8."""
+        q = self._need_goals("ig_goals")
+        return dict(q.out, goal_distance=q.goal_distance, goal_reached=q.goal_reached)
+
+    def _ig_goal_status(self, restart_mask):
+        q = self._goals
+        if q is not None:
+            self._igm.ig.goal_status(q.P, q.out, q.goal_distance, q.goal_reached, restart_mask)
+
     def detach_ig_mcts(self):
-        self._igm = None
+        self._igm = self._goals = None
         self.team_reward = None
 
     def _alloc_act(self):
@@ -315,7 +396,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         table the last step wrote, when that is not self.obs_oas (rollout: slice t - 1)."""
         ga3c = self._drives_ga3c()
         plans = self._igm is not None and self._igm.kind != "ig_learner"  # (a learner's robots are driven by the caller's rows)
-        if not ga3c and not plans:
+        goals = self._goals  # ... or, with attach_ig_goals, by the goal controller's, written over a copy of the caller's table
+        if not ga3c and not plans and goals is None:
             return a
         table = self._act
         if ga3c:
@@ -331,6 +413,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             self.team_reward = g.ig.mi_reward(observed, g.world, out=team_reward_out)  # before the move, as the reference computes it
             planned, _ = g.planner.plan(g.poses)
             g.ig.robot_actions(g.R, planned, table)
+        if goals is not None:
+            self._igm.ig.goal_actions(goals.P, goals.out, table, goals.choice)
         return table
 
     def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None, term=False):
@@ -352,6 +436,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             self._ig_log_update(restart, None if g.kind == "ig_learner" else self.team_reward)
         if g is not None and g.kind == "ig_learner":  # the observation of the state the step left; restarted worlds fold and start anew
             self._ig_observe(restart, EPISODE_FOLD if restart is not None else 0)
+            self._ig_goal_status(restart)  # (attach_ig_goals: the restarted worlds lose their goals)
         elif g is not None and g.episodic:
             g.ig.episode_boundary(g.planner.P, g.planner.workspace, self.team_reward, restart, EPISODE_FOLD)
 
@@ -360,7 +445,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read.  With attach_ig_learner the robots' rows are the learner's (v, omega), and info also carries
-        "belief_window", "gain" and "observed" of the state the step left, and with context=True "context_window"."""
+        "belief_window", "gain" and "observed" of the state the step left, with context=True "context_window", and with
+        attach_ig_goals "goal_distance" and "goal_reached"."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
             raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
@@ -375,6 +461,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             info.update(belief_window=g.belief_window, gain=g.gain, observed=g.observed)
             if g.context_window is not None:
                 info["context_window"] = g.context_window
+            if self._goals is not None:
+                info.update(goal_distance=self._goals.goal_distance, goal_reached=self._goals.goal_reached)
         if auto_reset and self._term is not None:
             info["terminal"] = dict(self._term, valid=self.game_over)
         return self._obs(), self.reward, self.game_over, info

@@ -12,6 +12,7 @@
 #include "../../include/cagym.h"
 #include "../../include/cagym_ig_observe.h"
 #include "../../include/cagym_ig_context.h"
+#include "../../include/cagym_ig_goals.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -31,6 +32,7 @@
 #include "cagym_ig_greedy.h"
 #include "cagym_ig_observe.h"
 #include "cagym_ig_context.h"
+#include "cagym_ig_geodesic.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2148,6 +2150,69 @@ int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, co
     P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.clear_max = p.clear_max;
     hipLaunchKernelGGL(k_ig_context_window, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G,
                        P, reinterpret_cast<const unsigned long long*>(observed), world_mask, context_window);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- goal actions for the learner's robots (csrc/cagym_ig_geodesic.h) -----------------------------------------------------------------
+// The checks of the three entries on their shared parameter block; `name`: the entry, for the message.
+static int ig_goal_params_check(Env* e, const cagym_ig_goal_params* params, const char* name, IgGoalParams* P) {
+    const std::string n(name);
+    if (!params) return fail(e, CAGYM_E_INVALID, n + ": null argument");
+    const cagym_ig_goal_params& p = *params;
+    if (p.n_robots < 1 || p.n_robots > IGG_MAXR) return fail(e, CAGYM_E_INVALID, n + ": n_robots must be 1..8");
+    if (p.window < 4 || p.window > 64 || (p.window & 1)) return fail(e, CAGYM_E_INVALID, n + ": window must be even and within 4..64");
+    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, n + ": rotate must be 0 or 1");
+    if (p.flags) return fail(e, CAGYM_E_INVALID, n + ": unknown flags");
+    const double pos[6] = {p.radius, p.v_max, p.w_max, p.align_tol, p.goal_tol, p.dt};
+    for (double v : pos)
+        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
+            return fail(e, CAGYM_E_INVALID, n + ": radius, v_max, w_max, align_tol, goal_tol and dt must be finite and positive");
+    if (int rc = ig_robots_check(e, p.n_robots, name)) return rc;
+    P->R = p.n_robots; P->G = p.window; P->rotate = p.rotate;
+    P->radius = p.radius; P->v_max = p.v_max; P->w_max = p.w_max; P->align_tol = p.align_tol; P->goal_tol = p.goal_tol; P->dt = p.dt;
+    return CAGYM_OK;
+}
+
+int cagym_ig_geodesic(void* env, const cagym_ig_goal_params* params, const uint8_t* mask, const double* goals_xy, const int32_t* goals_ab,
+                      float* field, double* goal_xy, uint8_t* active, int32_t* sweeps, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_geodesic");
+    if (!field || !goal_xy || !active) return fail(e, CAGYM_E_INVALID, "cagym_ig_geodesic: null argument");
+    if ((goals_xy != nullptr) == (goals_ab != nullptr))
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_geodesic: exactly one of goals_xy and goals_ab must be given");
+    IgGoalParams P;
+    if (int rc = ig_goal_params_check(e, params, "cagym_ig_geodesic", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_geodesic, dim3((unsigned)(e->cfg.n_worlds * P.R)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G,
+                       P, mask, goals_xy, goals_ab, field, goal_xy, active, sweeps);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_goal_actions(void* env, const cagym_ig_goal_params* params, const float* field, const double* goal_xy,
+                          const uint8_t* active, float* actions, uint8_t* choice, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_goal_actions");
+    if (!field || !goal_xy || !active || !actions) return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_actions: null argument");
+    if (reinterpret_cast<uintptr_t>(actions) & 7) return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_actions: actions must be 8-byte aligned");
+    IgGoalParams P;
+    if (int rc = ig_goal_params_check(e, params, "cagym_ig_goal_actions", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_goal_actions, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D, P, field,
+                       goal_xy, active, actions, choice);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_goal_status(void* env, const cagym_ig_goal_params* params, const uint8_t* restart_mask, const float* field,
+                         const double* goal_xy, uint8_t* active, float* goal_distance, uint8_t* goal_reached, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_goal_status");
+    if (!field || !goal_xy || !active || !goal_distance || !goal_reached)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_status: null argument");
+    IgGoalParams P;
+    if (int rc = ig_goal_params_check(e, params, "cagym_ig_goal_status", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_goal_status, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D, P,
+                       restart_mask, field, goal_xy, active, goal_distance, goal_reached);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

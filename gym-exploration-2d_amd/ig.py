@@ -6,6 +6,7 @@ policies/pydecmcts/DecMCTS.py:233-271).  Visibility sets are [.., 60] int64 tens
 <=> belief cell (i, j)); the tree bookkeeping (UCT select / expand / back-propagate) stays with the caller.
 """
 import ctypes as C
+import heapq
 import math
 
 import numpy as np
@@ -90,6 +91,58 @@ class InfoGain(object):
         P = _lib.IgContextParams(int(n_robots), int(window), int(rotate), int(flags), float(clear_max))
         _lib.call(self.L, self.b.h, "cagym_ig_context_window", C.byref(P), _lib.ptr(observed), _lib.ptr(world_mask),
                   context_window.data_ptr(), self.b._stream())
+
+    def goal_params(self, n_robots, window=24, rotate=True, radius=0.5, v_max=2.0, w_max=np.pi, align_tol=np.pi / 4, goal_tol=0.25):
+        """The cagym_ig_goal_params block of geodesic() / goal_actions() / goal_status() (dt is this object's)."""
+        return _lib.IgGoalParams(int(n_robots), int(window), int(rotate), 0, float(radius), float(v_max), float(w_max), float(align_tol),
+                                 float(goal_tol), self.dt)
+
+    def geodesic(self, points=None, cells=None, mask=None, radius=0.5, window=24, rotate=True, out=None):
+        """cagym_ig_geodesic: ONE launch on the current stream, one workgroup per (world, robot) - the obstacle-aware shortest-path
+        distance on the 60 x 60 belief grid FROM a source point per robot, on the world's current map: `points` [N,R,2] f64 in world
+        metres, or `cells` [N,R,2] i32, a cell (a, b) of each robot's belief window (window, rotate: attach_ig_learner's) on the
+        pose the state holds now - exactly one of the two.  mask [N,R] u8 or None (every robot): a robot whose byte is 0 keeps every
+        byte of its outputs.  A cell is free when EDF(centre) > radius + 0.1, the planners' test; ig.geodesic_spec states the rest.
+        With the robots' own positions as sources it tells which candidate goals each robot can reach before one is chosen.
+        Returns the dict of device tensors it wrote: field [N,R,60,60] f32 indexed [j, i] (+inf: blocked or unreachable), goal_xy
+        [N,R,2] f64 the point used, active [N,R] u8 (0: the point is not finite or outside the map; its field is all +inf), sweeps
+        [N,R] i32 the relaxation sweeps run; `out`: such a dict to write into again (default: new tensors)."""
+        if (points is None) == (cells is None):
+            raise ValueError("geodesic: exactly one of points and cells must be given")
+        N, dev = self.b.N, self.b.device
+        if points is not None:
+            src = points if (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()) \
+                else self._t(points, torch.float64)
+        else:
+            src = cells if (torch.is_tensor(cells) and cells.is_cuda and cells.dtype == torch.int32 and cells.is_contiguous()) \
+                else self._t(cells, torch.int32)
+        src = src.reshape(N, -1, 2)
+        R = src.shape[1]
+        if mask is not None:
+            mask = self._t(mask, torch.uint8, (N, R))
+        if out is None:
+            out = {"field": torch.empty((N, R, 60, 60), dtype=torch.float32, device=dev),
+                   "goal_xy": torch.empty((N, R, 2), dtype=torch.float64, device=dev),
+                   "active": torch.empty((N, R), dtype=torch.uint8, device=dev),
+                   "sweeps": torch.empty((N, R), dtype=torch.int32, device=dev)}
+        P = self.goal_params(R, window, rotate, radius)
+        _lib.call(self.L, self.b.h, "cagym_ig_geodesic", C.byref(P), _lib.ptr(mask), _lib.ptr(src if points is not None else None),
+                  _lib.ptr(src if cells is not None else None), out["field"].data_ptr(), out["goal_xy"].data_ptr(),
+                  out["active"].data_ptr(), _lib.ptr(out.get("sweeps")), self.b._stream())
+        return out
+
+    def goal_actions(self, params, goals, actions, choice=None):
+        """cagym_ig_goal_actions: the rows of the robots with an active goal in the action table `actions` [N,M,2] f32 (in place);
+        goals: geodesic()'s dict; choice [N,R] u8 or None: what each robot aims at (0..7 neighbour, 8 the goal point, 255 nothing)."""
+        _lib.call(self.L, self.b.h, "cagym_ig_goal_actions", C.byref(params), goals["field"].data_ptr(), goals["goal_xy"].data_ptr(),
+                  goals["active"].data_ptr(), actions.data_ptr(), _lib.ptr(choice), self.b._stream())
+
+    def goal_status(self, params, goals, goal_distance, goal_reached, restart_mask=None):
+        """cagym_ig_goal_status: behind the step and observe() - active = 0 for the worlds of the DEVICE mask restart_mask [N] u8,
+        then goal_distance [N,R] f32 (the field at the robot's cell) and goal_reached [N,R] u8."""
+        _lib.call(self.L, self.b.h, "cagym_ig_goal_status", C.byref(params), _lib.ptr(restart_mask), goals["field"].data_ptr(),
+                  goals["goal_xy"].data_ptr(), goals["active"].data_ptr(), goal_distance.data_ptr(), goal_reached.data_ptr(),
+                  self.b._stream())
 
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
@@ -299,6 +352,154 @@ def context_window_spec(edf, observed, poses, agents_xy, agents_value, G, rotate
             out[k, 1, a[n], b[n]] = max(out[k, 1, a[n], b[n]], val[n])
         a_s.append(a), b_s.append(b), fxs.append(fx), fys.append(fy)
     return out, a_s, b_s, fxs, fys
+
+
+GEO_ORTHO, GEO_DIAG = np.float32(0.5), np.float32(0.5 * np.sqrt(2.0))  # the move costs of the geodesic field
+# the controller's candidates in order: E, N, W, S, NE, NW, SW, SE as (di, dj), E = +x, N = +y
+GEO_NEIGHBOURS = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))
+
+
+_ATANHI = (4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00)
+_ATANLO = (2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17)
+_AT = (3.33333333333329318027e-01, -1.99999999998764832476e-01, 1.42857142725034663711e-01, -1.11111104054623557880e-01,
+       9.09088713343650656196e-02, -7.69187620504482999495e-02, 6.66107313738753120669e-02, -5.83357013379057348645e-02,
+       4.97687799461593236017e-02, -3.65315727442169155270e-02, 1.62858201153657823623e-02)
+_PI, _PI_LO = 3.1415926535897931160e+00, 1.2246467991473531772e-16
+
+
+def _atan_pos(x):
+    """fdlibm's atan (s_atan.c, public domain constants) for x >= 0, every product, sum and quotient a separate fp64 operation"""
+    if x >= 73786976294838206464.0:  # 2^66
+        return _ATANHI[3] + _ATANLO[3]
+    if x < 0.4375:
+        if x < 1.862645149230957e-09:  # 2^-29
+            return x
+        k = -1
+    elif x < 1.1875:
+        if x < 0.6875:
+            k, x = 0, (2.0 * x - 1.0) / (2.0 + x)
+        else:
+            k, x = 1, (x - 1.0) / (x + 1.0)
+    elif x < 2.4375:
+        k, x = 2, (x - 1.5) / (1.0 + 1.5 * x)
+    else:
+        k, x = 3, -1.0 / x
+    z = x * x
+    w = z * z
+    s1 = z * (_AT[0] + w * (_AT[2] + w * (_AT[4] + w * (_AT[6] + w * (_AT[8] + w * _AT[10])))))
+    s2 = w * (_AT[1] + w * (_AT[3] + w * (_AT[5] + w * (_AT[7] + w * _AT[9]))))
+    if k < 0:
+        return x - x * (s1 + s2)
+    return _ATANHI[k] - ((x * (s1 + s2) - _ATANLO[k]) - x)
+
+
+def atan2_spec(y, x):
+    """The controller's atan2 for finite operands: fdlibm's (e_atan2.c / s_atan.c), restated with nothing but fp64 sums, products
+    and quotients in a fixed order, so that cagym_ig_goal_actions (igg_atan2 in csrc/cagym_ig_geodesic.h, compiled without
+    contraction) and this function return the same double bit for bit; it is within an ulp of the C library's.  The heading error
+    of an aligned robot is a difference of two nearly equal angles: two atan2 that differ in their last bit would give turn rates
+    that differ by their whole size there."""
+    y, x = float(y), float(x)
+    m = (1 if math.copysign(1.0, y) < 0 else 0) + (2 if math.copysign(1.0, x) < 0 else 0)
+    if y == 0.0:
+        return y if m < 2 else (_PI if m == 2 else -_PI)
+    if x == 0.0:
+        return -(_ATANHI[3] + _ATANLO[3]) if m & 1 else _ATANHI[3] + _ATANLO[3]
+    z = _atan_pos(abs(y / x))
+    if m == 0:
+        return z
+    if m == 1:
+        return -z
+    if m == 2:
+        return _PI - (z - _PI_LO)
+    return (z - _PI_LO) - _PI
+
+
+def geodesic_spec(edf, point, radius):
+    """The field of cagym_ig_geodesic in plain numpy with heapq - its bit-exact specification.  edf: [300, 300] f64 distance field
+    in metres of the world's current scenario slot (InfoGain.edf()[slot]), indexed [row = y, column = x]; point: (x, y) in world
+    metres; radius: the robot's.  Returns (field [60, 60] f32 indexed [j, i], free [60, 60] bool, source_cell (si, sj) or None).
+    free[j, i] <=> edf[5 j + 2, 5 i + 2] > radius + 0.1 - the raster cell in the middle of the belief cell - or (i, j) is the
+    source cell si = floor((x + 15) / 0.5), sj likewise of y.  A point that is not finite or whose cell lies outside 0..59 has no
+    source cell: the field is all +inf.  Otherwise field[sj, si] = 0 and a Dijkstra search relaxes v from u with
+    np.float32(field[u] + cost), cost GEO_ORTHO for an orthogonal and GEO_DIAG for a diagonal move, v free, and for a diagonal both
+    orthogonal cells it passes between free.  fp32 addition is monotone and the costs are positive, so this is the unique fixed
+    point of field[v] = min over allowed u of fl32(field[u] + cost), whatever order a relaxation reaches it in."""
+    edf = np.asarray(edf, dtype=np.float64)
+    x, y = float(point[0]), float(point[1])
+    field = np.full((60, 60), np.inf, dtype=np.float32)
+    free = edf[2::5, 2::5] > float(radius) + 0.1
+    if not (np.isfinite(x) and np.isfinite(y)):
+        return field, free, None
+    si, sj = int(math.floor((x + 15.0) / 0.5)), int(math.floor((y + 15.0) / 0.5))
+    if not (0 <= si < 60 and 0 <= sj < 60):
+        return field, free, None
+    free = free.copy()
+    free[sj, si] = True
+    field[sj, si] = 0.0
+    heap = [(0.0, sj, si)]
+    while heap:
+        d, j, i = heapq.heappop(heap)
+        if d > field[j, i]:
+            continue
+        for k, (di, dj) in enumerate(GEO_NEIGHBOURS):
+            ni, nj = i + di, j + dj
+            if not (0 <= ni < 60 and 0 <= nj < 60 and free[nj, ni]):
+                continue
+            if k >= 4 and not (free[j, ni] and free[nj, i]):
+                continue
+            nd = np.float32(field[j, i] + (GEO_ORTHO if k < 4 else GEO_DIAG))
+            if nd < field[nj, ni]:
+                field[nj, ni] = nd
+                heapq.heappush(heap, (float(nd), nj, ni))
+    return field, free, (si, sj)
+
+
+def goal_action_spec(field, pose, goal_xy, dt, v_max, w_max, align_tol, goal_tol):
+    """The controller of cagym_ig_goal_actions for one robot with an active goal, in plain numpy fp64 - its specification.  field
+    [60, 60] f32 indexed [j, i] (geodesic_spec's), pose (x, y, heading), goal_xy the goal point.  Returns (v, omega, chosen_cell,
+    reached): the fp64 action (the library stores (float)v, (float)omega), the cell (i, j) aimed at - a neighbour, or the own
+    cell when the aim is the goal point itself, None when the action is (0, 0) - and dist <= goal_tol.
+      own cell (ci, cj) = floor((x + 15) / 0.5), floor((y + 15) / 0.5); outside the map: (0, 0).  dist = sqrt(dx dx + dy dy) to the
+      goal; reached: (0, 0).  Own cell == the goal's cell: aim at the goal point.  Else the neighbour with the smallest key
+      np.float32(field[n] + cost) among GEO_NEIGHBOURS in order (the first of equal keys), finite field values only, a diagonal
+      while the own value is finite only with both orthogonal neighbours finite; none: (0, 0); aim at its centre.
+      err = wrap(atan2_spec(ay - y, ax - x) - heading), wrap(a) = (a + pi) % (2 pi) - pi; omega = clip(err / dt, -w_max, w_max);
+      rem = err - omega dt; v = 0 when |rem| > align_tol, else v_max, or min(v_max, dist / dt) when the aim is the goal point."""
+    field = np.asarray(field, dtype=np.float32).reshape(60, 60)
+    x, y, th = (float(v) for v in pose)
+    gx, gy = float(goal_xy[0]), float(goal_xy[1])
+    ci, cj = int(math.floor((x + 15.0) / 0.5)), int(math.floor((y + 15.0) / 0.5))
+    dx, dy = gx - x, gy - y
+    dist = math.sqrt(dx * dx + dy * dy)
+    reached = dist <= goal_tol
+    if not (0 <= ci < 60 and 0 <= cj < 60) or reached:
+        return 0.0, 0.0, None, reached
+    at = lambda i, j: field[j, i] if (0 <= i < 60 and 0 <= j < 60) else np.float32(np.inf)
+    to_goal = (ci, cj) == (int(math.floor((gx + 15.0) / 0.5)), int(math.floor((gy + 15.0) / 0.5)))
+    if to_goal:
+        ax, ay, cell = gx, gy, (ci, cj)
+    else:
+        own, best, cell = np.isfinite(field[cj, ci]), np.float32(np.inf), None
+        for k, (di, dj) in enumerate(GEO_NEIGHBOURS):
+            val = at(ci + di, cj + dj)
+            if not np.isfinite(val):
+                continue
+            if k >= 4 and own and not (np.isfinite(at(ci + di, cj)) and np.isfinite(at(ci, cj + dj))):
+                continue
+            key = np.float32(val + (GEO_ORTHO if k < 4 else GEO_DIAG))
+            if key < best:
+                best, cell = key, (ci + di, cj + dj)
+        if cell is None:
+            return 0.0, 0.0, None, reached
+        ax, ay = cell[0] * 0.5 - 15.0 + 0.25, cell[1] * 0.5 - 15.0 + 0.25
+    err = (atan2_spec(ay - y, ax - x) - th + np.pi) % (2 * np.pi) - np.pi
+    omega = min(max(err / dt, -w_max), w_max)
+    rem = err - omega * dt
+    v = 0.0
+    if not abs(rem) > align_tol:
+        v = min(v_max, dist / dt) if to_goal else float(v_max)
+    return float(v), float(omega), cell, reached
 
 
 def cell_mi(r):

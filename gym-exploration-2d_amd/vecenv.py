@@ -114,6 +114,8 @@ class CagymVecEnv(object):
                 infos["belief_window"], infos["gain"] = info["belief_window"], info["gain"]
                 if "context_window" in info:  # attach_ig_learner(context=True): the second image, same frame
                     infos["context_window"] = info["context_window"]
+                if "goal_distance" in info:  # attach_ig_goals: metres to go along the grid, and goal reached
+                    infos["goal_distance"], infos["goal_reached"] = info["goal_distance"], info["goal_reached"]
         if self.terminal_observation:
             infos["terminal_observation"] = self.flat(info["terminal"])
         return self.flat(), rews, go.bool(), infos

@@ -530,6 +530,54 @@ typedef struct cagym_ig_context_params cagym_ig_context_params;
 int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, const uint64_t* observed, const uint8_t* world_mask,
                             float* context_window, void* stream);
 
+/* ---- Goal actions for the learner's robots: geodesic distance fields on the belief grid and a controller that descends them -------
+ * A learner may choose a PLACE for a robot - a world point, or a cell of the belief window it is handed - instead of a (v, omega)
+ * per step.  Three launches on `stream`, no host synchronisation, no global atomics, barriers only.  params of all three:
+ * cagym_ig_goal_params, defined in include/cagym_ig_goals.h (n_robots = R 1..8, window = G, rotate, flags = 0, radius, v_max, w_max,
+ * align_tol, goal_tol, dt); every call validates the whole block.  The robots of world w are its active CAGYM_POL_IGMCTS slots in
+ * slot order; cells are those of the belief: i = floor((x + 15) / 0.5), j likewise of y, inside <=> both in 0..59.
+ *
+ * cagym_ig_geodesic: one workgroup of 256 threads per (world, robot); mask DEVICE [N,R] u8 or NULL (= every robot): a robot whose
+ * byte is 0 is skipped, nothing of it is read or written.  Exactly one of goals_xy DEVICE [N,R,2] f64 (world metres) and goals_ab
+ * DEVICE [N,R,2] i32 is non-NULL; a cell (a, b) of the robot's belief window becomes its sample point (qx, qy) of cagym_ig_observe
+ * above, on the pose the state holds now.  Outputs, DEVICE: goal_xy [N,R,2] f64 the point used; active [N,R] u8 = the point is
+ * finite and its cell (si, sj) inside; field [N,R,60,60] f32 indexed [j, i]; sweeps [N,R] i32 or NULL, the relaxation sweeps run.
+ *   free[j, i] <=> sqrt((double)d2[5 j + 2][5 i + 2]) * 0.1 > radius + 0.1 on the field of the world's CURRENT scenario slot (the
+ *     value the planners' clearance test reads at the cell's centre), or (i, j) is the source cell.
+ *   field[sj, si] = 0; every other free cell holds min over its allowed neighbours u of fl32(field[u] + cost), cost 0.5f for an
+ *     orthogonal and (float)(0.5 * sqrt(2.0)) for a diagonal neighbour, a diagonal allowed only when both orthogonal cells it passes
+ *     between are free; blocked and unreached cells hold +inf.  The fixed point is unique (fp32 addition is monotone, costs are
+ *     positive): it is a Dijkstra's result with the same additions, bit for bit.  active = 0 gives an all-inf row.
+ *
+ * cagym_ig_goal_actions: before the step.  For every robot with active != 0 its row of actions [N,M,2] f32 (8-byte aligned) becomes
+ * ((float)v, (float)omega); every other row stays the caller's.  fp64, separate operations: (x, y, heading) the robot's pose, (ci, cj)
+ * its cell, dist = sqrt(dx dx + dy dy) to the goal point.
+ *   (0, 0) when the own cell is outside, when dist <= goal_tol, or when no candidate below exists.
+ *   aim = the goal point when the own cell is the goal's; else the centre of the neighbour cell with the smallest key
+ *     fl32(field[n] + cost(n)) among E, N, W, S, NE, NW, SW, SE (E = +x, N = +y; the first of equal keys wins) whose field value is
+ *     finite and, for a diagonal while the own cell's value is finite, whose two orthogonal neighbours' values are finite too.
+ *   err = wrap(atan2(ay - y, ax - x) - heading), wrap(a) = fmod(a + pi, 2 pi) made non-negative, - pi; omega = clamp(err / dt, +-w_max);
+ *   atan2 is fdlibm's, evaluated as separate fp64 operations in a fixed order (ig.atan2_spec returns the same double bit for bit);
+ *   rem = err - omega dt; v = 0 when |rem| > align_tol, else v_max, or fmin(v_max, dist / dt) when the aim is the goal point.
+ *   choice DEVICE [N,R] u8 or NULL: what every robot aims at - 0..7 the neighbour in candidate order, 8 the goal point, 255 nothing
+ *   (no active goal, or one of the (0, 0) cases).
+ *
+ * cagym_ig_goal_status: behind the step and cagym_ig_observe.  restart_mask DEVICE [N] u8 or NULL: the robots of a world whose byte
+ * is set get active = 0.  Then for every robot goal_distance [N,R] f32 = the field at its own cell (+inf when inactive or outside) and
+ * goal_reached [N,R] u8 = active and sqrt(dx dx + dy dy) <= goal_tol.
+ *
+ * Errors, all three, before the handle is touched: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params, field,
+ * goal_xy or active (or actions; goal_distance, goal_reached), n_robots outside 1..8, window odd or outside 4..64, rotate outside
+ * {0, 1}, flags != 0, a radius, v_max, w_max, align_tol, goal_tol or dt that is not finite or not positive, both or neither of
+ * goals_xy / goals_ab; the robot-count errors of cagym_ig_robot_inputs; CAGYM_E_DEVICE as every launching entry. */
+typedef struct cagym_ig_goal_params cagym_ig_goal_params;
+int cagym_ig_geodesic(void* env, const cagym_ig_goal_params* params, const uint8_t* mask, const double* goals_xy, const int32_t* goals_ab,
+                      float* field, double* goal_xy, uint8_t* active, int32_t* sweeps, void* stream);
+int cagym_ig_goal_actions(void* env, const cagym_ig_goal_params* params, const float* field, const double* goal_xy,
+                          const uint8_t* active, float* actions, uint8_t* choice, void* stream);
+int cagym_ig_goal_status(void* env, const cagym_ig_goal_params* params, const uint8_t* restart_mask, const float* field,
+                         const double* goal_xy, uint8_t* active, float* goal_distance, uint8_t* goal_reached, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
