@@ -37,7 +37,8 @@ class _IgState(object):
 
 class _IgGoals(object):
     """attach_ig_goals' state: the parameter block of the three launches and the tensors they keep."""
-    __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice")
+    __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice",
+                 "view", "own", "proposals", "proposals_k")  # (second row: ig_view_gain's / ig_propose_goals' buffers, made on first use)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -329,6 +330,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         q.goal_distance = torch.full((N, R), float("inf"), dtype=torch.float32, device=dev)
         q.goal_reached = torch.zeros((N, R), dtype=torch.uint8, device=dev)
         q.choice = torch.full((N, R), 255, dtype=torch.uint8, device=dev)
+        q.view = q.own = q.proposals = q.proposals_k = None
         self._goals = q
         self._alloc_act()
 
@@ -365,6 +367,61 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         [N, R] u8, goal_distance [N, R] f32, goal_reached [N, R] u8."""
         q = self._need_goals("ig_goals")
         return dict(q.out, goal_distance=q.goal_distance, goal_reached=q.goal_reached)
+
+    def ig_view_gain(self, points=None, world_mask=None):
+        """What a place is worth (needs attach_ig_goals, whose radius it uses; the range is attach_ig_learner's detect_range): ONE
+        launch on the current stream (cagym_ig_view_gain, InfoGain.view_gain).  points [N, P, 2] in world metres, or None: the
+        3600 cell centres.  Returns new device tensors gain f64, n_visible i32, valid u8, each [N, P], or [N, 60, 60] indexed
+        [j, i] for the map; a world whose byte of world_mask [N] is 0 keeps what the (uninitialised) tensors held."""
+        q = self._need_goals("ig_view_gain")
+        return self._igm.ig.view_gain(points=points, world_mask=world_mask, radius=q.P.radius)
+
+    def ig_propose_goals(self, k=8, min_sep=2.0, d0=1.0, mask=None):
+        """The best k places of every masked robot (mask [N, R], default: every robot) on the belief and the map as they are now -
+        a goal-level policy's discrete action space ("pick one of k").  Three launches on the current stream, nothing synchronises:
+        the view-gain map of the worlds that have a masked robot (cagym_ig_view_gain), the geodesic field FROM every masked robot's
+        own position, read from the state on the device, into a buffer of its own (cagym_ig_geodesic: the goal fields of ig_goals()
+        keep every byte), and the proposals (cagym_ig_propose_goals): cells ranked by gain / (distance + d0), chosen best first,
+        each suppressing the cells within min_sep metres of it (ig.propose_goals_spec).  The robots are the first R agent slots of
+        every world, as generate_exploration_worlds / stream_exploration_worlds lay them out.  Returns the dict of device tensors
+        cells [N, R, k, 2] i32 (i, j), xy [N, R, k, 2] f64, utility, gain [N, R, k] f64, distance [N, R, k] f32 and n_found [N, R]
+        i32 (rows past n_found: cells -1, xy NaN, utility = gain = 0, distance +inf), and the view-gain map it ranked as
+        view_gain / view_valid [N, 60, 60]; the buffers are allocated on the first call and written again by every later call with
+        the same k, and a robot outside the mask keeps its rows.  ig_set_goals(prop["xy"][:, :, 0]) sends every robot to its best
+        viewpoint (a robot with n_found = 0 gets a NaN goal: no active goal)."""
+        q = self._need_goals("ig_propose_goals")
+        g, N, dev = self._igm, self.N, self.device
+        ig, R, k = g.ig, g.R, int(k)
+        if k < 1 or k > 16:
+            raise ValueError("ig_propose_goals: k must be within 1..16, got %d" % k)
+        for name, val in (("min_sep", min_sep), ("d0", d0)):
+            if not (float(val) > 0.0 and np.isfinite(float(val))):
+                raise ValueError("ig_propose_goals: %s must be finite and positive, got %r" % (name, val))
+        world_mask = None
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=dev).to(torch.uint8).reshape(N, R).contiguous()
+            world_mask = (mask != 0).any(dim=1).to(torch.uint8)
+        if q.view is None:  # (zeroed once: a world that was never asked for has an empty map, not garbage)
+            q.view = {"gain": torch.zeros((N, 60, 60), dtype=torch.float64, device=dev),
+                      "n_visible": torch.zeros((N, 60, 60), dtype=torch.int32, device=dev),
+                      "valid": torch.zeros((N, 60, 60), dtype=torch.uint8, device=dev)}
+            q.own = {"field": torch.full((N, R, 60, 60), float("inf"), dtype=torch.float32, device=dev),
+                     "goal_xy": torch.zeros((N, R, 2), dtype=torch.float64, device=dev),
+                     "active": torch.zeros((N, R), dtype=torch.uint8, device=dev)}
+        if q.proposals_k != k:
+            q.proposals = {"cells": torch.full((N, R, k, 2), -1, dtype=torch.int32, device=dev),
+                           "xy": torch.full((N, R, k, 2), float("nan"), dtype=torch.float64, device=dev),
+                           "utility": torch.zeros((N, R, k), dtype=torch.float64, device=dev),
+                           "gain": torch.zeros((N, R, k), dtype=torch.float64, device=dev),
+                           "distance": torch.full((N, R, k), float("inf"), dtype=torch.float32, device=dev),
+                           "n_found": torch.zeros((N, R), dtype=torch.int32, device=dev)}
+            q.proposals_k = k
+        ig.view_gain(world_mask=world_mask, radius=q.P.radius, out=q.view)
+        st = self.state()
+        here = torch.stack((st["pos_x"][:, :R], st["pos_y"][:, :R]), dim=-1).contiguous()
+        ig.geodesic(points=here, mask=mask, radius=q.P.radius, window=q.P.window, rotate=bool(q.P.rotate), out=q.own)
+        ig.propose_goals(q.view["gain"], q.view["valid"], q.own["field"], k, min_sep, d0, mask=mask, out=q.proposals)
+        return dict(q.proposals, view_gain=q.view["gain"], view_valid=q.view["valid"])
 
     def _ig_goal_status(self, restart_mask):
         q = self._goals

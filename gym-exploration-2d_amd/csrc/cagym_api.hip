@@ -13,6 +13,7 @@
 #include "../../include/cagym_ig_observe.h"
 #include "../../include/cagym_ig_context.h"
 #include "../../include/cagym_ig_goals.h"
+#include "../../include/cagym_ig_viewpoints.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -33,6 +34,7 @@
 #include "cagym_ig_observe.h"
 #include "cagym_ig_context.h"
 #include "cagym_ig_geodesic.h"
+#include "cagym_ig_viewpoints.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2213,6 +2215,58 @@ int cagym_ig_goal_status(void* env, const cagym_ig_goal_params* params, const ui
     ON_DEVICE(e);
     hipLaunchKernelGGL(k_ig_goal_status, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D, P,
                        restart_mask, field, goal_xy, active, goal_distance, goal_reached);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- view gains and goal proposals (csrc/cagym_ig_viewpoints.h) -----------------------------------------------------------------------
+// The checks of the two entries on their shared parameter block; `name`: the entry, for the message.
+static int ig_view_params_check(Env* e, const cagym_ig_view_params* params, const char* name, IgViewParams* P) {
+    const std::string n(name);
+    if (!params) return fail(e, CAGYM_E_INVALID, n + ": null argument");
+    const cagym_ig_view_params& p = *params;
+    if (p.n_points < 0) return fail(e, CAGYM_E_INVALID, n + ": n_points must not be negative");
+    if (p.n_robots < 1 || p.n_robots > IGV_MAXR) return fail(e, CAGYM_E_INVALID, n + ": n_robots must be 1..8");
+    if (p.k < 1 || p.k > IGV_MAXK) return fail(e, CAGYM_E_INVALID, n + ": k must be 1..16");
+    if (p.flags) return fail(e, CAGYM_E_INVALID, n + ": unknown flags");
+    const double pos[4] = {p.radius, p.range, p.min_sep, p.d0};
+    for (double v : pos)
+        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
+            return fail(e, CAGYM_E_INVALID, n + ": radius, range, min_sep and d0 must be finite and positive");
+    P->P = p.n_points; P->R = p.n_robots; P->k = p.k;
+    P->radius = p.radius; P->range = p.range; P->min_sep = p.min_sep; P->d0 = p.d0;
+    return CAGYM_OK;
+}
+
+int cagym_ig_view_gain(void* env, const cagym_ig_view_params* params, const uint8_t* world_mask, const double* points_xy, double* gain,
+                       int32_t* n_visible, uint8_t* valid, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_view_gain");
+    if (!gain || !n_visible || !valid) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain: null argument");
+    IgViewParams P;
+    if (int rc = ig_view_params_check(e, params, "cagym_ig_view_gain", &P)) return rc;
+    if (!points_xy) P.P = IGV_CELLS;  // the map: the kernel generates the cell centres
+    const long long blocks = (long long)e->cfg.n_worlds * ((P.P + IGV_PER_WG - 1) / IGV_PER_WG);
+    if (blocks > 0x7fffffffll) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain: n_worlds * n_points is too large for one launch");
+    ON_DEVICE(e);
+    if (blocks == 0) return CAGYM_OK;
+    hipLaunchKernelGGL(k_ig_view_gain, dim3((unsigned)blocks), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G, P,
+                       world_mask, points_xy, gain, n_visible, valid);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_propose_goals(void* env, const cagym_ig_view_params* params, const uint8_t* mask, const double* gain_map,
+                           const uint8_t* valid_map, const float* field, int32_t* cells, double* xy, double* utility, double* gain,
+                           float* distance, int32_t* n_found, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_propose_goals");
+    if (!gain_map || !valid_map || !field || !cells || !xy || !utility || !gain || !distance || !n_found)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_propose_goals: null argument");
+    IgViewParams P;
+    if (int rc = ig_view_params_check(e, params, "cagym_ig_propose_goals", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_propose_goals, dim3((unsigned)(e->cfg.n_worlds * P.R)), dim3(IGV_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), P, mask, gain_map, valid_map, field, cells, xy, utility, gain, distance,
+                       n_found);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

@@ -144,6 +144,73 @@ class InfoGain(object):
                   goals["goal_xy"].data_ptr(), goals["active"].data_ptr(), goal_distance.data_ptr(), goal_reached.data_ptr(),
                   self.b._stream())
 
+    def view_params(self, n_points=0, n_robots=1, k=1, radius=0.5, range=None, min_sep=2.0, d0=1.0):
+        """The cagym_ig_view_params block of view_gain() / propose_goals() (range: this object's sensing range by default)."""
+        return _lib.IgViewParams(int(n_points), int(n_robots), int(k), 0, float(radius), float(self.range if range is None else range),
+                                 float(min_sep), float(d0))
+
+    def view_gain(self, points=None, world_mask=None, radius=0.5, range=None, out=None):
+        """cagym_ig_view_gain: ONE launch on the current stream - what a place is worth: the mutual information of every belief cell
+        a robot standing there could see through the walls of the world's current map, turning on the spot (no field of view, no
+        heading; ig.view_gain_spec states the rule).  `points` [N,P,2] f64 in world metres, or None: the 3600 cell centres - "the
+        map", whose values are the points call's on the same points bit for bit.  world_mask [N] u8 or None (every world): a world
+        whose byte is 0 keeps every byte of its outputs.  range: the sensing range (default: this object's).  Returns the dict of
+        device tensors it wrote: gain f64, n_visible i32, valid u8 (0: not finite, outside the map or within radius + 0.1 of an
+        obstacle; its gain and n_visible are 0), each [N,P], or [N,60,60] indexed [j, i] for the map; `out`: such a dict to write
+        into again (default: new tensors)."""
+        N, dev = self.b.N, self.b.device
+        if points is not None:
+            if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()):
+                points = self._t(points, torch.float64)
+            points = points.reshape(N, -1, 2)
+            shape = (N, points.shape[1])
+        else:
+            shape = (N, 60, 60)
+        if world_mask is not None:
+            world_mask = self._t(world_mask, torch.uint8, (N,))
+        if out is None:
+            out = {"gain": torch.empty(shape, dtype=torch.float64, device=dev), "n_visible": torch.empty(shape, dtype=torch.int32, device=dev),
+                   "valid": torch.empty(shape, dtype=torch.uint8, device=dev)}
+        P = self.view_params(n_points=shape[1] if points is not None else 0, radius=radius, range=range)
+        _lib.call(self.L, self.b.h, "cagym_ig_view_gain", C.byref(P), _lib.ptr(world_mask), _lib.ptr(points), out["gain"].data_ptr(),
+                  out["n_visible"].data_ptr(), out["valid"].data_ptr(), self.b._stream())
+        return out
+
+    def propose_goals(self, gain, valid, field, k, min_sep, d0, mask=None, out=None):
+        """cagym_ig_propose_goals: ONE launch on the current stream, one workgroup per (world, robot) - the best k places of each
+        robot: gain, valid [N,60,60] a view-gain map (view_gain()'s), field [N,R,60,60] f32 the geodesic field FROM the robot's own
+        place (geodesic(points=robot positions)["field"]).  A cell is eligible when valid, gain > 0 and field finite; its utility
+        is gain / (field + d0); k rounds take the best cell left and suppress every cell within min_sep metres of it
+        (ig.propose_goals_spec states the rule).  mask [N,R] u8 or None (every robot): a robot whose byte is 0 keeps every byte of
+        its outputs.  Returns the dict of device tensors it wrote: cells [N,R,k,2] i32 (i, j), xy [N,R,k,2] f64 their centres,
+        utility, gain [N,R,k] f64, distance [N,R,k] f32, n_found [N,R] i32; rows past n_found hold cells -1, xy NaN, utility =
+        gain = 0, distance +inf.  `out`: such a dict to write into again (default: new tensors)."""
+        N, dev = self.b.N, self.b.device
+        field = field if (torch.is_tensor(field) and field.is_cuda and field.dtype == torch.float32 and field.is_contiguous()) \
+            else self._t(field, torch.float32)
+        field = field.reshape(N, -1, 60, 60)
+        R, k = field.shape[1], int(k)
+        gain = gain if (torch.is_tensor(gain) and gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous()) \
+            else self._t(gain, torch.float64, (N, 60, 60))
+        valid = valid if (torch.is_tensor(valid) and valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous()) \
+            else self._t(valid, torch.uint8, (N, 60, 60))
+        if gain.numel() != N * 3600 or valid.numel() != N * 3600:
+            raise ValueError("propose_goals: gain and valid must be [N, 60, 60] maps")
+        if mask is not None:
+            mask = self._t(mask, torch.uint8, (N, R))
+        P = self.view_params(n_robots=R, k=k, min_sep=min_sep, d0=d0)
+        if out is None:
+            kk = max(k, 1)  # (a k the library refuses: nothing is written)
+            out = {"cells": torch.empty((N, R, kk, 2), dtype=torch.int32, device=dev),
+                   "xy": torch.empty((N, R, kk, 2), dtype=torch.float64, device=dev),
+                   "utility": torch.empty((N, R, kk), dtype=torch.float64, device=dev),
+                   "gain": torch.empty((N, R, kk), dtype=torch.float64, device=dev),
+                   "distance": torch.empty((N, R, kk), dtype=torch.float32, device=dev),
+                   "n_found": torch.empty((N, R), dtype=torch.int32, device=dev)}
+        _lib.call(self.L, self.b.h, "cagym_ig_propose_goals", C.byref(P), _lib.ptr(mask), gain.data_ptr(), valid.data_ptr(), field.data_ptr(),
+                  *[out[n].data_ptr() for n in ("cells", "xy", "utility", "gain", "distance", "n_found")], self.b._stream())
+        return out
+
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
         world = self._t(world, torch.int32, (-1,))
@@ -500,6 +567,116 @@ def goal_action_spec(field, pose, goal_xy, dt, v_max, w_max, align_tol, goal_tol
     if not abs(rem) > align_tol:
         v = min(v_max, dist / dt) if to_goal else float(v_max)
     return float(v), float(omega), cell, reached
+
+
+def edf_at_spec(edf, x, y):
+    """edfMap.get_edf_value_from_pose on arrays: edf [300, 300] f64 indexed [row = y, column = x]; the column is the floor of the
+    true quotient (x + 15) / 0.1, the row likewise of y; a negative index wraps once, as numpy's does; anything else outside, and
+    a coordinate that is not finite, reads 0.0."""
+    edf = np.asarray(edf, dtype=np.float64)
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        fx, fy = np.floor((x + 15.0) / 0.1), np.floor((y + 15.0) / 0.1)
+        ok = (np.abs(fx) < 1e6) & (np.abs(fy) < 1e6)  # (False for NaN and for +-inf)
+    xi = np.where(ok, fx, -1000.0).astype(np.int64)
+    yi = np.where(ok, fy, -1000.0).astype(np.int64)
+    xi, yi = np.where(xi < 0, xi + 300, xi), np.where(yi < 0, yi + 300, yi)
+    ok = ok & (xi >= 0) & (xi < 300) & (yi >= 0) & (yi < 300)
+    return np.where(ok, edf[np.clip(yi, 0, 299), np.clip(xi, 0, 299)], 0.0)
+
+
+def check_visibility_spec(edf, point, cx, cy):
+    """edfMap.checkVisibility(point, (cx[n], cy[n])) for arrays of goals, the statements of ig_check_visibility in csrc/cagym_ig.h:
+    dist = sqrt(dx dx + dy dy), u = 0.05 / dist; while u < 1: sample (1 - u) p + u c, fail when edf_at_spec there is < 0.001, else
+    u += edf / dist.  A goal at dist = 0 is visible (u is infinite, the loop is skipped).  The goals are lanes that step in lockstep
+    under a mask; a lane still inside the loop after 100000 trips fails.  Every product and sum is a separate fp64 operation.
+    point: (x, y), two numbers - or two arrays of cx's shape, a viewpoint per goal.  Returns a bool array of cx's shape."""
+    cx, cy = np.asarray(cx, dtype=np.float64), np.asarray(cy, dtype=np.float64)
+    shape = cx.shape
+    cx, cy = cx.ravel(), cy.ravel()
+    px = np.broadcast_to(np.asarray(point[0], dtype=np.float64), shape).ravel()
+    py = np.broadcast_to(np.asarray(point[1], dtype=np.float64), shape).ravel()
+    dx, dy = cx - px, cy - py
+    dist = np.sqrt(dx * dx + dy * dy)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = 0.05 / dist
+        live = u < 1
+        for _ in range(100000):
+            if not live.any():
+                break
+            n = np.flatnonzero(live)
+            un = u[n]
+            md = edf_at_spec(edf, (1 - un) * px[n] + un * cx[n], (1 - un) * py[n] + un * cy[n])
+            hit = md < 0.001
+            u[n] = np.where(hit, np.nan, un + md / dist[n])  # (NaN: failed, and out of the loop)
+            live[n] = u[n] < 1
+        return (~(u < 1) & ~np.isnan(u)).reshape(shape)
+
+
+def view_gain_spec(edf, mi, point, radius, range=5.0):
+    """The view gain of cagym_ig_view_gain for one point of one world, in numpy - its specification.  edf: [300, 300] f64 distance
+    field in metres of the world's current scenario slot (InfoGain.edf()[slot]); mi: [60, 60] f64 cell MI, cell_mi(belief), indexed
+    [j, i]; point (x, y) in world metres; radius: the robot's; range: the sensing range.  Returns (gain, n_visible, valid, visible
+    [60, 60] bool, in_range [60, 60] bool).
+      valid <=> x, y finite, the cell floor((p + 15) / 0.5) in 0..59 on both axes and edf_at_spec(x, y) > radius + 0.1, the planners'
+        feasibility test at the point itself; an invalid point has gain 0, n_visible 0 and empty masks.
+      candidates: i in max(0, cell(x - range)) .. min(59, cell(x + range)), j likewise; centre c = i * 0.5 - 15 + 0.25;
+      in_range <=> dx dx + dy dy < range range, dx = cx - x; visible <=> in_range and check_visibility_spec(point, c): a robot
+        turning on the spot, no field of view, no heading.
+      gain = math.fsum of mi over the visible cells (the library adds them in a fixed order: equal up to the rounding of ~300 sums)."""
+    mi = np.asarray(mi, dtype=np.float64).reshape(60, 60)
+    x, y, rng = float(point[0]), float(point[1]), float(range)
+    vis, inr = np.zeros((60, 60), dtype=bool), np.zeros((60, 60), dtype=bool)
+    if not (math.isfinite(x) and math.isfinite(y)):
+        return 0.0, 0, False, vis, inr
+    cell = lambda v: int(min(max(math.floor((v + 15.0) / 0.5), -10 ** 6), 10 ** 6))
+    if not (0 <= cell(x) < 60 and 0 <= cell(y) < 60) or not float(edf_at_spec(edf, x, y)) > float(radius) + 0.1:
+        return 0.0, 0, False, vis, inr
+    i = np.arange(max(0, cell(x - rng)), min(59, cell(x + rng)) + 1)
+    j = np.arange(max(0, cell(y - rng)), min(59, cell(y + rng)) + 1)
+    jj, ii = np.meshgrid(j, i, indexing="ij")
+    cx, cy = ii * 0.5 - 15.0 + 0.25, jj * 0.5 - 15.0 + 0.25
+    dx, dy = cx - x, cy - y
+    near = dx * dx + dy * dy < rng * rng
+    inr[jj[near], ii[near]] = True
+    seen = check_visibility_spec(edf, (x, y), cx[near], cy[near])
+    vis[jj[near][seen], ii[near][seen]] = True
+    return math.fsum(mi[vis]), int(vis.sum()), True, vis, inr
+
+
+def propose_goals_spec(gain, valid, field, k, min_sep, d0):
+    """The proposals of cagym_ig_propose_goals for one (world, robot), in numpy - their bit-exact specification.  gain [60, 60] f64
+    and valid [60, 60]: the world's view-gain map at the cell centres, indexed [j, i]; field [60, 60] f32: the robot's geodesic field
+    with its own position as the source; k in 1..16, min_sep > 0 and d0 > 0 in metres.
+      A cell is eligible iff valid != 0, gain > 0 and field is finite; its utility is gain / ((double)field + d0): one fp64 addition,
+      one fp64 division.  Up to k rounds: take the eligible, unsuppressed cell of largest utility, of equal utilities the smallest flat
+      index j * 60 + i; then suppress every cell with (double)(di di + dj dj) * 0.25 < min_sep min_sep, the chosen cell included.
+      Stop when nothing is left.
+    Returns a dict: cells [k, 2] i32 (i, j), xy [k, 2] f64 the cell centres, utility, gain [k] f64, distance [k] f32, n_found; rows
+    past n_found hold cells = -1, xy = NaN, utility = gain = 0 and distance = +inf."""
+    gain = np.asarray(gain, dtype=np.float64).reshape(60, 60)
+    valid = np.asarray(valid).reshape(60, 60)
+    field = np.asarray(field, dtype=np.float32).reshape(60, 60)
+    k, sep2, d0 = int(k), float(min_sep) * float(min_sep), float(d0)
+    if not (1 <= k <= 16 and float(min_sep) > 0 and d0 > 0):
+        raise ValueError("propose_goals_spec: k must be 1..16, min_sep and d0 positive")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        eligible = (valid != 0) & (gain > 0) & np.isfinite(field)
+        util = np.where(eligible, gain / (field.astype(np.float64) + d0), -1.0)  # (an eligible cell's utility is >= 0)
+    out = {"cells": np.full((k, 2), -1, dtype=np.int32), "xy": np.full((k, 2), np.nan), "utility": np.zeros(k), "gain": np.zeros(k),
+           "distance": np.full(k, np.inf, dtype=np.float32), "n_found": 0}
+    jj, ii = np.meshgrid(np.arange(60), np.arange(60), indexing="ij")
+    for n in range(k):
+        q = int(np.argmax(util))  # (the first of equal maxima: the smallest flat index)
+        j, i = divmod(q, 60)
+        if not util[j, i] >= 0:
+            break
+        out["cells"][n] = (i, j)
+        out["xy"][n] = (i * 0.5 - 15.0 + 0.25, j * 0.5 - 15.0 + 0.25)
+        out["utility"][n], out["gain"][n], out["distance"][n] = util[j, i], gain[j, i], field[j, i]
+        out["n_found"] = n + 1
+        util[((ii - i) ** 2 + (jj - j) ** 2).astype(np.float64) * 0.25 < sep2] = -1.0
+    return out
 
 
 def cell_mi(r):

@@ -578,6 +578,45 @@ int cagym_ig_goal_actions(void* env, const cagym_ig_goal_params* params, const f
 int cagym_ig_goal_status(void* env, const cagym_ig_goal_params* params, const uint8_t* restart_mask, const float* field,
                          const double* goal_xy, uint8_t* active, float* goal_distance, uint8_t* goal_reached, void* stream);
 
+/* ---- View gains and goal proposals: what a place is worth to an IG robot, and the best k places per robot ---------------------------
+ * Two launches on `stream`, on demand (no step runs them), no host synchronisation, no global atomics, barriers only.  params of both:
+ * cagym_ig_view_params, defined in include/cagym_ig_viewpoints.h (n_points = P, n_robots = R 1..8, k 1..16, flags = 0, radius, range,
+ * min_sep, d0); every call validates the whole block.  Cells are those of the belief: i = floor((x + 15) / 0.5), j likewise of y,
+ * centre c(i) = i * 0.5 - 15 + 0.25.
+ *
+ * cagym_ig_view_gain: the mutual information a robot standing at a point would cover turning on the spot (no field of view, no
+ * heading), through the walls of the world's CURRENT scenario slot.  points_xy DEVICE [N,P,2] f64 in world metres, or NULL: the 3600
+ * cell centres, P = 3600, point j * 60 + i = (c(i), c(j)) - the outputs are then maps [N,60,60] indexed [j, i], and their values are
+ * those of a points call on the same points bit for bit.  world_mask DEVICE [N] u8 or NULL (= every world): a world whose byte is 0
+ * is skipped, nothing of it is read or written.  Outputs, DEVICE [N,P]: valid u8, n_visible i32, gain f64.
+ *   valid <=> x and y are finite, the point's cell lies in 0..59 on both axes, and EDF(x, y) > radius + 0.1 (the planners' feasibility
+ *     test, edfMap.get_edf_value_from_pose).  An invalid point has gain = 0 and n_visible = 0.
+ *   candidates: cells i in max(0, cell(x - range)) .. min(59, cell(x + range)), j likewise; in range <=> dx dx + dy dy < range range
+ *     with dx = c(i) - x (fp64, separate operations); visible <=> edfMap.checkVisibility(point, centre), the sphere trace of
+ *     cagym_ig_visible_cells (the own cell at distance 0 is visible).
+ *   n_visible = the visible in-range candidates, gain = the sum of the MI cache's values (cell_mi(belief), as cagym_ig_mi_reward reads
+ *     them) over them: per lane in candidate order (row-major, lane = candidate mod 64), the 64 lanes in a fixed tree - the same bits
+ *     on every call.
+ *
+ * cagym_ig_propose_goals: one workgroup per (world, robot); mask DEVICE [N,R] u8 or NULL (= every robot): a robot whose byte is 0 is
+ * skipped, nothing of it is read or written.  gain_map DEVICE [N,60,60] f64 and valid_map DEVICE [N,60,60] u8: a world's view-gain
+ * map; field DEVICE [N,R,60,60] f32: cagym_ig_geodesic's with the robot's own place as the source.
+ *   eligible <=> valid != 0, gain > 0 and field finite; utility = gain / ((double)field + d0), one fp64 addition, one fp64 division.
+ *   up to k rounds: the eligible, unsuppressed cell of largest utility (of equal ones the smallest j * 60 + i) is chosen, then every
+ *   cell with (double)(di di + dj dj) * 0.25 < min_sep min_sep is suppressed, the chosen one included; stop when none is left.
+ * Outputs, DEVICE: cells [N,R,k,2] i32 (i, j); xy [N,R,k,2] f64 the centres; utility, gain [N,R,k] f64; distance [N,R,k] f32 the field
+ * there; n_found [N,R] i32.  Rows past n_found hold cells = -1, xy = NaN, utility = gain = 0, distance = +inf.
+ *
+ * Errors, both, before anything is touched: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params or output (or
+ * gain_map, valid_map, field), n_points < 0, n_robots outside 1..8, k outside 1..16, flags != 0, a radius, range, min_sep or d0 that
+ * is not finite or not positive; CAGYM_E_DEVICE as every launching entry. */
+typedef struct cagym_ig_view_params cagym_ig_view_params;
+int cagym_ig_view_gain(void* env, const cagym_ig_view_params* params, const uint8_t* world_mask, const double* points_xy, double* gain,
+                       int32_t* n_visible, uint8_t* valid, void* stream);
+int cagym_ig_propose_goals(void* env, const cagym_ig_view_params* params, const uint8_t* mask, const double* gain_map,
+                           const uint8_t* valid_map, const float* field, int32_t* cells, double* xy, double* utility, double* gain,
+                           float* distance, int32_t* n_found, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
