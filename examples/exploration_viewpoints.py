@@ -7,10 +7,14 @@ robot that has arrived gives its goal up and turns once round (--spin steps of t
 place - by then the belief round it is settled and the proposals lie elsewhere.  A robot whose world restarted starts over, with
 a look round, as every robot does at the start.  Everything stays on the device.
 
+--headings H (default 0: the loop above) scores POSES instead: ig_propose_goals(headings=H) ranks every place by the best of H sensor
+cones there and hands the cone's heading back, ig_set_goals(..., headings=) makes the robot turn to it on arrival, and the robot
+gives its goal up once info["goal_facing"] says "there, and facing it" - there is no look round, at the start or anywhere else.
+
 The same seed, hence the same never-repeating sequence of worlds, is then run by the built-in ig_greedy; both keep the IG team's
 episode log, and stats.paired_by_key compares the two episode by episode on the worlds both finished.
 
-    python examples/exploration_viewpoints.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--k 8] [--spin 20]
+    python examples/exploration_viewpoints.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--k 8] [--spin 20] [--headings 0]
 """
 import argparse
 import importlib
@@ -73,6 +77,7 @@ def main():
     ap.add_argument("--min-sep", type=float, default=2.0, help="metres between two proposals, and between two robots' targets")
     ap.add_argument("--d0", type=float, default=1.0, help="metres added to the distance in gain / (distance + d0)")
     ap.add_argument("--spin", type=int, default=20, help="steps a robot turns on the spot after it has arrived (20 x 0.1 s x pi rad/s: once round)")
+    ap.add_argument("--headings", type=int, default=0, help="H > 0: proposals and goals carry the best of H headings; no look round")
     ap.add_argument("--turn", type=float, default=3.141592653589793, help="rad/s of that turn")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--capacity", type=int, default=65536, help="rows of each episode log")
@@ -80,6 +85,7 @@ def main():
     ap.add_argument("--pref-speed", type=float, default=10.0, help="sets the robots' time limit 3 (|p - g| - 0.75) / pref_speed")
     a = ap.parse_args()
     N, R = a.worlds, a.robots
+    look = 0 if a.headings > 0 else a.spin  # steps of a look round: none when the goals carry a heading
 
     # best viewpoints: the env scores places and drives, the loop only picks one of k
     env, M = make(a)
@@ -88,27 +94,32 @@ def main():
     env.attach_ig_episode_log(capacity=a.capacity, p_found=a.p_found)
     env.reset()
     actions = torch.zeros((N, M, 2), dtype=torch.float32, device=env.device)  # rows of robots without a target: the caller's
-    goals = env.ig_goals()
     nan = torch.full((N, R, 2), float("nan"), dtype=torch.float64, device=env.device)
-    spin = torch.full((N, R), a.spin, dtype=torch.int64, device=env.device)  # steps of the look round still to go
+    if a.headings > 0:  # (no goal yet, but from here on the goals carry headings: ig_goals() and info hold goal_facing)
+        env.ig_set_goals(nan, headings=nan[:, :, 0])
+    goals = env.ig_goals()
+    spin = torch.full((N, R), look, dtype=torch.int64, device=env.device)  # steps of the look round still to go
     n_set = n_shifted = 0
     for t in range(a.steps):
         active = goals["active"] != 0
-        arrived = active & (goals["goal_reached"] != 0)
+        arrived = active & (goals["goal_facing" if a.headings > 0 else "goal_reached"] != 0)
         env.ig_clear_goals(mask=arrived.to(torch.uint8))  # (a proposal is a place the robot can reach: nobody gets stuck)
-        spin = torch.where(arrived, torch.full_like(spin, a.spin), spin)
+        spin = torch.where(arrived, torch.full_like(spin, look), spin)
         active = goals["active"] != 0
         need = ~active & (spin == 0)
-        prop = env.ig_propose_goals(k=a.k, min_sep=a.min_sep, d0=a.d0, mask=need.to(torch.uint8))
+        prop = env.ig_propose_goals(k=a.k, min_sep=a.min_sep, d0=a.d0, mask=need.to(torch.uint8), headings=a.headings if a.headings > 0 else None)
         target = torch.where(active[:, :, None], goals["goal_xy"], nan)  # what the robots that keep their target aim at
         target, rank = pick_apart(prop, target, need, a.min_sep)
-        env.ig_set_goals(target, mask=need.to(torch.uint8))
+        if a.headings > 0:  # the chosen proposal's best cone: the robot turns to it once it is there
+            env.ig_set_goals(target, mask=need.to(torch.uint8), headings=prop["heading"].gather(2, rank[:, :, None])[:, :, 0])
+        else:
+            env.ig_set_goals(target, mask=need.to(torch.uint8))
         n_set += int(need.sum())  # (host reads per step: an example's bookkeeping, not a training loop's)
         n_shifted += int((need & (rank > 0)).sum())
         actions[:, :R, 1] = torch.where(spin > 0, a.turn, 0.0).to(torch.float32)  # (read only by robots without a target)
         spin = (spin - 1).clamp(min=0)
         _, _, over, _ = env.step(actions, auto_reset=True)
-        spin = torch.where((over != 0)[:, None], torch.full_like(spin, a.spin), spin)  # a new world: look round first
+        spin = torch.where((over != 0)[:, None], torch.full_like(spin, look), spin)  # a new world: look round first
     print("viewpoints targets set %d  moved off a teammate's %d  active now %d of %d" % (n_set, n_shifted, int(goals["active"].sum()), N * R))
     logs = {"viewpoints": report("viewpoints", env)}
     env.close()

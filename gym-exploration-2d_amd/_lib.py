@@ -162,6 +162,12 @@ class IgViewParams(C.Structure):
                 ("range", C.c_double), ("min_sep", C.c_double), ("d0", C.c_double)]
 
 
+class IgHeadingParams(C.Structure):
+    """cagym_ig_heading_params (include/cagym_ig_headings.h; not in STRUCTS, as IgObserveParams)."""
+    _fields_ = [("n_points", C.c_int32), ("n_headings", C.c_int32), ("flags", C.c_uint32), ("radius", C.c_double),
+                ("range", C.c_double), ("fov", C.c_double), ("headings", C.c_double * 16)]
+
+
 # cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
 IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
                 ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
@@ -266,6 +272,9 @@ _ARGTYPES = {
     "cagym_ig_goal_status": [_vp, _P(IgGoalParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_view_gain": [_vp, _P(IgViewParams), _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_propose_goals": [_vp, _P(IgViewParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_view_gain_headings": [_vp, _P(IgHeadingParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_goal_face_actions": [_vp, _P(IgGoalParams), _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_goal_face_status": [_vp, _P(IgGoalParams), C.c_double, _vp, _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],
     "cagym_dmcts_plan": [_vp, _P(DmctsParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     "cagym_episode_records_init": [_vp, _int, _vp],

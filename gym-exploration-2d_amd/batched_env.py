@@ -38,7 +38,8 @@ class _IgState(object):
 class _IgGoals(object):
     """attach_ig_goals' state: the parameter block of the three launches and the tensors they keep."""
     __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice",
-                 "view", "own", "proposals", "proposals_k")  # (second row: ig_view_gain's / ig_propose_goals' buffers, made on first use)
+                 "view", "own", "proposals", "proposals_k",  # (second row: ig_view_gain's / ig_propose_goals' buffers, made on first use)
+                 "face_tol", "goal_heading", "goal_facing", "hview", "hprop")  # (third: goal headings, made by the first headings= call)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -300,7 +301,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             g.ig.context_window(g.R, g.context_window, g.window, g.rotate, g.clear_max, g.observed, restart_mask,
                                 CONTEXT_ONLY_MASKED if flags & OBSERVE_ONLY_RESTARTED else 0)
 
-    def attach_ig_goals(self, radius=0.5, v_max=2.0, w_max=np.pi, align_tol=np.pi / 4, goal_tol=0.25):
+    def attach_ig_goals(self, radius=0.5, v_max=2.0, w_max=np.pi, align_tol=np.pi / 4, goal_tol=0.25, face_tol=np.pi / 18):
         """Goal actions for the learner's robots (needs attach_ig_learner): from now on a robot may be given a PLACE to go to
         (ig_set_goals) instead of a (v, omega) per step, and while it holds an active goal step() overwrites its row of the action
         table with a controller's that descends the goal's geodesic field - the obstacle-aware shortest-path distance on the
@@ -314,11 +315,17 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
           "goal_reached" [N, R] u8 - 1 when an active goal lies within goal_tol of the robot,
         both of the state the step left, written by one launch behind the observe launch (cagym_ig_goal_status); one launch in front
         of the step writes the rows (cagym_ig_goal_actions, on the env's own table: `actions` is only read).  Everything is
-        stream-ordered, nothing synchronises.  Attaching another IG policy, or detach_ig_mcts(), drops the goals."""
+        stream-ordered, nothing synchronises.  Attaching another IG policy, or detach_ig_mcts(), drops the goals.
+        A goal may carry a heading (ig_set_goals(..., headings=)): from the first such call on, a robot that has arrived turns on
+        the spot to its goal's heading (cagym_ig_goal_face_actions behind the controller's launch) and info gains
+          "goal_facing" [N, R] u8 - 1 when the robot is within goal_tol of an active goal and either has no goal heading or faces
+              it within face_tol radians (cagym_ig_goal_face_status behind the status launch; ig.goal_face_spec states both).
+        Until that call nothing of this is allocated or launched and info has no such key."""
         g = self._igm
         if g is None or g.kind != "ig_learner":
             raise RuntimeError("attach_ig_goals needs attach_ig_learner first: the goals drive the learner's robots")
-        for name, val in (("radius", radius), ("v_max", v_max), ("w_max", w_max), ("align_tol", align_tol), ("goal_tol", goal_tol)):
+        for name, val in (("radius", radius), ("v_max", v_max), ("w_max", w_max), ("align_tol", align_tol), ("goal_tol", goal_tol),
+                          ("face_tol", face_tol)):
             if not (float(val) > 0.0 and np.isfinite(float(val))):
                 raise ValueError("attach_ig_goals: %s must be finite and positive, got %r" % (name, val))
         N, R, dev = self.N, g.R, self.device
@@ -331,6 +338,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         q.goal_reached = torch.zeros((N, R), dtype=torch.uint8, device=dev)
         q.choice = torch.full((N, R), 255, dtype=torch.uint8, device=dev)
         q.view = q.own = q.proposals = q.proposals_k = None
+        q.face_tol, q.goal_heading, q.goal_facing, q.hview, q.hprop = float(face_tol), None, None, None, None
         self._goals = q
         self._alloc_act()
 
@@ -339,18 +347,33 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             raise RuntimeError("%s needs attach_ig_goals" % what)
         return self._goals
 
-    def ig_set_goals(self, goals, mask=None, frame="world"):
+    def ig_set_goals(self, goals, mask=None, frame="world", headings=None):
         """Give the masked robots (mask [N, R], default: every robot) a goal each, in ONE geodesic launch on the current stream
         followed by the status launch: goals [N, R, 2], with frame="world" points (x, y) in metres, with frame="window" cells (a, b)
         of each robot's belief window as the state has it now (a forward, b left - e.g. the argmax of a channel of
         info["belief_window"]).  A goal that is not finite or lies outside the map leaves its robot without an active goal.  Robots
-        outside the mask keep every byte of their field, goal and active flag."""
+        outside the mask keep every byte of their field, goal and active flag.
+        headings [N, R] f64: the heading in radians each masked robot is to face once it has arrived, NaN for none (e.g.
+        ig_propose_goals(headings=8)["heading"][:, :, 0]).  The first call with headings allocates goal_heading [N, R] (NaN) and
+        switches on the two face launches and info["goal_facing"] (attach_ig_goals); a later call without headings stores NaN for
+        the masked robots."""
         q = self._need_goals("ig_set_goals")
         if frame not in ("world", "window"):
             raise ValueError("ig_set_goals: frame must be 'world' or 'window', got %r" % (frame,))
-        ig = self._igm.ig
+        ig, N, R, dev = self._igm.ig, self.N, self._igm.R, self.device
         kw = {"points": goals} if frame == "world" else {"cells": goals}
         ig.geodesic(mask=mask, radius=q.P.radius, window=q.P.window, rotate=bool(q.P.rotate), out=q.out, **kw)
+        if headings is not None and q.goal_heading is None:
+            q.goal_heading = torch.full((N, R), float("nan"), dtype=torch.float64, device=dev)
+            q.goal_facing = torch.zeros((N, R), dtype=torch.uint8, device=dev)
+        if q.goal_heading is not None:
+            new = torch.full((N, R), float("nan"), dtype=torch.float64, device=dev) if headings is None else \
+                torch.as_tensor(headings, device=dev).to(torch.float64).reshape(N, R)
+            if mask is None:
+                q.goal_heading.copy_(new)
+            else:
+                m = torch.as_tensor(mask, device=dev).reshape(N, R) != 0
+                q.goal_heading.copy_(torch.where(m, new, q.goal_heading))
         self._ig_goal_status(None)
 
     def ig_clear_goals(self, mask=None):
@@ -364,9 +387,13 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
 
     def ig_goals(self):
         """Zero-copy device views of the goal state: field [N, R, 60, 60] f32 (indexed [j, i]), goal_xy [N, R, 2] f64, active
-        [N, R] u8, goal_distance [N, R] f32, goal_reached [N, R] u8."""
+        [N, R] u8, goal_distance [N, R] f32, goal_reached [N, R] u8 and, once a goal has been given a heading, goal_heading
+        [N, R] f64 (NaN: none) and goal_facing [N, R] u8."""
         q = self._need_goals("ig_goals")
-        return dict(q.out, goal_distance=q.goal_distance, goal_reached=q.goal_reached)
+        d = dict(q.out, goal_distance=q.goal_distance, goal_reached=q.goal_reached)
+        if q.goal_heading is not None:
+            d.update(goal_heading=q.goal_heading, goal_facing=q.goal_facing)
+        return d
 
     def ig_view_gain(self, points=None, world_mask=None):
         """What a place is worth (needs attach_ig_goals, whose radius it uses; the range is attach_ig_learner's detect_range): ONE
@@ -376,7 +403,17 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         q = self._need_goals("ig_view_gain")
         return self._igm.ig.view_gain(points=points, world_mask=world_mask, radius=q.P.radius)
 
-    def ig_propose_goals(self, k=8, min_sep=2.0, d0=1.0, mask=None):
+    def ig_view_gain_headings(self, points=None, headings=8, world_mask=None):
+        """What a POSE is worth (needs attach_ig_goals, whose radius it uses; fov and range are attach_ig_learner's detect_fov and
+        detect_range): ONE launch on the current stream (cagym_ig_view_gain_headings, InfoGain.view_gain_headings).  points
+        [N, P, 2] in world metres, or None: the 3600 cell centres; headings: an int H, meaning h * 2 pi / H, or a sequence of
+        1..16 radians.  Returns new device tensors gain_h f64 and n_visible_h i32 [N, P, H], best_heading i32, best_gain f64 and
+        valid u8 [N, P] ([N, 60, 60, H] and [N, 60, 60] indexed [j, i] for the map), and "headings", the list used; for heading h
+        the counted cells are exactly those the reward's sensor model sees from the pose (x, y, headings[h])."""
+        q = self._need_goals("ig_view_gain_headings")
+        return self._igm.ig.view_gain_headings(points=points, headings=headings, world_mask=world_mask, radius=q.P.radius)
+
+    def ig_propose_goals(self, k=8, min_sep=2.0, d0=1.0, mask=None, headings=None):
         """The best k places of every masked robot (mask [N, R], default: every robot) on the belief and the map as they are now -
         a goal-level policy's discrete action space ("pick one of k").  Three launches on the current stream, nothing synchronises:
         the view-gain map of the worlds that have a masked robot (cagym_ig_view_gain), the geodesic field FROM every masked robot's
@@ -388,7 +425,16 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         i32 (rows past n_found: cells -1, xy NaN, utility = gain = 0, distance +inf), and the view-gain map it ranked as
         view_gain / view_valid [N, 60, 60]; the buffers are allocated on the first call and written again by every later call with
         the same k, and a robot outside the mask keeps its rows.  ig_set_goals(prop["xy"][:, :, 0]) sends every robot to its best
-        viewpoint (a robot with n_found = 0 gets a NaN goal: no active goal)."""
+        viewpoint (a robot with n_found = 0 gets a NaN goal: no active goal).
+        headings=H or a sequence (ig_view_gain_headings'): the map that is ranked is the heading-resolved one's best_gain - what the
+        best single sensor cone at a place sees, not a robot turning once round - and the result gains heading [N, R, k] f64, the
+        heading of the chosen cell's best cone, and heading_index [N, R, k] i32, its index in this call's list (rows past n_found:
+        NaN and -1), gathered on the device for the masked robots; view_gain is then that best_gain map.  The two are buffers like
+        the other keys: a robot outside the mask keeps the rows an earlier headings call gave it - the heading in radians stays
+        what it was, heading_index refers to THAT call's list - or NaN and -1 if there was none with this k.  The heading map is
+        one buffer too: a call with another list of headings empties it first (valid 0, best_heading -1), so a world without a
+        masked robot never shows indices of another list.  ig_set_goals(prop["xy"][:, :, 0], headings=prop["heading"][:, :, 0])
+        sends every robot to its best pose."""
         q = self._need_goals("ig_propose_goals")
         g, N, dev = self._igm, self.N, self.device
         ig, R, k = g.ig, g.R, int(k)
@@ -416,17 +462,59 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
                            "distance": torch.full((N, R, k), float("inf"), dtype=torch.float32, device=dev),
                            "n_found": torch.zeros((N, R), dtype=torch.int32, device=dev)}
             q.proposals_k = k
-        ig.view_gain(world_mask=world_mask, radius=q.P.radius, out=q.view)
+            if q.hprop is not None:  # (the rows of another k are gone: so are their headings)
+                q.hprop["heading"] = q.hprop["heading_index"] = None
+        if headings is None:
+            ig.view_gain(world_mask=world_mask, radius=q.P.radius, out=q.view)
+            gain_map, valid_map = q.view["gain"], q.view["valid"]
+        else:
+            if q.hview is None:  # (zeroed once, as the omni map above)
+                q.hview = {"best_heading": torch.full((N, 60, 60), -1, dtype=torch.int32, device=dev),
+                           "best_gain": torch.zeros((N, 60, 60), dtype=torch.float64, device=dev),
+                           "valid": torch.zeros((N, 60, 60), dtype=torch.uint8, device=dev)}
+            hs = tuple(ig.heading_list(headings))
+            if q.hprop is None or q.hprop["list"] != hs:  # another list: uploaded once, and the map of the old one is emptied
+                if q.hprop is not None:
+                    q.hview["best_heading"].fill_(-1)
+                    q.hview["best_gain"].zero_()
+                    q.hview["valid"].zero_()
+                old = q.hprop or {}
+                q.hprop = {"list": hs, "table": torch.tensor(hs, dtype=torch.float64, device=dev), "heading": old.get("heading"),
+                           "heading_index": old.get("heading_index")}
+            if q.hprop["heading"] is None:
+                q.hprop["heading"] = torch.full((N, R, k), float("nan"), dtype=torch.float64, device=dev)
+                q.hprop["heading_index"] = torch.full((N, R, k), -1, dtype=torch.int32, device=dev)
+            hv = ig.view_gain_headings(headings=list(hs), world_mask=world_mask, radius=q.P.radius, out=q.hview, want_rows=False)
+            gain_map, valid_map = hv["best_gain"], hv["valid"]
         st = self.state()
         here = torch.stack((st["pos_x"][:, :R], st["pos_y"][:, :R]), dim=-1).contiguous()
         ig.geodesic(points=here, mask=mask, radius=q.P.radius, window=q.P.window, rotate=bool(q.P.rotate), out=q.own)
-        ig.propose_goals(q.view["gain"], q.view["valid"], q.own["field"], k, min_sep, d0, mask=mask, out=q.proposals)
-        return dict(q.proposals, view_gain=q.view["gain"], view_valid=q.view["valid"])
+        ig.propose_goals(gain_map, valid_map, q.own["field"], k, min_sep, d0, mask=mask, out=q.proposals)
+        res = dict(q.proposals, view_gain=gain_map, view_valid=valid_map)
+        if headings is not None:  # the chosen cells' best cones: a gather on the device, nothing synchronises
+            cells = q.proposals["cells"].long()
+            found = cells[..., 0] >= 0
+            flat = (cells[..., 1] * 60 + cells[..., 0]).clamp_(min=0).reshape(N, R * k)
+            idx = torch.gather(hv["best_heading"].reshape(N, 3600), 1, flat).reshape(N, R, k)
+            table = q.hprop["table"]
+            idx = torch.where(found & (idx >= 0) & (idx < table.numel()), idx, torch.full_like(idx, -1))  # (never past the table)
+            new = torch.where(idx >= 0, table[idx.clamp(min=0).long()], torch.full((), float("nan"), dtype=torch.float64, device=dev))
+            if mask is None:
+                q.hprop["heading_index"].copy_(idx)
+                q.hprop["heading"].copy_(new)
+            else:  # the masked robots' rows alone
+                on = (mask != 0)[:, :, None]
+                q.hprop["heading_index"].copy_(torch.where(on, idx, q.hprop["heading_index"]))
+                q.hprop["heading"].copy_(torch.where(on, new, q.hprop["heading"]))
+            res["heading_index"], res["heading"] = q.hprop["heading_index"], q.hprop["heading"]
+        return res
 
     def _ig_goal_status(self, restart_mask):
         q = self._goals
         if q is not None:
             self._igm.ig.goal_status(q.P, q.out, q.goal_distance, q.goal_reached, restart_mask)
+            if q.goal_heading is not None:
+                self._igm.ig.goal_face_status(q.P, q.out, q.goal_heading, q.goal_facing, q.face_tol)
 
     def detach_ig_mcts(self):
         self._igm = self._goals = None
@@ -472,6 +560,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             g.ig.robot_actions(g.R, planned, table)
         if goals is not None:
             self._igm.ig.goal_actions(goals.P, goals.out, table, goals.choice)
+            if goals.goal_heading is not None:
+                self._igm.ig.goal_face_actions(goals.P, goals.out, goals.goal_heading, table)
         return table
 
     def _chained_step(self, a, o, auto_reset, restart, team_reward_out=None, oas=None, term=False):
@@ -503,7 +593,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read.  With attach_ig_learner the robots' rows are the learner's (v, omega), and info also carries
         "belief_window", "gain" and "observed" of the state the step left, with context=True "context_window", and with
-        attach_ig_goals "goal_distance" and "goal_reached"."""
+        attach_ig_goals "goal_distance" and "goal_reached" (and "goal_facing" once a goal has carried a heading)."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
             raise RuntimeError("step(auto_reset=True) with %s attached: the planner's per-world restart (beliefs, "
@@ -520,6 +610,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
                 info["context_window"] = g.context_window
             if self._goals is not None:
                 info.update(goal_distance=self._goals.goal_distance, goal_reached=self._goals.goal_reached)
+                if self._goals.goal_heading is not None:
+                    info["goal_facing"] = self._goals.goal_facing
         if auto_reset and self._term is not None:
             info["terminal"] = dict(self._term, valid=self.game_over)
         return self._obs(), self.reward, self.game_over, info

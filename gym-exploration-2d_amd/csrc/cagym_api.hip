@@ -14,6 +14,7 @@
 #include "../../include/cagym_ig_context.h"
 #include "../../include/cagym_ig_goals.h"
 #include "../../include/cagym_ig_viewpoints.h"
+#include "../../include/cagym_ig_headings.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -35,6 +36,7 @@
 #include "cagym_ig_context.h"
 #include "cagym_ig_geodesic.h"
 #include "cagym_ig_viewpoints.h"
+#include "cagym_ig_headings.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2267,6 +2269,70 @@ int cagym_ig_propose_goals(void* env, const cagym_ig_view_params* params, const 
     hipLaunchKernelGGL(k_ig_propose_goals, dim3((unsigned)(e->cfg.n_worlds * P.R)), dim3(IGV_THREADS), 0,
                        reinterpret_cast<hipStream_t>(stream), P, mask, gain_map, valid_map, field, cells, xy, utility, gain, distance,
                        n_found);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- heading-resolved view gains, goal headings and facing (csrc/cagym_ig_headings.h) -------------------------------------------------
+int cagym_ig_view_gain_headings(void* env, const cagym_ig_heading_params* params, const uint8_t* world_mask, const double* points_xy,
+                                double* gain_h, int32_t* n_visible_h, int32_t* best_heading, double* best_gain, uint8_t* valid,
+                                void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_view_gain_headings");
+    if (!params || !best_heading || !best_gain || !valid) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: null argument");
+    const cagym_ig_heading_params& p = *params;
+    if (p.n_points < 0) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_points must not be negative");
+    if (p.n_headings < 1 || p.n_headings > IGH_MAXH) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_headings must be 1..16");
+    if (p.flags) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: unknown flags");
+    const double pos[3] = {p.radius, p.range, p.fov};
+    for (double v : pos)
+        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
+            return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: radius, range and fov must be finite and positive");
+    IgHeadingParams P;
+    P.P = points_xy ? p.n_points : IGV_CELLS;  // the map: the kernel generates the cell centres
+    P.H = p.n_headings;
+    P.radius = p.radius; P.range = p.range; P.fov = p.fov;
+    for (int h = 0; h < IGH_MAXH; h++) {
+        if (h < p.n_headings && !std::isfinite(p.headings[h]))
+            return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: the first n_headings headings must be finite");
+        P.headings[h] = h < p.n_headings ? p.headings[h] : 0.0;
+    }
+    const long long blocks = (long long)e->cfg.n_worlds * (((long long)P.P + IGV_PER_WG - 1) / IGV_PER_WG);  // (no int sum near INT_MAX)
+    if (blocks > 0x7fffffffll)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_worlds * n_points is too large for one launch");
+    ON_DEVICE(e);
+    if (blocks == 0) return CAGYM_OK;
+    hipLaunchKernelGGL(k_ig_view_gain_headings, dim3((unsigned)blocks), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
+                       P, world_mask, points_xy, gain_h, n_visible_h, best_heading, best_gain, valid);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_goal_face_actions(void* env, const cagym_ig_goal_params* params, const double* goal_xy, const uint8_t* active,
+                               const double* goal_heading, float* actions, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_goal_face_actions");
+    if (!goal_xy || !active || !goal_heading || !actions) return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_actions: null argument");
+    if (reinterpret_cast<uintptr_t>(actions) & 7)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_actions: actions must be 8-byte aligned");
+    IgGoalParams P;
+    if (int rc = ig_goal_params_check(e, params, "cagym_ig_goal_face_actions", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_goal_face_actions, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D, P,
+                       goal_xy, active, goal_heading, actions);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_goal_face_status(void* env, const cagym_ig_goal_params* params, double face_tol, const double* goal_xy,
+                              const uint8_t* active, const double* goal_heading, uint8_t* goal_facing, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_goal_face_status");
+    if (!goal_xy || !active || !goal_heading || !goal_facing) return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_status: null argument");
+    if (!(face_tol > 0.0) || !std::isfinite(face_tol))  // (the negated comparison refuses NaN)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_status: face_tol must be finite and positive");
+    IgGoalParams P;
+    if (int rc = ig_goal_params_check(e, params, "cagym_ig_goal_face_status", &P)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_goal_face_status, dim3((unsigned)e->cfg.n_worlds), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), e->D, P,
+                       face_tol, goal_xy, active, goal_heading, goal_facing);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

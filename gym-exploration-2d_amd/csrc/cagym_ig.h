@@ -140,6 +140,32 @@ __device__ __forceinline__ bool ig_in_cone(double r0, double r1, const IgCone& c
     return rn < range && fabs(dphi) < fov / 2;
 }
 
+// The box of targetMap.getVisibleCells (targetMap.py:43-62) for the pose (px, py, phi): the cells xs <= i < xe, ys <= j < ye it
+// tests - the upper bounds are EXCLUSIVE, as the reference's ranges are.  Shared by ig_visible_block and the heading-resolved view
+// gains (cagym_ig_headings.h), which must count the very same cells.  ig_visible_box_sc: from the sines and cosines of phi, phi + fov
+// and phi - fov (the heading kernel evaluates them once per launch, not once per viewpoint); ig_visible_box: those first.
+__device__ __forceinline__ void ig_visible_box_sc(double px, double py, double range, double s, double c, double sl, double cl, double sr,
+                                                  double cr, int& xs, int& ys, int& xe, int& ye) {
+    int cx[4] = {ig_bel_cell(px), ig_bel_cell(ig_clamp(px + range * c)), ig_bel_cell(ig_clamp(px + range * cl)),
+                 ig_bel_cell(ig_clamp(px + range * cr))};
+    int cy[4] = {ig_bel_cell(py), ig_bel_cell(ig_clamp(py + range * s)), ig_bel_cell(ig_clamp(py + range * sl)),
+                 ig_bel_cell(ig_clamp(py + range * sr))};
+    xs = min(min(cx[0], cx[1]), min(cx[2], cx[3])), xe = max(max(cx[0], cx[1]), max(cx[2], cx[3]));
+    ys = min(min(cy[0], cy[1]), min(cy[2], cy[3])), ye = max(max(cy[0], cy[1]), max(cy[2], cy[3]));
+    xs = max(xs, 0);
+    ys = max(ys, 0);
+    xe = min(xe, IG_BEL);
+    ye = min(ye, IG_BEL);
+}
+__device__ __forceinline__ void ig_visible_box(double px, double py, double phi, double fov, double range, double& s, double& c,
+                                               int& xs, int& ys, int& xe, int& ye) {
+    ig_sincos(phi, &s, &c);
+    double sl, cl, sr, cr;
+    ig_sincos(phi + fov, &sl, &cl);
+    ig_sincos(phi - fov, &sr, &cr);
+    ig_visible_box_sc(px, py, range, s, c, sl, cl, sr, cr, xs, ys, xe, ye);
+}
+
 // targetMap.getVisibleCells (targetMap.py:43-84), computed by all `nthreads` threads of a block into the
 // LDS mask `vis[60]` (zeroed here).  Ends with a barrier.
 __device__ inline void ig_visible_block(const uint32_t* d2, double px, double py, double phi, double fov, double range,
@@ -147,20 +173,8 @@ __device__ inline void ig_visible_block(const uint32_t* d2, double px, double py
     for (int j = tid; j < IG_BEL; j += nthreads) vis[j] = 0ull;
     __syncthreads();
     double s, c;
-    ig_sincos(phi, &s, &c);
-    double sl, cl, sr, cr;
-    ig_sincos(phi + fov, &sl, &cl);
-    ig_sincos(phi - fov, &sr, &cr);
-    int cx[4] = {ig_bel_cell(px), ig_bel_cell(ig_clamp(px + range * c)), ig_bel_cell(ig_clamp(px + range * cl)),
-                 ig_bel_cell(ig_clamp(px + range * cr))};
-    int cy[4] = {ig_bel_cell(py), ig_bel_cell(ig_clamp(py + range * s)), ig_bel_cell(ig_clamp(py + range * sl)),
-                 ig_bel_cell(ig_clamp(py + range * sr))};
-    int xs = min(min(cx[0], cx[1]), min(cx[2], cx[3])), xe = max(max(cx[0], cx[1]), max(cx[2], cx[3]));
-    int ys = min(min(cy[0], cy[1]), min(cy[2], cy[3])), ye = max(max(cy[0], cy[1]), max(cy[2], cy[3]));
-    xs = max(xs, 0);
-    ys = max(ys, 0);
-    xe = min(xe, IG_BEL);
-    ye = min(ye, IG_BEL);
+    int xs, ys, xe, ye;
+    ig_visible_box(px, py, phi, fov, range, s, c, xs, ys, xe, ye);
     const int w = xe - xs, h = ye - ys;
     const int total = (w > 0 && h > 0) ? w * h : 0;
     const IgCone cn = cone ? *cone : ig_cone(fov);

@@ -211,6 +211,72 @@ class InfoGain(object):
                   *[out[n].data_ptr() for n in ("cells", "xy", "utility", "gain", "distance", "n_found")], self.b._stream())
         return out
 
+    def heading_list(self, headings):
+        """The headings a caller means: an int H is h * 2 pi / H for h = 0..H-1, computed in fp64 here; a sequence is taken as
+        given (radians).  Returns a list of 1..16 floats."""
+        if isinstance(headings, (int, np.integer)) and not isinstance(headings, bool):
+            H = int(headings)
+            if H < 1 or H > 16:
+                raise ValueError("headings: H must be within 1..16, got %d" % H)
+            return [h * 2.0 * math.pi / H for h in range(H)]
+        hs = [float(v) for v in (headings.tolist() if hasattr(headings, "tolist") else headings)]
+        if not 1 <= len(hs) <= 16:
+            raise ValueError("headings: 1..16 headings, got %d" % len(hs))
+        return hs
+
+    def view_gain_headings(self, points=None, headings=8, world_mask=None, radius=0.5, range=None, out=None, want_rows=True):
+        """cagym_ig_view_gain_headings: ONE launch on the current stream - what a POSE is worth: view_gain() for the sensor cone
+        (this object's fov) at H headings per point.  For heading h the counted cells are exactly visible_cells() of the pose
+        (x, y, headings[h]); every cell is traced once and shared by the H cones (ig.view_gain_headings_spec states the rule).
+        points, world_mask, radius, range: as view_gain().  headings: an int H (h * 2 pi / H) or a sequence of 1..16 radians.
+        Returns the dict of device tensors it wrote: gain_h f64 and n_visible_h i32 [N,P,H], best_heading i32 (the first index of
+        the largest gain_h; -1: invalid), best_gain f64 (that value bit for bit) and valid u8 [N,P] - [N,60,60,H] and [N,60,60]
+        indexed [j, i] for the map - and "headings", the list used.  want_rows=False: the two [.., H] tensors are not written
+        (NULL) and not returned.  `out`: a dict of such tensors to write into again (default: new tensors; with want_rows=True it
+        must hold the two rows), which itself is left as it is: the result is a new dict of the same tensors."""
+        N, dev = self.b.N, self.b.device
+        hs = self.heading_list(headings)
+        H = len(hs)
+        if points is not None:
+            if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()):
+                points = self._t(points, torch.float64)
+            points = points.reshape(N, -1, 2)
+            shape = (N, points.shape[1])
+        else:
+            shape = (N, 60, 60)
+        if world_mask is not None:
+            world_mask = self._t(world_mask, torch.uint8, (N,))
+        if out is None:
+            out = {"best_heading": torch.empty(shape, dtype=torch.int32, device=dev),
+                   "best_gain": torch.empty(shape, dtype=torch.float64, device=dev),
+                   "valid": torch.empty(shape, dtype=torch.uint8, device=dev)}
+            if want_rows:
+                out["gain_h"] = torch.empty(shape + (H,), dtype=torch.float64, device=dev)
+                out["n_visible_h"] = torch.empty(shape + (H,), dtype=torch.int32, device=dev)
+        rows = [out.get("gain_h"), out.get("n_visible_h")] if want_rows else [None, None]
+        if want_rows and (rows[0] is None or rows[1] is None):
+            raise ValueError("view_gain_headings: want_rows=True needs out['gain_h'] and out['n_visible_h']")
+        for t in rows:
+            if t is not None and t.shape[-1] != H:
+                raise ValueError("view_gain_headings: out's rows hold %d headings, asked for %d" % (t.shape[-1], H))
+        P = _lib.IgHeadingParams(shape[1] if points is not None else 0, H, 0, float(radius), float(self.range if range is None else range),
+                                 self.fov, (C.c_double * 16)(*hs))
+        _lib.call(self.L, self.b.h, "cagym_ig_view_gain_headings", C.byref(P), _lib.ptr(world_mask), _lib.ptr(points), _lib.ptr(rows[0]),
+                  _lib.ptr(rows[1]), out["best_heading"].data_ptr(), out["best_gain"].data_ptr(), out["valid"].data_ptr(), self.b._stream())
+        return dict(out, headings=hs)  # (a new dict: the caller's `out` gains no key)
+
+    def goal_face_actions(self, params, goals, goal_heading, actions):
+        """cagym_ig_goal_face_actions: directly behind goal_actions() - the rows of the robots that stand within goal_tol of an
+        active goal with a finite goal_heading [N,R] f64 become (0, clip(wrap(goal_heading - heading) / dt, -w_max, w_max))."""
+        _lib.call(self.L, self.b.h, "cagym_ig_goal_face_actions", C.byref(params), goals["goal_xy"].data_ptr(), goals["active"].data_ptr(),
+                  goal_heading.data_ptr(), actions.data_ptr(), self.b._stream())
+
+    def goal_face_status(self, params, goals, goal_heading, goal_facing, face_tol):
+        """cagym_ig_goal_face_status: directly behind goal_status() - goal_facing [N,R] u8 = 1 for a robot within goal_tol of an
+        active goal that has no finite goal heading or faces it within face_tol."""
+        _lib.call(self.L, self.b.h, "cagym_ig_goal_face_status", C.byref(params), float(face_tol), goals["goal_xy"].data_ptr(),
+                  goals["active"].data_ptr(), goal_heading.data_ptr(), goal_facing.data_ptr(), self.b._stream())
+
     def visible_cells(self, poses, world):
         poses = self._t(poses, torch.float64, (-1, 3))
         world = self._t(world, torch.int32, (-1,))
@@ -642,6 +708,83 @@ def view_gain_spec(edf, mi, point, radius, range=5.0):
     seen = check_visibility_spec(edf, (x, y), cx[near], cy[near])
     vis[jj[near][seen], ii[near][seen]] = True
     return math.fsum(mi[vis]), int(vis.sum()), True, vis, inr
+
+
+def view_gain_headings_spec(edf, mi, point, headings, radius, fov, range):
+    """The heading-resolved view gains of cagym_ig_view_gain_headings for one point of one world, in numpy - their specification.
+    edf, mi, point, radius: as view_gain_spec; headings: a sequence of H radians; fov: the cone's full opening angle; range: the
+    sensing range.  Returns a dict: gain_h [H] f64, n_visible_h [H] i32, best_heading, best_gain, valid and masks [H, 60, 60]
+    bool indexed [h, j, i].
+      valid: view_gain_spec's rule; an invalid point has zero rows, best_heading -1 and best_gain 0.
+      For heading phi the counted cells are targetMap.getVisibleCells of the pose (x, y, phi), written out:
+        box: with the four points p, p + range (cos, sin)(phi), p + range (cos, sin)(phi + fov), p + range (cos, sin)(phi - fov),
+          each coordinate clamped to +-15, and cell(v) = floor((v + 15) / 0.5): i in max(0, min cell) .. min(60, max cell) - 1, the
+          upper bound EXCLUSIVE, j likewise;
+        cone: r0 = c dx + s dy, r1 = -s dx + c dy with dx = centre - x; inside <=> sqrt(r0 r0 + r1 r1) < range and
+          |atan2(r1 + 0.0, r0 + 0.0)| < fov / 2;
+        visible <=> check_visibility_spec(point, centre) - which does not depend on the heading: every cell is traced once.
+      gain_h = math.fsum of mi over the heading's cells, n_visible_h their number; best_heading = the first index of the largest
+      gain_h.  (Sine and cosine are the C library's here and ig_sincos on the device: a cell exactly on a cone edge or on the range
+      circle may be decided differently; headings h 2 pi / 8 or / 16 with range 4.9 or 2.3 keep every cell of a cell-centre
+      viewpoint at least 4e-3 rad and 2e-2 m off.)"""
+    mi = np.asarray(mi, dtype=np.float64).reshape(60, 60)
+    hs = [float(h) for h in headings]
+    H = len(hs)
+    x, y, rng, fov = float(point[0]), float(point[1]), float(range), float(fov)
+    out = {"gain_h": np.zeros(H), "n_visible_h": np.zeros(H, dtype=np.int32), "best_heading": -1, "best_gain": 0.0, "valid": False,
+           "masks": np.zeros((H, 60, 60), dtype=bool)}
+    if not (math.isfinite(x) and math.isfinite(y)):
+        return out
+    cell = lambda v: int(min(max(math.floor((v + 15.0) / 0.5), -10 ** 6), 10 ** 6))
+    clamp = lambda v: max(min(v, 15.0), -15.0)
+    if not (0 <= cell(x) < 60 and 0 <= cell(y) < 60) or not float(edf_at_spec(edf, x, y)) > float(radius) + 0.1:
+        return out
+    out["valid"] = True
+    inside = np.zeros((H, 60, 60), dtype=bool)
+    for h, phi in enumerate(hs):
+        s, c = math.sin(phi), math.cos(phi)
+        sl, cl, sr, cr = math.sin(phi + fov), math.cos(phi + fov), math.sin(phi - fov), math.cos(phi - fov)
+        cxs = [cell(x), cell(clamp(x + rng * c)), cell(clamp(x + rng * cl)), cell(clamp(x + rng * cr))]
+        cys = [cell(y), cell(clamp(y + rng * s)), cell(clamp(y + rng * sl)), cell(clamp(y + rng * sr))]
+        xs, xe, ys, ye = max(min(cxs), 0), min(max(cxs), 60), max(min(cys), 0), min(max(cys), 60)
+        if xe <= xs or ye <= ys:
+            continue
+        jj, ii = np.meshgrid(np.arange(ys, ye), np.arange(xs, xe), indexing="ij")
+        dx, dy = (ii * 0.5 - 15.0 + 0.25) - x, (jj * 0.5 - 15.0 + 0.25) - y
+        r0, r1 = c * dx + s * dy, -s * dx + c * dy
+        ok = (np.sqrt(r0 * r0 + r1 * r1) < rng) & (np.abs(np.arctan2(r1 + 0.0, r0 + 0.0)) < fov / 2)
+        inside[h, jj[ok], ii[ok]] = True
+    jall, iall = np.nonzero(inside.any(axis=0))
+    seen = np.zeros((60, 60), dtype=bool)
+    if len(jall):
+        seen[jall, iall] = check_visibility_spec(edf, (x, y), iall * 0.5 - 15.0 + 0.25, jall * 0.5 - 15.0 + 0.25)
+    out["masks"] = inside & seen[None]
+    for h in np.arange(H):
+        out["gain_h"][h] = math.fsum(mi[out["masks"][h]])
+        out["n_visible_h"][h] = int(out["masks"][h].sum())
+    out["best_heading"] = int(np.argmax(out["gain_h"]))  # (the first of equal maxima)
+    out["best_gain"] = float(out["gain_h"][out["best_heading"]])
+    return out
+
+
+def goal_face_spec(pose, goal_xy, goal_heading, dt, w_max, goal_tol, face_tol):
+    """cagym_ig_goal_face_actions and cagym_ig_goal_face_status for one robot with an ACTIVE goal, in plain fp64 - their bit-exact
+    specification.  pose (x, y, heading), goal_xy the goal point, goal_heading in radians or NaN: none.  Returns (row, reached,
+    facing): row is None when the robot's row keeps its bytes, else (0.0, omega) in fp64 (the library stores (float)omega).
+      reached = sqrt(dx dx + dy dy) <= goal_tol, the test on which goal_action_spec stops the robot;
+      err = wrap(goal_heading - heading), wrap(a) = (a + pi) % (2 pi) - pi, goal_action_spec's; the short way across +-pi;
+      row = (0, clip(err / dt, -w_max, w_max)) when reached and the goal heading is finite;
+      facing = reached and (the goal heading is not finite or |err| <= face_tol)."""
+    x, y, th = (float(v) for v in pose)
+    dx, dy = float(goal_xy[0]) - x, float(goal_xy[1]) - y
+    reached = math.sqrt(dx * dx + dy * dy) <= goal_tol
+    gh = float(goal_heading)
+    if not math.isfinite(gh):
+        return None, reached, reached
+    err = (gh - th + np.pi) % (2 * np.pi) - np.pi
+    if not reached:
+        return None, False, False
+    return (0.0, min(max(err / dt, -w_max), w_max)), True, abs(err) <= face_tol
 
 
 def propose_goals_spec(gain, valid, field, k, min_sep, d0):

@@ -617,6 +617,44 @@ int cagym_ig_propose_goals(void* env, const cagym_ig_view_params* params, const 
                            const uint8_t* valid_map, const float* field, int32_t* cells, double* xy, double* utility, double* gain,
                            float* distance, int32_t* n_found, void* stream);
 
+/* ---- Heading-resolved view gains, goal headings and facing: what a POSE is worth, and a goal that says which way to look -----------
+ * On `stream`, on demand or opt-in, no host synchronisation, no global atomics, barriers only.
+ *
+ * cagym_ig_view_gain_headings: cagym_ig_view_gain for a sensor cone.  params: cagym_ig_heading_params, defined in
+ * include/cagym_ig_headings.h (n_points = P, n_headings = H 1..16, flags = 0, radius, range, fov, headings[16] in radians).
+ * points_xy DEVICE [N,P,2] f64 or NULL (the 3600 cell centres, outputs then [N,60,60,..] indexed [j, i], values those of a points
+ * call bit for bit) and world_mask DEVICE [N] u8 or NULL as cagym_ig_view_gain takes them.  Outputs, DEVICE: gain_h [N,P,H] f64 and
+ * n_visible_h [N,P,H] i32, either may be NULL; best_heading [N,P] i32, best_gain [N,P] f64, valid [N,P] u8.
+ *   valid: cagym_ig_view_gain's rule (finite, inside the map, EDF(x, y) > radius + 0.1).
+ *   For a valid point and heading h the counted cells are exactly the mask cagym_ig_visible_cells returns for the pose
+ *     (x, y, headings[h]) on the world's current scenario slot with this fov and range: the box with its exclusive upper bound, the
+ *     rotation, the cone test `rn < range and |atan2(r1, r0)| < fov / 2` and the sphere trace are the same device functions.
+ *   n_visible_h = their number, gain_h = the sum of the MI cache's values over them: per lane in candidate order (row-major over
+ *     cell(p - range) .. cell(p + range), lane = candidate mod 64), the 64 lanes in a fixed tree - the same bits on every call.
+ *   best_heading = the first index of the largest gain_h, best_gain = that value bit for bit.
+ *   An invalid point: best_heading -1, best_gain 0, gain_h and n_visible_h rows 0.
+ * Errors, before anything is touched: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params, best_heading, best_gain
+ * or valid, n_points < 0, n_headings outside 1..16, flags != 0, a radius, range or fov that is not finite or not positive, a heading
+ * among the first n_headings that is not finite, more than 2^31 - 1 workgroups; CAGYM_E_DEVICE as every launching entry.
+ *
+ * cagym_ig_goal_face_actions: directly behind cagym_ig_goal_actions, with its params, goal_xy, active and actions; goal_heading
+ * DEVICE [N,R] f64 radians, NaN = none.  A robot with an active goal, a finite goal heading and sqrt(dx dx + dy dy) <= goal_tol -
+ * the predicate on which cagym_ig_goal_actions stops it - gets the row (0, clip(wrap(goal_heading - heading) / dt, -w_max, w_max)),
+ * wrap(a) = (a + pi) mod 2 pi - pi, computed in fp64 and stored as f32; every other row keeps its bytes.
+ *
+ * cagym_ig_goal_face_status: directly behind cagym_ig_goal_status, on the `active` it left.  goal_facing DEVICE [N,R] u8 = 1 when the
+ * robot is active, within goal_tol of its goal point, and either has no finite goal heading or |wrap(goal_heading - heading)| <=
+ * face_tol (radians, by value; finite, > 0, else CAGYM_E_INVALID).
+ * Errors of the two: as cagym_ig_goal_actions / cagym_ig_goal_status. */
+typedef struct cagym_ig_heading_params cagym_ig_heading_params;
+int cagym_ig_view_gain_headings(void* env, const cagym_ig_heading_params* params, const uint8_t* world_mask, const double* points_xy,
+                                double* gain_h, int32_t* n_visible_h, int32_t* best_heading, double* best_gain, uint8_t* valid,
+                                void* stream);
+int cagym_ig_goal_face_actions(void* env, const cagym_ig_goal_params* params, const double* goal_xy, const uint8_t* active,
+                               const double* goal_heading, float* actions, void* stream);
+int cagym_ig_goal_face_status(void* env, const cagym_ig_goal_params* params, double face_tol, const double* goal_xy,
+                              const uint8_t* active, const double* goal_heading, uint8_t* goal_facing, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
