@@ -17,6 +17,14 @@
 // measures 2.6e-6 / 8.2e-6 and 4 % slower (profiles/r4/ga3c16_ab.txt).  Activations are clamped to the f16 range (65 504) before
 // the split; the network's are below 100.
 //
+// Beyond the f16 range.  The NORMALISED inputs (x - avg) / std are clamped to +-65 504 as well (ga16_clamp, once per tile, off the
+// LSTM loop): an input of 4e5 m behaves exactly like one of 65 504 std (327 520 m for the distances), where the unclamped split
+// (hi = f16(v) = inf, lo = f16(v - hi)) measured finite probabilities but action 1 against the fp32 kernels' 5.  Inside the range the
+// kernel keeps its fp32-class accuracy as long as no ReLU output exceeds 65 504 in turn: measured with normalised inputs of 6e4
+// (dist_to_goal = 3e5 m, observed agents at +-3e5 m; layer activations up to 4.1e4) max |p - p_fp64| is the fp32 kernels' 4.7e-8.  An input that drives an activation past 65 504
+// saturates there and the action may differ from the fp32 kernels' - e.g. dist_to_goal = -3e5, which no state row holds (it is a
+// norm): layer1 reaches 1.0e5 (tests/test_ga3c_crowded.py).
+//
 // Orientation.  D[neuron][agent] = W^T[neuron][k] * X[k][agent]: the WEIGHTS are the A operand (row = output neuron), the layer
 // input the B operand (column = agent).  A lane of the 32 x 32 result then holds ONE agent (its column) and 16 neurons (its
 // registers) - and the B operand of the next layer's K-step wants, per lane, 8 consecutive k of ONE agent: exactly registers
@@ -67,6 +75,8 @@ __device__ __forceinline__ void ga16_split(float v, _Float16& hi, _Float16& lo) 
     hi = (_Float16)v;
     lo = (_Float16)((v - (float)hi) * GA16_SC);  // both operations exact
 }
+// a value on its way into the split, kept inside the f16 range: beyond it hi would be +-inf and lo = v - hi = -+inf
+__device__ __forceinline__ float ga16_clamp(float v) { return fminf(fmaxf(v, -65504.f), 65504.f); }
 
 // The gates' non-linearities are evaluated as rcp(1 + exp2(.)): sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 1 - 2 / (1 + 2^(2 x log2 e)).
 // The factor in front of x is folded into the packed LSTM kernel and bias (gate order i, j, f, o; the forget gate's + 1.0 - TF1's
@@ -307,7 +317,7 @@ __device__ __forceinline__ void ga16_forward_tile(const unsigned char* __restric
             for (int f = 1; f < 5; f++) {
                 const float avg = f == 3 ? 1.0f : (f == 4 ? 0.5f : 0.0f);
                 const float sd = f == 1 ? 5.0f : (f == 2 ? 3.14f : 1.0f);
-                ga16_split((x[f] - avg) / sd, hi.f[f - 1], lo.f[f - 1]);
+                ga16_split(ga16_clamp((x[f] - avg) / sd), hi.f[f - 1], lo.f[f - 1]);
             }
             *reinterpret_cast<uint4*>(hostf + g * 16) = hi.u;
             *reinterpret_cast<uint4*>(hostf + 512 + g * 16) = lo.u;
@@ -316,7 +326,7 @@ __device__ __forceinline__ void ga16_forward_tile(const unsigned char* __restric
             for (int c = 0; c < 7; c++) {
                 const float avg = c == 4 ? 0.5f : (c == 6 ? 1.0f : 0.0f);
                 const float sd = (c == 0 || c == 1 || c == 5) ? 5.0f : 1.0f;
-                ga16_split((x[c] - avg) / sd, hi.f[c], lo.f[c]);
+                ga16_split(ga16_clamp((x[c] - avg) / sd), hi.f[c], lo.f[c]);
             }
             *reinterpret_cast<uint4*>(xf + t * 1024 + g * 16) = hi.u;
             *reinterpret_cast<uint4*>(xf + t * 1024 + 512 + g * 16) = lo.u;

@@ -66,12 +66,14 @@ def _mm_split(x, Wm):
 
 def forward_split_f16(W, x75, split=True):
     """The forward pass in the arithmetic of k_ga3c_forward_h16 (fp32 everywhere, matrix products on split f16 operands, fp32
-    accumulation, activations clamped to the f16 range); split=False: the same in plain fp32 (the arithmetic of the exact-fp32
+    accumulation, normalised inputs and activations clamped to the f16 range); split=False: the same in plain fp32 (the arithmetic of the exact-fp32
     kernels).  Returns softmax_p [B, 11] (float64 view of fp32 results)."""
     f32 = np.float32
     _mm = _mm_split if split else (lambda a, b: (np.asarray(a, f32) @ np.asarray(b, f32)).astype(f32))
     x = np.asarray(x75, dtype=f32)
     xn = ((x - AVG.astype(f32)) / STD.astype(f32)).astype(f32)
+    if split:  # the kernel keeps its normalised inputs inside the f16 range, like its activations
+        xn[:, 1:] = np.clip(xn[:, 1:], f32(-65504), f32(65504))
     B = x.shape[0]
     n = x[:, 0].astype(np.int64)
     h = np.zeros((B, 64), f32)

@@ -567,6 +567,81 @@ def ga3c_states():
     print("%-28s          %8.1f KB" % ("ga3c_states", os.path.getsize(path) / 1024))
 
 
+def tie_world(M):
+    """Everyone drives in +x at the same speed: agent 0 from the origin, the others in groups of four at (+-x_k, +-y_k),
+    x_k = 1.5 + 0.75 k, y_k = 1.0 + 0.5 k, each to its start + (12, 0).  Agent 0's frame is exactly (1, 0) / (0, 1), so p_orth of a
+    member stays exactly +-y_k: the front / back members of a side tie in BOTH sort keys (index order decides, and the slot order
+    within a group rotates with k so that it is not always the same member), the left / right sides tie in round(d, 2) only.
+    Radii are exact binary fractions: agent 0's own, one for the even groups and one for the odd groups.  d holds the radius, so
+    the members of a group cannot differ without losing agent 0's ties, and a member of group k sees groups k - 1 and k + 1 of its
+    side at the same d (a first-key tie for every agent, not only agent 0) because the two share a radius."""
+    w = np.zeros((M, 6))
+    w[0] = [0.0, 0.0, 12.0, 0.0, 1.0, 0.25]
+    corners = [(1, 1), (-1, 1), (1, -1), (-1, -1)]
+    for s in range(1, M):
+        k, m = (s - 1) // 4, (s - 1) % 4
+        cx, cy = corners[(m + k) % 4]
+        x, y = cx * (1.5 + 0.75 * k), cy * (1.0 + 0.5 * k)
+        w[s] = [x, y, x + 12.0, y, 1.0, 0.125 + (k % 2) / 16.0]
+    return w
+
+
+def ga3c_states_crowded():
+    """ga3c_states() with MORE agents than the state vector observes (the clip sorted_inds[-MAX_NUM_OTHER_AGENTS_OBSERVED:] of
+    policies/GA3CCADRLPolicy.py:69 drops the farthest ones on every step), 17 .. 32 agents, and worlds built to tie in the sort key.
+    The random worlds carry a different radius (an exact binary fraction) per agent, so that column r_other of a row names the agent;
+    two agents of m24 stand on their goals (dist_to_goal = 0: the unnormalised ref_prll of agent.py)."""
+    with rh.quiet():
+        from gym_collision_avoidance.envs.policies.GA3CCADRLPolicy import GA3CCADRLPolicy
+    U, NC = scen.DYN_UNICYCLE, scen.POLICY_NONCOOP
+    out = {}
+    saved = (Config.MAX_NUM_AGENTS_IN_ENVIRONMENT, Config.MAX_NUM_OTHER_AGENTS_OBSERVED)
+
+    class Dummy(object):
+        pass
+    steps = 8
+    for name, M, observed, seed in (("m14", 14, 9, 31), ("m24", 24, 10, 32), ("m32", 32, 10, 33), ("m17o1", 17, 1, 34),
+                                    ("tie17", 17, 10, None), ("tie32", 32, 10, None)):
+        if seed is None:
+            w = tie_world(M)
+        else:
+            w = scen.random_world(np.random.default_rng(seed), M)
+            w[:, 5] = 0.25 + np.arange(M) / 128.0
+        if name == "m24":
+            w[5, 2:4] = w[5, 0:2]
+            w[17, 2:4] = w[17, 0:2]
+        set_max_agents(M)
+        Config.MAX_NUM_OTHER_AGENTS_OBSERVED = observed
+        Config.EVALUATE_MODE = True
+        with rh.quiet():
+            agents = [Agent(w[i, 0], w[i, 1], w[i, 2], w[i, 3], w[i, 5], w[i, 4],
+                            np.float64(np.arctan2(w[i, 3] - w[i, 1], w[i, 2] - w[i, 0])), POLICIES[NC], DYNAMICS[U],
+                            [OtherAgentsStatesSensor], i) for i in range(M)]
+            for a in agents:
+                a.policy.targetMap = None
+            env = OracleEnv()
+            env.set_agents(agents)
+            env.reset()
+        states = []
+        for t in range(steps + 1):
+            if t:
+                with rh.quiet():
+                    env.step({})
+            st = np.zeros((M, 76))
+            for i in range(M):
+                st[i] = GA3CCADRLPolicy.agents_to_ga3c_cadrl_state(Dummy(), env.agents[i],
+                                                                   env.agents[:i] + env.agents[i + 1:])
+            states.append(st)
+        out[name + "__agents6"] = w
+        out[name + "__max_observed"] = np.array(observed)
+        out[name + "__states"] = np.array(states)
+    set_max_agents(saved[0])
+    Config.MAX_NUM_OTHER_AGENTS_OBSERVED = saved[1]
+    path = os.path.join(OUT, "ga3c_states_crowded.npz")
+    np.savez_compressed(path, **out)
+    print("%-28s          %8.1f KB" % ("ga3c_states_crowded", os.path.getsize(path) / 1024))
+
+
 def dmcts_reference(n_seeds=6, n_steps=6):
     """Cumulative team reward of the reference's own Dec-MCTS loop (experiments/src/dmcts.py:50-95) on its
     default scenario IG_agent_crossing with a tiny planning budget, for a few np.random seeds.  The planner uses
@@ -794,6 +869,8 @@ if __name__ == "__main__":
         scenario_statistics()
     elif "--ga3c-only" in only:
         ga3c_states()
+    elif "--ga3c-crowded-only" in only:
+        ga3c_states_crowded()
     elif "--adapters-only" in only:
         adapters()
     elif "--ig-only" in only:
@@ -810,6 +887,7 @@ if __name__ == "__main__":
         ga3c_episodes()
         ig_primitives()
         ga3c_states()
+        ga3c_states_crowded()
         dmcts_reference()
         scenario_statistics()
         adapters()
