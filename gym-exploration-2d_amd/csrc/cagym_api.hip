@@ -1970,6 +1970,33 @@ static int ig_robots_check(Env* e, int n_robots, const char* what) {
     return CAGYM_OK;
 }
 
+// The argument checks the learner entries share; `name`: the entry, for the message.  Which of two errors wins is part of the ABI
+// (tests/test_ig_learner_refusals.py): the team's range is checked in front of a parameter block, the pool's team (ig_robots_check) behind it.
+static int ig_team_check(Env* e, const std::string& name, int n_robots) {
+    return (n_robots < 1 || n_robots > IG_MAXR) ? fail(e, CAGYM_E_INVALID, name + ": n_robots must be 1..8") : CAGYM_OK;
+}
+static int ig_flags_check(Env* e, const std::string& name, uint32_t flags, uint32_t known) {
+    return (flags & ~known) ? fail(e, CAGYM_E_INVALID, name + ": unknown flags") : CAGYM_OK;
+}
+// the head of a window's parameter block: team, window, rotate, flags
+static int ig_frame_check(Env* e, const std::string& name, int n_robots, int window, int rotate, uint32_t flags, uint32_t known) {
+    if (int rc = ig_team_check(e, name, n_robots)) return rc;
+    if (window < 4 || window > 64 || (window & 1)) return fail(e, CAGYM_E_INVALID, name + ": window must be even and within 4..64");
+    if (rotate != 0 && rotate != 1) return fail(e, CAGYM_E_INVALID, name + ": rotate must be 0 or 1");
+    return ig_flags_check(e, name, flags, known);
+}
+static int ig_positive_check(Env* e, const std::string& name, std::initializer_list<double> values, const char* what) {
+    for (double v : values)
+        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
+            return fail(e, CAGYM_E_INVALID, name + ": " + what);
+    return CAGYM_OK;
+}
+// the workgroups of a view-gain launch: IGV_PER_WG viewpoints of one world each (no int sum near INT_MAX); refused beyond one launch
+static int igv_blocks(Env* e, const std::string& name, int n_points, long long* blocks) {
+    *blocks = (long long)e->cfg.n_worlds * (((long long)n_points + IGV_PER_WG - 1) / IGV_PER_WG);
+    return *blocks > 0x7fffffffll ? fail(e, CAGYM_E_INVALID, name + ": n_worlds * n_points is too large for one launch") : CAGYM_OK;
+}
+
 int cagym_ig_robot_inputs(void* env, int n_robots, double detect_range, const float* obs_oas, double* poses, double* detections,
                           int32_t* n_det, void* stream) {
     ENTRY(e, env);
@@ -2093,12 +2120,11 @@ int cagym_ig_greedy_plan(void* env, const cagym_ig_greedy_params* params, const 
     ON_DEVICE(e);
     if (!params || !poses || !actions || !choice) return fail(e, CAGYM_E_INVALID, "null argument");
     const cagym_ig_greedy_params& p = *params;
-    if (p.n_robots < 1 || p.n_robots > DM_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: n_robots must be 1..8");
+    if (int rc = ig_team_check(e, "cagym_ig_greedy_plan", p.n_robots)) return rc;
     if (p.coordinate != 0 && p.coordinate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: coordinate must be 0 or 1");
-    // (the negated comparisons refuse NaN)
-    if (!(p.dt > 0.0 && p.fov_rad > 0.0 && p.range > 0.0 && p.radius >= 0.0) || !std::isfinite(p.dt) || !std::isfinite(p.fov_rad) ||
-        !std::isfinite(p.range) || !std::isfinite(p.radius))
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: dt, fov_rad and range must be finite and positive, radius finite and not negative");
+    const char* what = "dt, fov_rad and range must be finite and positive, radius finite and not negative";
+    if (int rc = ig_positive_check(e, "cagym_ig_greedy_plan", {p.dt, p.fov_rad, p.range}, what)) return rc;
+    if (!(p.radius >= 0.0) || !std::isfinite(p.radius)) return fail(e, CAGYM_E_INVALID, std::string("cagym_ig_greedy_plan: ") + what);
     for (int k = 0; k < 3; k++)
         if (!std::isfinite(p.v[k]) || !std::isfinite(p.w[k])) return fail(e, CAGYM_E_INVALID, "cagym_ig_greedy_plan: non-finite candidate");
     IgGreedyParams P;
@@ -2117,16 +2143,11 @@ int cagym_ig_observe(void* env, const cagym_ig_observe_params* params, const flo
     ENTRY_IG(e, env, "cagym_ig_observe");
     if (!params || !obs_oas) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: null argument");
     const cagym_ig_observe_params& p = *params;
-    if (p.n_robots < 1 || p.n_robots > IGO_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: n_robots must be 1..8");
-    if (p.window < 4 || p.window > 64 || (p.window & 1)) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: window must be even and within 4..64");
-    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: rotate must be 0 or 1");
-    if (p.flags & ~(uint32_t)(CAGYM_IG_EPISODE_FOLD | CAGYM_IG_OBSERVE_ONLY_RESTARTED))
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: unknown flags");
-    // (the negated comparison refuses NaN)
-    if (!(p.fov_rad > 0.0 && p.range > 0.0 && p.detect_range > 0.0) || !std::isfinite(p.fov_rad) || !std::isfinite(p.range) ||
-        !std::isfinite(p.detect_range))
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_observe: fov_rad, range and detect_range must be finite and positive");
-    if (int rc = ig_robots_check(e, p.n_robots, "cagym_ig_observe")) return rc;
+    const char* name = "cagym_ig_observe";
+    if (int rc = ig_frame_check(e, name, p.n_robots, p.window, p.rotate, p.flags, CAGYM_IG_EPISODE_FOLD | CAGYM_IG_OBSERVE_ONLY_RESTARTED)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.fov_rad, p.range, p.detect_range}, "fov_rad, range and detect_range must be finite and positive"))
+        return rc;
+    if (int rc = ig_robots_check(e, p.n_robots, name)) return rc;
     ON_DEVICE(e);
     IgObserveParams P;
     P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.det_range = (float)p.detect_range; P.fov = p.fov_rad; P.range = p.range;
@@ -2141,14 +2162,10 @@ int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, co
     ENTRY_IG(e, env, "cagym_ig_context_window");
     if (!params || !context_window) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: null argument");
     const cagym_ig_context_params& p = *params;
-    if (p.n_robots < 1 || p.n_robots > IGC_MAXR) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: n_robots must be 1..8");
-    if (p.window < 4 || p.window > 64 || (p.window & 1))
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: window must be even and within 4..64");
-    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: rotate must be 0 or 1");
-    if (p.flags & ~(uint32_t)CAGYM_IG_CONTEXT_ONLY_MASKED) return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: unknown flags");
-    if (!(p.clear_max > 0.0) || !std::isfinite(p.clear_max))  // (the negated comparison refuses NaN)
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_context_window: clear_max must be finite and positive");
-    if (int rc = ig_robots_check(e, p.n_robots, "cagym_ig_context_window")) return rc;
+    const char* name = "cagym_ig_context_window";
+    if (int rc = ig_frame_check(e, name, p.n_robots, p.window, p.rotate, p.flags, CAGYM_IG_CONTEXT_ONLY_MASKED)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.clear_max}, "clear_max must be finite and positive")) return rc;
+    if (int rc = ig_robots_check(e, p.n_robots, name)) return rc;
     ON_DEVICE(e);
     IgContextParams P;
     P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.clear_max = p.clear_max;
@@ -2164,14 +2181,10 @@ static int ig_goal_params_check(Env* e, const cagym_ig_goal_params* params, cons
     const std::string n(name);
     if (!params) return fail(e, CAGYM_E_INVALID, n + ": null argument");
     const cagym_ig_goal_params& p = *params;
-    if (p.n_robots < 1 || p.n_robots > IGG_MAXR) return fail(e, CAGYM_E_INVALID, n + ": n_robots must be 1..8");
-    if (p.window < 4 || p.window > 64 || (p.window & 1)) return fail(e, CAGYM_E_INVALID, n + ": window must be even and within 4..64");
-    if (p.rotate != 0 && p.rotate != 1) return fail(e, CAGYM_E_INVALID, n + ": rotate must be 0 or 1");
-    if (p.flags) return fail(e, CAGYM_E_INVALID, n + ": unknown flags");
-    const double pos[6] = {p.radius, p.v_max, p.w_max, p.align_tol, p.goal_tol, p.dt};
-    for (double v : pos)
-        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
-            return fail(e, CAGYM_E_INVALID, n + ": radius, v_max, w_max, align_tol, goal_tol and dt must be finite and positive");
+    if (int rc = ig_frame_check(e, n, p.n_robots, p.window, p.rotate, p.flags, 0)) return rc;
+    if (int rc = ig_positive_check(e, n, {p.radius, p.v_max, p.w_max, p.align_tol, p.goal_tol, p.dt},
+                                   "radius, v_max, w_max, align_tol, goal_tol and dt must be finite and positive"))
+        return rc;
     if (int rc = ig_robots_check(e, p.n_robots, name)) return rc;
     P->R = p.n_robots; P->G = p.window; P->rotate = p.rotate;
     P->radius = p.radius; P->v_max = p.v_max; P->w_max = p.w_max; P->align_tol = p.align_tol; P->goal_tol = p.goal_tol; P->dt = p.dt;
@@ -2228,13 +2241,10 @@ static int ig_view_params_check(Env* e, const cagym_ig_view_params* params, cons
     if (!params) return fail(e, CAGYM_E_INVALID, n + ": null argument");
     const cagym_ig_view_params& p = *params;
     if (p.n_points < 0) return fail(e, CAGYM_E_INVALID, n + ": n_points must not be negative");
-    if (p.n_robots < 1 || p.n_robots > IGV_MAXR) return fail(e, CAGYM_E_INVALID, n + ": n_robots must be 1..8");
+    if (int rc = ig_team_check(e, n, p.n_robots)) return rc;
     if (p.k < 1 || p.k > IGV_MAXK) return fail(e, CAGYM_E_INVALID, n + ": k must be 1..16");
-    if (p.flags) return fail(e, CAGYM_E_INVALID, n + ": unknown flags");
-    const double pos[4] = {p.radius, p.range, p.min_sep, p.d0};
-    for (double v : pos)
-        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
-            return fail(e, CAGYM_E_INVALID, n + ": radius, range, min_sep and d0 must be finite and positive");
+    if (int rc = ig_flags_check(e, n, p.flags, 0)) return rc;
+    if (int rc = ig_positive_check(e, n, {p.radius, p.range, p.min_sep, p.d0}, "radius, range, min_sep and d0 must be finite and positive")) return rc;
     P->P = p.n_points; P->R = p.n_robots; P->k = p.k;
     P->radius = p.radius; P->range = p.range; P->min_sep = p.min_sep; P->d0 = p.d0;
     return CAGYM_OK;
@@ -2247,8 +2257,8 @@ int cagym_ig_view_gain(void* env, const cagym_ig_view_params* params, const uint
     IgViewParams P;
     if (int rc = ig_view_params_check(e, params, "cagym_ig_view_gain", &P)) return rc;
     if (!points_xy) P.P = IGV_CELLS;  // the map: the kernel generates the cell centres
-    const long long blocks = (long long)e->cfg.n_worlds * ((P.P + IGV_PER_WG - 1) / IGV_PER_WG);
-    if (blocks > 0x7fffffffll) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain: n_worlds * n_points is too large for one launch");
+    long long blocks;
+    if (int rc = igv_blocks(e, "cagym_ig_view_gain", P.P, &blocks)) return rc;
     ON_DEVICE(e);
     if (blocks == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_ig_view_gain, dim3((unsigned)blocks), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G, P,
@@ -2280,13 +2290,11 @@ int cagym_ig_view_gain_headings(void* env, const cagym_ig_heading_params* params
     ENTRY_IG(e, env, "cagym_ig_view_gain_headings");
     if (!params || !best_heading || !best_gain || !valid) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: null argument");
     const cagym_ig_heading_params& p = *params;
+    const char* name = "cagym_ig_view_gain_headings";
     if (p.n_points < 0) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_points must not be negative");
     if (p.n_headings < 1 || p.n_headings > IGH_MAXH) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_headings must be 1..16");
-    if (p.flags) return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: unknown flags");
-    const double pos[3] = {p.radius, p.range, p.fov};
-    for (double v : pos)
-        if (!(v > 0.0) || !std::isfinite(v))  // (the negated comparison refuses NaN)
-            return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: radius, range and fov must be finite and positive");
+    if (int rc = ig_flags_check(e, name, p.flags, 0)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.radius, p.range, p.fov}, "radius, range and fov must be finite and positive")) return rc;
     IgHeadingParams P;
     P.P = points_xy ? p.n_points : IGV_CELLS;  // the map: the kernel generates the cell centres
     P.H = p.n_headings;
@@ -2296,9 +2304,8 @@ int cagym_ig_view_gain_headings(void* env, const cagym_ig_heading_params* params
             return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: the first n_headings headings must be finite");
         P.headings[h] = h < p.n_headings ? p.headings[h] : 0.0;
     }
-    const long long blocks = (long long)e->cfg.n_worlds * (((long long)P.P + IGV_PER_WG - 1) / IGV_PER_WG);  // (no int sum near INT_MAX)
-    if (blocks > 0x7fffffffll)
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_view_gain_headings: n_worlds * n_points is too large for one launch");
+    long long blocks;
+    if (int rc = igv_blocks(e, name, P.P, &blocks)) return rc;
     ON_DEVICE(e);
     if (blocks == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_ig_view_gain_headings, dim3((unsigned)blocks), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
@@ -2326,8 +2333,7 @@ int cagym_ig_goal_face_status(void* env, const cagym_ig_goal_params* params, dou
                               const uint8_t* active, const double* goal_heading, uint8_t* goal_facing, void* stream) {
     ENTRY_IG(e, env, "cagym_ig_goal_face_status");
     if (!goal_xy || !active || !goal_heading || !goal_facing) return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_status: null argument");
-    if (!(face_tol > 0.0) || !std::isfinite(face_tol))  // (the negated comparison refuses NaN)
-        return fail(e, CAGYM_E_INVALID, "cagym_ig_goal_face_status: face_tol must be finite and positive");
+    if (int rc = ig_positive_check(e, "cagym_ig_goal_face_status", {face_tol}, "face_tol must be finite and positive")) return rc;
     IgGoalParams P;
     if (int rc = ig_goal_params_check(e, params, "cagym_ig_goal_face_status", &P)) return rc;
     ON_DEVICE(e);

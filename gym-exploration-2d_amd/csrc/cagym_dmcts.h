@@ -27,7 +27,7 @@
 
 #define DM_MAXH 8      // horizon
 #define DM_MAXCOMM 8   // communicated plans per robot
-#define DM_MAXR 8      // IG robots per world
+#define DM_MAXR IG_MAXR  // IG robots per world
 #define DM_MAXSIMS 32
 #ifndef DM_THREADS
 #define DM_THREADS 128  /* lanes per world (round 4: 256 -> 128, see k_dmcts_plan) */
@@ -237,7 +237,7 @@ __device__ inline void dm_visible_wave(const uint32_t* d2, double px, double py,
             if (q < lim) {
                 i = xs + q / h;
                 j = ys + q % h;
-                double cxp = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cyp = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+                double cxp = ig_cell_centre(i), cyp = ig_cell_centre(j);
                 double r0, r1;
                 mat2vec(c, s, cxp - px, cyp - py, r0, r1);
                 inside = ig_in_cone(r0, r1, cone, r2_in, r2_out, fov, range);
@@ -251,7 +251,7 @@ __device__ inline void dm_visible_wave(const uint32_t* d2, double px, double py,
             const int e = e0 + lane;
             if (e < n) {
                 const int i = list[e] >> 8, j = list[e] & 255;
-                double cxp = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cyp = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+                double cxp = ig_cell_centre(i), cyp = ig_cell_centre(j);
                 if (ig_check_visibility(d2, px, py, cxp, cyp)) atomicOr(&vis[j], 1ull << i);
             }
         }

@@ -16,6 +16,13 @@
 #define IG_HALF 15.0
 #define IG_EDF_CELL 0.1
 #define IG_BEL_CELL 0.5
+#define IG_MAXR 8   // the robots of a world's team: THE limit of every IG entry and of the Dec-MCTS planner (DM_MAXR)
+#define IG_MAXK 31  // the other agents of a robot's world, its OtherAgentsStates rows: M - 1, M <= 32
+
+// the centre of belief cell c along either axis (exact in fp64): THE spelling, of every kernel that names a cell's place
+__device__ __forceinline__ double ig_cell_centre(int c) { return (c)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2; }
+__device__ __forceinline__ float ig_inf_f() { return __int_as_float(0x7f800000); }
+__device__ __forceinline__ double ig_nan_d() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 struct IgDev {
     int N, S;
@@ -181,7 +188,7 @@ __device__ inline void ig_visible_block(const uint32_t* d2, double px, double py
     const double r2_in = range * range * (1.0 - 1e-12), r2_out = range * range * (1.0 + 1e-12);
     for (int q = tid; q < total; q += nthreads) {
         int i = xs + q / h, j = ys + q % h;
-        double cxp = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cyp = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+        double cxp = ig_cell_centre(i), cyp = ig_cell_centre(j);
         double r0, r1;
         mat2vec(c, s, cxp - px, cyp - py, r0, r1);
         if (ig_in_cone(r0, r1, cn, r2_in, r2_out, fov, range)) {
@@ -379,7 +386,7 @@ __global__ void __launch_bounds__(256) k_ig_update(IgDev G, const double* poses,
             if (!((vis[j] >> i) & 1ull)) continue;
             double rs = 0.66;
             if (nd > 0) {
-                double cx = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cy = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+                double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
                 double r0, r1;
                 mat2vec(c, s, cx - px, cy - py, r0, r1);
                 for (int d = 0; d < nd; d++) {
@@ -506,6 +513,62 @@ __device__ __forceinline__ bool ig_robot_slot(const CagymDev& D, int w, int lane
     robots = __ballot(robot);
     return robot;
 }
+// the next robot of the world in slot order: its slot, or -1 when none is left (wave-uniform); the robot leaves `robots`
+__device__ __forceinline__ int ig_next_robot(unsigned long long& robots) {
+    const int slot = robots ? __ffsll((long long)robots) - 1 : -1;
+    robots &= robots - 1ull;
+    return slot;
+}
+// ... and robot number r alone
+__device__ __forceinline__ int ig_nth_robot(unsigned long long robots, int r) {
+    for (int k = 0; k < r; k++) robots &= robots - 1ull;
+    return ig_next_robot(robots);
+}
+// The opening of the one-wave-per-world kernels that give every robot a lane of its own: this lane's rank among the world's robots,
+// or -1 for a lane that holds no robot or one beyond the R the caller asked for - that lane leaves.
+__device__ __forceinline__ int ig_robot_rank(const CagymDev& D, int w, int lane, int R) {
+    unsigned long long robots;
+    if (!ig_robot_slot(D, w, lane, robots)) return -1;
+    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
+    return rank < R ? rank : -1;
+}
+
+// ---- the window frame of a learner's robot: G x G sample points half a metre apart around its pose, out cell (a, b) = a forward, b
+// left.  k_ig_observe's belief window, k_ig_context_window's image and k_ig_geodesic's goal cells agree bit for bit: all go through these.
+// the frame's (sin, cos): of the robot's heading, or (0, 1) for a window that is not heading-aligned
+__device__ __forceinline__ void ig_window_sincos(int rotate, double th, double& sn, double& cs) {
+    sn = 0.0;
+    cs = 1.0;
+    if (rotate) ig_sincos(th, &sn, &cs);
+}
+// the sample point of window cell (a, b); half = (double)(G / 2), which a caller evaluates once
+__device__ __forceinline__ void ig_window_point(double px, double py, double sn, double cs, double half, int a, int b, double& qx, double& qy) {
+    const double ex = ((double)a - half + 0.5) * IG_BEL_CELL, ey = ((double)b - half + 0.5) * IG_BEL_CELL;
+    qx = px + cs * ex - sn * ey;
+    qy = py + sn * ex + cs * ey;
+}
+// The walk over world w's windows window[w] = [R,3,G,G], b fastest: a block's threads stride over the R * G * G out cells, each
+// from the frames wave 0 left in LDS (s_pose[r][0..1] the position, s_sc[r] = (sin, cos)) to the sample point (qx, qy) and its belief
+// cell (i, j); cell(rb, ab, qx, qy, i, j, inside the map, ch) fills the three channels ch[0..2] (zero on entry), stored contiguous in b.
+template <int POSE, typename F>
+__device__ __forceinline__ void ig_window_walk(const double (*s_pose)[POSE], const double (*s_sc)[2], int R, int Gw, float* window, int w,
+                                               int tid, F cell) {
+    const int GG = Gw * Gw, cells = R * GG;
+    const double half = (double)(Gw / 2);
+    float* out = window + (size_t)w * 3 * cells;
+    for (int o = tid; o < cells; o += blockDim.x) {
+        const int rb = o / GG, ab = o - rb * GG, a = ab / Gw, b = ab - a * Gw;
+        double qx, qy;
+        ig_window_point(s_pose[rb][0], s_pose[rb][1], s_sc[rb][0], s_sc[rb][1], half, a, b, qx, qy);
+        const int i = ig_bel_cell(qx), j = ig_bel_cell(qy);
+        float ch[3] = {0.f, 0.f, 0.f};
+        cell(rb, ab, qx, qy, i, j, i >= 0 && i < IG_BEL && j >= 0 && j < IG_BEL, ch);
+        float* dst = out + (size_t)rb * 3 * GG + ab;
+        dst[0] = ch[0];
+        dst[GG] = ch[1];
+        dst[2 * GG] = ch[2];
+    }
+}
 
 // ig_mcts.update_belief's inputs (ig_mcts.py:117-152) for the R robots of every world: poses [N,R,3] = (x, y, heading) of the state,
 // and the detector emulation (find_targets_in_obs) on each robot's OtherAgentsStates rows oas [N,M,M-1,10]: a row is a target when
@@ -518,8 +581,7 @@ __global__ void __launch_bounds__(64) k_ig_robot_inputs(CagymDev D, int R, float
     ig_robot_slot(D, w, lane, robots);
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int r = 0; r < R; r++) {
-        const int slot = robots ? __ffsll((long long)robots) - 1 : -1;  // wave-uniform
-        robots &= robots - 1ull;
+        const int slot = ig_next_robot(robots);
         double px = 0.0, py = 0.0, th = 0.0;
         int cnt = 0;
         if (slot >= 0) {
@@ -550,10 +612,8 @@ __global__ void __launch_bounds__(64) k_ig_robot_inputs(CagymDev D, int R, float
 // the planner's (v, omega) [N,R,2] into the robots' rows of the action table [N*M,2] (fp64 -> fp32 round to nearest)
 __global__ void __launch_bounds__(64) k_ig_robot_actions(CagymDev D, int R, const double* __restrict__ planned, float* actions) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned long long robots;
-    if (!ig_robot_slot(D, w, lane, robots)) return;
-    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
-    if (rank >= R) return;
+    const int rank = ig_robot_rank(D, w, lane, R);
+    if (rank < 0) return;
     const double* p = planned + ((size_t)w * R + rank) * 2;
     reinterpret_cast<float2*>(actions)[(size_t)w * D.M + lane] = make_float2((float)p[0], (float)p[1]);
 }

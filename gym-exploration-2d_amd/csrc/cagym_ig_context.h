@@ -6,16 +6,13 @@
 //   2  seen now:  1 where the sample's belief cell is in `observed`, the union k_ig_observe just wrote
 //
 // One workgroup of 256 threads per world.  Wave 0 (lane j = slot j, M <= 32) finds the robots with ig_robot_slot and leaves poses and
-// (sin, cos) in LDS - the expressions of k_ig_observe on the same operands, so both windows agree on every sample point - and compacts,
+// (sin, cos) in LDS - ig_window_sincos, and ig_window_walk over them, as k_ig_observe: both windows agree on every sample point - and compacts,
 // per robot, the agents whose window cell lies inside its window into a short LDS list (ballot + popcount, at most M - 1 entries of
 // cell index | teammate bit).  Then lanes stride over the R * G * G out cells, b fastest: one gather from the distance field, one LDS
 // word of the observed set, a walk over the robot's list (a handful of entries, not M slots), three stores contiguous in b.
 // No atomics, no waits: one barrier, one early exit per workgroup in front of it.
 #pragma once
 #include "cagym_ig.h"
-
-#define IGC_MAXR 8
-#define IGC_MAXK 31  // the other agents of a robot's world: M - 1, M <= 32
 
 struct IgContextParams {
     int R, G, rotate;
@@ -26,10 +23,10 @@ struct IgContextParams {
 __global__ void __launch_bounds__(256) k_ig_context_window(CagymDev D, IgDev G, IgContextParams P, const unsigned long long* __restrict__ observed,
                                                            const uint8_t* __restrict__ world_mask, float* window) {
     __shared__ unsigned long long s_obs[IG_BEL];
-    __shared__ double s_pose[IGC_MAXR][2];
-    __shared__ double s_sc[IGC_MAXR][2];
-    __shared__ int s_agent[IGC_MAXR][IGC_MAXK + 1];  // a_s * G + b_s, bit 16: a teammate
-    __shared__ int s_na[IGC_MAXR];
+    __shared__ double s_pose[IG_MAXR][2];
+    __shared__ double s_sc[IG_MAXR][2];
+    __shared__ int s_agent[IG_MAXR][IG_MAXK + 1];  // a_s * G + b_s, bit 16: a teammate
+    __shared__ int s_na[IG_MAXR];
     const int w = blockIdx.x, tid = threadIdx.x, M = D.M, R = P.R, Gw = P.G;
     if ((P.flags & 1u) && !(world_mask && world_mask[w])) return;  // CAGYM_IG_CONTEXT_ONLY_MASKED: nothing of this world is read or written
 
@@ -49,15 +46,14 @@ __global__ void __launch_bounds__(256) k_ig_context_window(CagymDev D, IgDev G, 
         const unsigned long long below = (1ull << lane) - 1ull;
         const double half = (double)(Gw / 2);
         for (int r = 0; r < R; r++) {
-            const int slot = robots ? __ffsll((long long)robots) - 1 : -1;  // wave-uniform
-            robots &= robots - 1ull;
+            const int slot = ig_next_robot(robots);
             double px = 0.0, py = 0.0, th = 0.0;
             if (slot >= 0) {
                 const size_t a = (size_t)w * M + slot;
                 px = D.px[a]; py = D.py[a]; th = D.heading[a];
             }
-            double sn = 0.0, cs = 1.0;
-            if (P.rotate) ig_sincos(th, &sn, &cs);
+            double sn, cs;
+            ig_window_sincos(P.rotate, th, sn, cs);
             // this lane's agent in robot r's frame: window cell (a_s, b_s) = floor(f / 0.5) + G / 2
             const double dx = ax - px, dy = ay - py;
             const double fx = cs * dx + sn * dy, fy = cs * dy - sn * dx;
@@ -77,30 +73,18 @@ __global__ void __launch_bounds__(256) k_ig_context_window(CagymDev D, IgDev G, 
     for (int j = tid; j < IG_BEL; j += blockDim.x) s_obs[j] = observed ? observed[(size_t)w * IG_BEL + j] : 0ull;
     __syncthreads();
 
-    // 2. the cells: out cell (a, b) = a forward, b left, b fastest - k_ig_observe's sample point and source cell
+    // 2. the cells (ig_window_walk: k_ig_observe's sample points and source cells)
     const uint32_t* d2 = G.d2 + (size_t)ig_scenario(G, w) * CAGYM_MAPD * CAGYM_MAPD;
-    const int GG = Gw * Gw, cells = R * GG;
-    const double half = (double)(Gw / 2);
-    float* out = window + (size_t)w * 3 * cells;
-    for (int o = tid; o < cells; o += blockDim.x) {
-        const int rb = o / GG, ab = o - rb * GG, a = ab / Gw, b = ab - a * Gw;
-        const double ex = ((double)a - half + 0.5) * IG_BEL_CELL, ey = ((double)b - half + 0.5) * IG_BEL_CELL;
-        const double sn = s_sc[rb][0], cs = s_sc[rb][1];
-        const double qx = s_pose[rb][0] + cs * ex - sn * ey, qy = s_pose[rb][1] + sn * ex + cs * ey;
-        const int i = ig_bel_cell(qx), j = ig_bel_cell(qy);
-        float clear = 0.f, seen = 0.f, agents = 0.f;
-        if (i >= 0 && i < IG_BEL && j >= 0 && j < IG_BEL) {
-            clear = (float)(fmin(edf_at(d2, qx, qy), P.clear_max) / P.clear_max);
-            seen = ((s_obs[j] >> i) & 1ull) ? 1.f : 0.f;
-        }
-        const int na = s_na[rb];
-        for (int n = 0; n < na; n++) {
-            const int e = s_agent[rb][n];
-            if ((e & 0xffff) == ab) agents = fmaxf(agents, (e & 0x10000) ? 1.0f : 0.5f);
-        }
-        float* cell = out + (size_t)rb * 3 * GG + ab;
-        cell[0] = clear;
-        cell[GG] = agents;
-        cell[2 * GG] = seen;
-    }
+    ig_window_walk(s_pose, s_sc, R, Gw, window, w, tid,
+                   [&](int rb, int ab, double qx, double qy, int i, int j, bool inside, float* ch) {
+                       if (inside) {
+                           ch[0] = (float)(fmin(edf_at(d2, qx, qy), P.clear_max) / P.clear_max);  // clearance
+                           ch[2] = ((s_obs[j] >> i) & 1ull) ? 1.f : 0.f;                          // seen now
+                       }
+                       const int na = s_na[rb];
+                       for (int n = 0; n < na; n++) {  // agents
+                           const int e = s_agent[rb][n];
+                           if ((e & 0xffff) == ab) ch[1] = fmaxf(ch[1], (e & 0x10000) ? 1.0f : 0.5f);
+                       }
+                   });
 }

@@ -20,11 +20,10 @@
 // workgroup-wide OR (__syncthreads_or, which is also the barrier between two sweeps).  The loop is capped at 3600 trips (no chain is
 // longer than the number of cells).  No global atomics, no waits: barriers only.
 //
-// k_ig_goal_actions / k_ig_goal_status: one wave per world, lane = agent slot, one lane per robot (ig_robot_slot gives its rank).
+// k_ig_goal_actions / k_ig_goal_status: one wave per world, lane = agent slot, one lane per robot (ig_robot_rank gives its rank).
 #pragma once
 #include "cagym_ig.h"
 
-#define IGG_MAXR 8
 #define IGG_TW 62                 // tile width: 60 cells and a halo of one on either side
 #define IGG_SWEEP_CAP 3600
 #define IGG_ORTHO 0.5f
@@ -50,22 +49,16 @@ __global__ void __launch_bounds__(256) k_ig_geodesic(CagymDev D, IgDev G, IgGoal
         if (goals_xy) {
             x = goals_xy[2 * (size_t)wr];
             y = goals_xy[2 * (size_t)wr + 1];
-        } else {  // a cell (a, b) of the robot's belief window: k_ig_observe's sample point on the pose as it is now
+        } else {  // a cell (a, b) of the robot's belief window: ig_window_point on the pose as it is now
             unsigned long long robots;
             ig_robot_slot(D, w, tid, robots);
-            for (int k = 0; k < r; k++) robots &= robots - 1ull;
-            const int slot = robots ? __ffsll((long long)robots) - 1 : -1;  // wave-uniform
-            x = y = __longlong_as_double(0x7ff8000000000000ll);              // (a world without that robot: no source)
+            const int slot = ig_nth_robot(robots, r);  // wave-uniform
+            x = y = ig_nan_d();                        // (a world without that robot: no source)
             if (slot >= 0) {
                 const size_t a = (size_t)w * D.M + slot;
-                const double px = D.px[a], py = D.py[a], th = D.heading[a];
-                double sn = 0.0, cs = 1.0;
-                if (P.rotate) ig_sincos(th, &sn, &cs);
-                const double half = (double)(P.G / 2);
-                const double ex = ((double)goals_ab[2 * (size_t)wr] - half + 0.5) * IG_BEL_CELL;
-                const double ey = ((double)goals_ab[2 * (size_t)wr + 1] - half + 0.5) * IG_BEL_CELL;
-                x = px + cs * ex - sn * ey;
-                y = py + sn * ex + cs * ey;
+                double sn, cs;
+                ig_window_sincos(P.rotate, D.heading[a], sn, cs);
+                ig_window_point(D.px[a], D.py[a], sn, cs, (double)(P.G / 2), goals_ab[2 * (size_t)wr], goals_ab[2 * (size_t)wr + 1], x, y);
             }
         }
         if (tid == 0) {
@@ -79,7 +72,7 @@ __global__ void __launch_bounds__(256) k_ig_geodesic(CagymDev D, IgDev G, IgGoal
             active[wr] = ok ? 1 : 0;
         }
     }
-    const float inf = __int_as_float(0x7f800000);
+    const float inf = ig_inf_f();
     for (int q = tid; q < IGG_TW * IGG_TW; q += blockDim.x) tile[q] = inf;
     for (int q = tid; q < IGG_TW; q += blockDim.x) fm[q] = 0ull;
     __syncthreads();
@@ -207,7 +200,7 @@ __device__ __forceinline__ double igg_wrap(double a) {
 }
 
 __device__ __forceinline__ float igg_at(const float* f, int i, int j) {
-    return (i >= 0 && i < IG_BEL && j >= 0 && j < IG_BEL) ? f[j * IG_BEL + i] : __int_as_float(0x7f800000);
+    return (i >= 0 && i < IG_BEL && j >= 0 && j < IG_BEL) ? f[j * IG_BEL + i] : ig_inf_f();
 }
 
 // The controller (ig.goal_action_spec): for every robot with an active goal its row of the action table [N*M, 2] f32; every other
@@ -216,10 +209,8 @@ __global__ void __launch_bounds__(64) k_ig_goal_actions(CagymDev D, IgGoalParams
                                                         const double* __restrict__ goal_xy, const uint8_t* __restrict__ active,
                                                         float* actions, uint8_t* choice) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned long long robots;
-    if (!ig_robot_slot(D, w, lane, robots)) return;
-    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
-    if (rank >= P.R) return;
+    const int rank = ig_robot_rank(D, w, lane, P.R);
+    if (rank < 0) return;
     const size_t wr = (size_t)w * P.R + rank, a = (size_t)w * D.M + lane;
     if (!active[wr]) {
         if (choice) choice[wr] = 255;
@@ -237,7 +228,7 @@ __global__ void __launch_bounds__(64) k_ig_goal_actions(CagymDev D, IgGoalParams
     int pick = go ? 8 : 255;  // what the robot aims at: 0..7 the neighbour in candidate order, 8 the goal point, 255 nothing
     const bool to_goal = ci == ig_bel_cell(gx) && cj == ig_bel_cell(gy);
     if (go && !to_goal) {
-        const float inf = __int_as_float(0x7f800000);
+        const float inf = ig_inf_f();
         const bool own = f[cj * IG_BEL + ci] < inf;
         const float e = igg_at(f, ci + 1, cj), n = igg_at(f, ci, cj + 1), wv = igg_at(f, ci - 1, cj), s = igg_at(f, ci, cj - 1);
         // E, N, W, S, NE, NW, SW, SE: the first of the smallest keys wins (the loop unrolls: every index below is a constant)
@@ -261,8 +252,8 @@ __global__ void __launch_bounds__(64) k_ig_goal_actions(CagymDev D, IgGoalParams
                 pick = k;
             }
         }
-        ax = (double)ni * IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
-        ay = (double)nj * IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+        ax = ig_cell_centre(ni);
+        ay = ig_cell_centre(nj);
     }
     if (go) {
         const double err = igg_wrap(igg_atan2(ay - y, ax - x) - th);
@@ -280,17 +271,15 @@ __global__ void __launch_bounds__(64) k_ig_goal_status(CagymDev D, IgGoalParams 
                                                        const float* __restrict__ field, const double* __restrict__ goal_xy,
                                                        uint8_t* active, float* goal_distance, uint8_t* goal_reached) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned long long robots;
-    if (!ig_robot_slot(D, w, lane, robots)) return;
-    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
-    if (rank >= P.R) return;
+    const int rank = ig_robot_rank(D, w, lane, P.R);
+    if (rank < 0) return;
     const size_t wr = (size_t)w * P.R + rank, a = (size_t)w * D.M + lane;
     bool act = active[wr] != 0;
     if (restart_mask && restart_mask[w]) {
         act = false;
         active[wr] = 0;
     }
-    float dist = __int_as_float(0x7f800000);
+    float dist = ig_inf_f();
     bool reached = false;
     if (act) {
         const double x = D.px[a], y = D.py[a];

@@ -3,8 +3,8 @@
 // the spot; the sensor is a cone, the planners and the reward score a pose (x, y, theta).  Here every viewpoint is scored at H
 // caller-chosen headings: for heading h exactly the cells cagym_ig_visible_cells returns for the pose (x, y, headings[h]).
 //
-// k_ig_view_gain_headings keeps k_ig_view_gain's layout: 256 threads, IGV_PER_WG = 60 consecutive viewpoints per workgroup (in map
-// mode the 60 cell centres of one belief row, generated here and run through the points mode's statements: the same bits), the
+// k_ig_view_gain_headings keeps k_ig_view_gain's layout and shares its opening (igv_span, igv_stage_mi, igv_point, igv_rect): 256 threads,
+// IGV_PER_WG = 60 consecutive viewpoints per workgroup (in map mode the 60 cell centres of one belief row: the same bits), the
 // world's MI cache staged in LDS once, one wave per viewpoint round robin, the candidate cells - the rectangle cell(p - range) ..
 // cell(p + range) - dealt to the 64 lanes round robin in row-major order.  The sphere trace does not depend on the heading, so a
 // candidate is traced ONCE and the answer kept as bit t of a per-lane register (candidate lane + 64 t: at most 7 at range 5, at
@@ -37,13 +37,11 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain_headings(IgDev G, 
                                                                        int32_t* n_visible_h, int32_t* best_heading, double* best_gain,
                                                                        uint8_t* valid) {
     __shared__ double s_mi[IGV_CELLS];
-    const int chunks = (P.P - 1) / IGV_PER_WG + 1;  // (P.P >= 1: the entry launches nothing for 0; no sum that could pass INT_MAX)
-    const int w = blockIdx.x / chunks, chunk = blockIdx.x - w * chunks;
+    int w, p0, p1;
+    igv_span(P.P, w, p0, p1);
     if (world_mask && !world_mask[w]) return;  // not flagged: nothing of this world is read or written
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double* mi = G.mi + (size_t)w * IGV_CELLS;
-    for (int q = tid; q < IGV_CELLS; q += IGV_THREADS) s_mi[q] = mi[q];
-    __syncthreads();
+    igv_stage_mi(G, w, tid, s_mi);
     const uint32_t* d2 = G.d2 + (size_t)ig_scenario(G, w) * CAGYM_MAPD * CAGYM_MAPD;
     const double need = P.radius + 0.1, r2_pre = P.range * P.range * (1.0 + 1e-9);
     const IgCone cn = ig_cone(P.fov);  // one per launch, as k_ig_visible's ig_visible_block evaluates it
@@ -56,21 +54,10 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain_headings(IgDev G, 
         const int k = lane - 3 * h;
         if (k >= 0 && k < 3) ig_sincos(k == 0 ? phi : (k == 1 ? phi + P.fov : phi - P.fov), &my_s, &my_c);
     }
-    const int p0 = chunk * IGV_PER_WG, p1 = P.P - p0 < IGV_PER_WG ? P.P : p0 + IGV_PER_WG;
     for (int p = p0 + wave; p < p1; p += IGV_THREADS / 64) {  // (every value below but the lane's own cells is wave-uniform)
         const size_t o = (size_t)w * P.P + p;
         double px, py;
-        if (points_xy) {
-            px = points_xy[2 * o];
-            py = points_xy[2 * o + 1];
-        } else {
-            px = igv_centre(p % IG_BEL);
-            py = igv_centre(p / IG_BEL);
-        }
-        const int ci = ig_bel_cell(px), cj = ig_bel_cell(py);
-        bool ok = isfinite(px) && isfinite(py) && ci >= 0 && ci < IG_BEL && cj >= 0 && cj < IG_BEL;
-        if (ok) ok = edf_at(d2, px, py) > need;  // cagym_ig_view_gain's rule
-        if (!ok) {
+        if (!igv_point(d2, points_xy, o, p, need, px, py)) {
             if (lane < P.H) {
                 if (gain_h) gain_h[o * P.H + lane] = 0.0;
                 if (n_visible_h) n_visible_h[o * P.H + lane] = 0;
@@ -83,11 +70,9 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain_headings(IgDev G, 
             continue;
         }
         // 1. the traces, once per candidate: bit t of `seen` <=> candidate lane + 64 t is near enough and visible
-        const int xs = max(0, ig_bel_cell(px - P.range)), xe = min(IG_BEL - 1, ig_bel_cell(px + P.range));
-        const int ys = max(0, ig_bel_cell(py - P.range)), ye = min(IG_BEL - 1, ig_bel_cell(py + P.range));
-        const int wd = xe - xs + 1, ht = ye - ys + 1;
-        const int total = (wd > 0 && ht > 0) ? wd * ht : 0;  // <= 3600
-        const int trips = (total + 63) >> 6;                 // <= 57: a bit each
+        int xs, ys, wd;
+        const int total = igv_rect(px, py, P.range, xs, ys, wd);  // <= 3600
+        const int trips = (total + 63) >> 6;                      // <= 57: a bit each
         // q / wd without the integer division: (q + 0.5) / wd lies at least 0.5 / wd from an integer and the fp32 product is off
         // by at most (3600 / wd) 2^-23, so the truncation is the quotient for every q < 3600, wd <= 60
         const float rwd = 1.0f / (float)max(wd, 1);
@@ -97,7 +82,7 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain_headings(IgDev G, 
             if (q < total) {
                 const int jj = (int)(((float)q + 0.5f) * rwd);
                 const int i = xs + (q - jj * wd), j = ys + jj;  // both within 0..59
-                const double cx = igv_centre(i), cy = igv_centre(j);
+                const double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
                 const double dx = cx - px, dy = cy - py;
                 if (dx * dx + dy * dy <= r2_pre && ig_check_visibility(d2, px, py, cx, cy)) seen |= 1ull << t;
             }
@@ -118,7 +103,7 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain_headings(IgDev G, 
                     const int jj = (int)(((float)q + 0.5f) * rwd);
                     const int i = xs + (q - jj * wd), j = ys + jj;
                     if (i >= bxs && i < bxe && j >= bys && j < bye) {
-                        const double cxp = igv_centre(i), cyp = igv_centre(j);
+                        const double cxp = ig_cell_centre(i), cyp = ig_cell_centre(j);
                         double r0, r1;
                         mat2vec(c, s, cxp - px, cyp - py, r0, r1);
                         if (ig_in_cone(r0, r1, cn, r2_in, r2_out, P.fov, P.range)) {
@@ -157,10 +142,8 @@ __global__ void __launch_bounds__(64) k_ig_goal_face_actions(CagymDev D, IgGoalP
                                                              const uint8_t* __restrict__ active,
                                                              const double* __restrict__ goal_heading, float* actions) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned long long robots;
-    if (!ig_robot_slot(D, w, lane, robots)) return;
-    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
-    if (rank >= P.R) return;
+    const int rank = ig_robot_rank(D, w, lane, P.R);
+    if (rank < 0) return;
     const size_t wr = (size_t)w * P.R + rank, a = (size_t)w * D.M + lane;
     if (!active[wr]) return;
     const double gh = goal_heading[wr];
@@ -180,10 +163,8 @@ __global__ void __launch_bounds__(64) k_ig_goal_face_status(CagymDev D, IgGoalPa
                                                             const double* __restrict__ goal_xy, const uint8_t* __restrict__ active,
                                                             const double* __restrict__ goal_heading, uint8_t* goal_facing) {
     const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned long long robots;
-    if (!ig_robot_slot(D, w, lane, robots)) return;
-    const int rank = __popcll(robots & ((1ull << lane) - 1ull));
-    if (rank >= P.R) return;
+    const int rank = ig_robot_rank(D, w, lane, P.R);
+    if (rank < 0) return;
     const size_t wr = (size_t)w * P.R + rank, a = (size_t)w * D.M + lane;
     bool facing = false;
     if (active[wr]) {

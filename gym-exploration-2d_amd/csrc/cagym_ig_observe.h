@@ -17,9 +17,6 @@
 #include "cagym_ig.h"
 #include "cagym_ig_episode.h"
 
-#define IGO_MAXR 8
-#define IGO_MAXK 31  // OtherAgentsStates rows of a robot: M - 1, M <= 32
-
 struct IgObserveParams {
     int R, G, rotate;
     unsigned int flags;  // CAGYM_IG_EPISODE_FOLD | CAGYM_IG_OBSERVE_ONLY_RESTARTED
@@ -33,10 +30,10 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
     __shared__ unsigned long long vis[IG_BEL];
     __shared__ unsigned long long uni[IG_BEL];
     __shared__ double red[256];
-    __shared__ double s_pose[IGO_MAXR][3];
-    __shared__ double s_sc[IGO_MAXR][2];  // the window's (sin, cos) of each robot
-    __shared__ double s_det[IGO_MAXR][IGO_MAXK][2];
-    __shared__ int s_nd[IGO_MAXR];
+    __shared__ double s_pose[IG_MAXR][3];
+    __shared__ double s_sc[IG_MAXR][2];  // the window's (sin, cos) of each robot
+    __shared__ double s_det[IG_MAXR][IG_MAXK][2];
+    __shared__ int s_nd[IG_MAXR];
     const int w = blockIdx.x, tid = threadIdx.x, M = D.M, K = M - 1, R = P.R;
     const bool restarted = restart_mask && restart_mask[w];  // uniform
     if ((P.flags & 4u) && !restarted) return;                // CAGYM_IG_OBSERVE_ONLY_RESTARTED: nothing of this world is read or written
@@ -63,8 +60,7 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
         ig_robot_slot(D, w, lane, robots);
         const unsigned long long below = (1ull << lane) - 1ull;
         for (int r = 0; r < R; r++) {
-            const int slot = robots ? __ffsll((long long)robots) - 1 : -1;  // wave-uniform
-            robots &= robots - 1ull;
+            const int slot = ig_next_robot(robots);
             double px = 0.0, py = 0.0, th = 0.0;
             int cnt = 0;
             if (slot >= 0) {
@@ -89,8 +85,8 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
             if (lane < 3) s_pose[r][lane] = lane == 0 ? px : lane == 1 ? py : th;
             if (lane == 0) {
                 s_nd[r] = cnt;
-                double s = 0.0, c = 1.0;
-                if (P.rotate) ig_sincos(th, &s, &c);
+                double s, c;
+                ig_window_sincos(P.rotate, th, s, c);
                 s_sc[r][0] = s;
                 s_sc[r][1] = c;
             }
@@ -115,7 +111,7 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
             if (!((vis[j] >> i) & 1ull)) continue;
             double rs = 0.66;
             if (nd > 0) {
-                double cx = (i)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2, cy = (j)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2;
+                double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
                 double r0, r1;
                 mat2vec(c, s, cx - px, cy - py, r0, r1);
                 for (int d = 0; d < nd; d++) {
@@ -146,29 +142,15 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
         if (team_reward) team_reward[w] = restarted ? 0.0 : r;  // ... and is no reward for the action that ended the old one
     }
 
-    // 5. each robot's window: out cell (a, b) = a forward, b left, b fastest.  Lanes stride over the R * G * G cells and store the
-    //    three channels of theirs (the sample point and the source cell are the same for all three): each store is contiguous in b
+    // 5. each robot's window (ig_window_walk: the sample point and the source cell are the same for all three channels)
     if (!window) return;
-    const int GG = P.G * P.G, cells = R * GG;
-    const double half = (double)(P.G / 2);
-    float* out = window + (size_t)w * 3 * cells;
-    for (int o = tid; o < cells; o += blockDim.x) {
-        const int rb = o / GG, ab = o - rb * GG, a = ab / P.G, b = ab - a * P.G;
-        const double ex = ((double)a - half + 0.5) * IG_BEL_CELL, ey = ((double)b - half + 0.5) * IG_BEL_CELL;
-        const double sn = s_sc[rb][0], cs = s_sc[rb][1];
-        const double qx = s_pose[rb][0] + cs * ex - sn * ey, qy = s_pose[rb][1] + sn * ex + cs * ey;
-        const int i = ig_bel_cell(qx), j = ig_bel_cell(qy);
-        float p_occ = 0.f, cell_mi = 0.f, inside = 0.f;
-        if (i >= 0 && i < IG_BEL && j >= 0 && j < IG_BEL) {
-            const int q = j * IG_BEL + i;
-            const double odds = bel[q];
-            p_occ = (float)(odds / (odds + 1));
-            cell_mi = (float)mi[q];
-            inside = 1.f;
-        }
-        float* cell = out + (size_t)rb * 3 * GG + ab;
-        cell[0] = p_occ;
-        cell[GG] = cell_mi;
-        cell[2 * GG] = inside;
-    }
+    ig_window_walk(s_pose, s_sc, R, P.G, window, w, tid,
+                   [&](int, int, double, double, int i, int j, bool inside, float* ch) {
+                       if (!inside) return;
+                       const int q = j * IG_BEL + i;
+                       const double odds = bel[q];
+                       ch[0] = (float)(odds / (odds + 1));  // P(occupied)
+                       ch[1] = (float)mi[q];                // cached cell MI
+                       ch[2] = 1.f;                         // inside the map
+                   });
 }

@@ -22,7 +22,6 @@
 #pragma once
 #include "cagym_ig.h"
 
-#define IGV_MAXR 8
 #define IGV_MAXK 16
 #define IGV_PER_WG 60
 #define IGV_THREADS 256
@@ -33,46 +32,69 @@ struct IgViewParams {
     double radius, range, min_sep, d0;
 };
 
-__device__ __forceinline__ double igv_centre(int c) { return (c)*IG_BEL_CELL - IG_HALF + IG_BEL_CELL / 2; }  // ig_visible_block's expression
+// ---- what k_ig_view_gain and k_ig_view_gain_headings (cagym_ig_headings.h) do alike.  The workgroup's world w and its viewpoints
+// p0 <= p < p1 of the n_points per world (n_points >= 1: the entries launch nothing for 0; no sum that could pass INT_MAX) ...
+__device__ __forceinline__ void igv_span(int n_points, int& w, int& p0, int& p1) {
+    const int chunks = (n_points - 1) / IGV_PER_WG + 1;
+    w = blockIdx.x / chunks;
+    p0 = (blockIdx.x - w * chunks) * IGV_PER_WG;
+    p1 = n_points - p0 < IGV_PER_WG ? n_points : p0 + IGV_PER_WG;
+}
+// ... the world's MI cache into s_mi[IGV_CELLS] by every thread of the workgroup, ending with the kernel's one barrier ...
+__device__ __forceinline__ void igv_stage_mi(const IgDev& G, int w, int tid, double* s_mi) {
+    const double* mi = G.mi + (size_t)w * IGV_CELLS;
+    for (int q = tid; q < IGV_CELLS; q += IGV_THREADS) s_mi[q] = mi[q];
+    __syncthreads();
+}
+// ... viewpoint o = w * n_points + p: the caller's point, or in map mode (points_xy NULL) the centre of belief cell p, and whether a robot
+// can stand there - finite, inside the map and clear by the planners' feasibility test EDF > need = radius + 0.1.
+__device__ __forceinline__ bool igv_point(const uint32_t* d2, const double* __restrict__ points_xy, size_t o, int p, double need, double& px, double& py) {
+    if (points_xy) {
+        px = points_xy[2 * o];
+        py = points_xy[2 * o + 1];
+    } else {
+        px = ig_cell_centre(p % IG_BEL);
+        py = ig_cell_centre(p / IG_BEL);
+    }
+    const int ci = ig_bel_cell(px), cj = ig_bel_cell(py);
+    bool ok = isfinite(px) && isfinite(py) && ci >= 0 && ci < IG_BEL && cj >= 0 && cj < IG_BEL;
+    if (ok) ok = edf_at(d2, px, py) > need;
+    return ok;
+}
+// ... and its candidate cells: the rectangle cell(p - range) .. cell(p + range) inside the map, wd wide from (xs, ys); returns their number
+__device__ __forceinline__ int igv_rect(double px, double py, double range, int& xs, int& ys, int& wd) {
+    xs = max(0, ig_bel_cell(px - range));
+    ys = max(0, ig_bel_cell(py - range));
+    const int xe = min(IG_BEL - 1, ig_bel_cell(px + range)), ye = min(IG_BEL - 1, ig_bel_cell(py + range));
+    wd = xe - xs + 1;
+    const int ht = ye - ys + 1;
+    return (wd > 0 && ht > 0) ? wd * ht : 0;
+}
 
 __global__ void __launch_bounds__(IGV_THREADS) k_ig_view_gain(IgDev G, IgViewParams P, const uint8_t* __restrict__ world_mask,
                                                               const double* __restrict__ points_xy, double* gain, int32_t* n_visible,
                                                               uint8_t* valid) {
     __shared__ double s_mi[IGV_CELLS];
-    const int chunks = (P.P + IGV_PER_WG - 1) / IGV_PER_WG;
-    const int w = blockIdx.x / chunks, chunk = blockIdx.x - w * chunks;
+    int w, p0, p1;
+    igv_span(P.P, w, p0, p1);
     if (world_mask && !world_mask[w]) return;  // not flagged: nothing of this world is read or written
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double* mi = G.mi + (size_t)w * IGV_CELLS;
-    for (int q = tid; q < IGV_CELLS; q += IGV_THREADS) s_mi[q] = mi[q];
-    __syncthreads();
+    igv_stage_mi(G, w, tid, s_mi);
     const uint32_t* d2 = G.d2 + (size_t)ig_scenario(G, w) * CAGYM_MAPD * CAGYM_MAPD;
     const double need = P.radius + 0.1, r2 = P.range * P.range;
-    const int p0 = chunk * IGV_PER_WG, p1 = min(P.P, p0 + IGV_PER_WG);
     for (int p = p0 + wave; p < p1; p += IGV_THREADS / 64) {  // (every value below but the lane's own cells is wave-uniform)
         const size_t o = (size_t)w * P.P + p;
         double px, py;
-        if (points_xy) {
-            px = points_xy[2 * o];
-            py = points_xy[2 * o + 1];
-        } else {
-            px = igv_centre(p % IG_BEL);
-            py = igv_centre(p / IG_BEL);
-        }
-        const int ci = ig_bel_cell(px), cj = ig_bel_cell(py);
-        bool ok = isfinite(px) && isfinite(py) && ci >= 0 && ci < IG_BEL && cj >= 0 && cj < IG_BEL;
-        if (ok) ok = edf_at(d2, px, py) > need;  // the planners' feasibility test at the point itself
+        const bool ok = igv_point(d2, points_xy, o, p, need, px, py);
         double acc = 0.0;
         int cnt = 0;
         if (ok) {
-            const int xs = max(0, ig_bel_cell(px - P.range)), xe = min(IG_BEL - 1, ig_bel_cell(px + P.range));
-            const int ys = max(0, ig_bel_cell(py - P.range)), ye = min(IG_BEL - 1, ig_bel_cell(py + P.range));
-            const int wd = xe - xs + 1, ht = ye - ys + 1;
-            const int total = (wd > 0 && ht > 0) ? wd * ht : 0;
+            int xs, ys, wd;
+            const int total = igv_rect(px, py, P.range, xs, ys, wd);
             for (int q = lane; q < total; q += 64) {
                 const int jj = q / wd;
                 const int i = xs + (q - jj * wd), j = ys + jj;  // both within 0..59
-                const double cx = igv_centre(i), cy = igv_centre(j);
+                const double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
                 const double dx = cx - px, dy = cy - py;
                 if (dx * dx + dy * dy < r2 && ig_check_visibility(d2, px, py, cx, cy)) {
                     acc += s_mi[j * IG_BEL + i];
@@ -114,7 +136,7 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_propose_goals(IgViewParams P
     const double* g = gain_map + (size_t)w * IGV_CELLS;
     const uint8_t* v = valid_map + (size_t)w * IGV_CELLS;
     const float* f = field + (size_t)wr * IGV_CELLS;
-    const float inf = __int_as_float(0x7f800000);
+    const float inf = ig_inf_f();
     for (int q = tid; q < IGV_CELLS; q += IGV_THREADS) {
         const double gv = g[q];
         const float fv = f[q];
@@ -156,8 +178,8 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_propose_goals(IgViewParams P
             const size_t o = row + found;
             cells[2 * o] = ci;
             cells[2 * o + 1] = cj;
-            xy[2 * o] = igv_centre(ci);
-            xy[2 * o + 1] = igv_centre(cj);
+            xy[2 * o] = ig_cell_centre(ci);
+            xy[2 * o + 1] = ig_cell_centre(cj);
             utility[o] = bu;
             gain[o] = g[bi];
             distance[o] = f[bi];
@@ -172,7 +194,7 @@ __global__ void __launch_bounds__(IGV_THREADS) k_ig_propose_goals(IgViewParams P
     if (tid >= found && tid < P.k) {  // rows past n_found
         const size_t o = row + tid;
         cells[2 * o] = cells[2 * o + 1] = -1;
-        xy[2 * o] = xy[2 * o + 1] = __longlong_as_double(0x7ff8000000000000ll);
+        xy[2 * o] = xy[2 * o + 1] = ig_nan_d();
         utility[o] = 0.0;
         gain[o] = 0.0;
         distance[o] = inf;

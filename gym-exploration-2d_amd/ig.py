@@ -42,6 +42,26 @@ class InfoGain(object):
             t = t.reshape(shape)
         return t.contiguous()
 
+    def _dev(self, x, dtype, shape=None):
+        """x itself (the same memory: callers rely on in-place writes) when it is a contiguous device tensor of that dtype, else _t's copy."""
+        as_it_is = torch.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
+        return x if as_it_is else self._t(x, dtype, shape)
+
+    def _out(self, out, spec):
+        """`out` when the caller gave one, else new device tensors of spec = {name: (shape, dtype)}."""
+        return out if out is not None else {k: torch.empty(s, dtype=d, device=self.b.device) for k, (s, d) in spec.items()}
+
+    def _viewpoints(self, points, world_mask):
+        """view_gain()'s and view_gain_headings()'s places: (points [N,P,2] f64 or None for the map, world_mask [N] u8 or None, the
+        shape of a per-point output, n_points of the parameter block)."""
+        N = self.b.N
+        if points is not None:
+            points = self._dev(points, torch.float64).reshape(N, -1, 2)
+        shape = (N, 60, 60) if points is None else (N, points.shape[1])
+        if world_mask is not None:
+            world_mask = self._t(world_mask, torch.uint8, (N,))
+        return points, world_mask, shape, 0 if points is None else shape[1]
+
     def robot_inputs(self, n_robots, detect_range, obs_oas, poses, detections, n_det):
         """cagym_ig_robot_inputs: the R robots' poses [N,R,3] and detections [N,R,M-1,2] / n_det [N,R] (the detector emulation of
         find_targets_in_obs on their rows of obs_oas), written into the given device tensors."""
@@ -109,22 +129,13 @@ class InfoGain(object):
         [N,R] i32 the relaxation sweeps run; `out`: such a dict to write into again (default: new tensors)."""
         if (points is None) == (cells is None):
             raise ValueError("geodesic: exactly one of points and cells must be given")
-        N, dev = self.b.N, self.b.device
-        if points is not None:
-            src = points if (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()) \
-                else self._t(points, torch.float64)
-        else:
-            src = cells if (torch.is_tensor(cells) and cells.is_cuda and cells.dtype == torch.int32 and cells.is_contiguous()) \
-                else self._t(cells, torch.int32)
-        src = src.reshape(N, -1, 2)
+        N = self.b.N
+        src = (self._dev(points, torch.float64) if points is not None else self._dev(cells, torch.int32)).reshape(N, -1, 2)
         R = src.shape[1]
         if mask is not None:
             mask = self._t(mask, torch.uint8, (N, R))
-        if out is None:
-            out = {"field": torch.empty((N, R, 60, 60), dtype=torch.float32, device=dev),
-                   "goal_xy": torch.empty((N, R, 2), dtype=torch.float64, device=dev),
-                   "active": torch.empty((N, R), dtype=torch.uint8, device=dev),
-                   "sweeps": torch.empty((N, R), dtype=torch.int32, device=dev)}
+        out = self._out(out, {"field": ((N, R, 60, 60), torch.float32), "goal_xy": ((N, R, 2), torch.float64),
+                              "active": ((N, R), torch.uint8), "sweeps": ((N, R), torch.int32)})
         P = self.goal_params(R, window, rotate, radius)
         _lib.call(self.L, self.b.h, "cagym_ig_geodesic", C.byref(P), _lib.ptr(mask), _lib.ptr(src if points is not None else None),
                   _lib.ptr(src if cells is not None else None), out["field"].data_ptr(), out["goal_xy"].data_ptr(),
@@ -158,20 +169,9 @@ class InfoGain(object):
         device tensors it wrote: gain f64, n_visible i32, valid u8 (0: not finite, outside the map or within radius + 0.1 of an
         obstacle; its gain and n_visible are 0), each [N,P], or [N,60,60] indexed [j, i] for the map; `out`: such a dict to write
         into again (default: new tensors)."""
-        N, dev = self.b.N, self.b.device
-        if points is not None:
-            if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()):
-                points = self._t(points, torch.float64)
-            points = points.reshape(N, -1, 2)
-            shape = (N, points.shape[1])
-        else:
-            shape = (N, 60, 60)
-        if world_mask is not None:
-            world_mask = self._t(world_mask, torch.uint8, (N,))
-        if out is None:
-            out = {"gain": torch.empty(shape, dtype=torch.float64, device=dev), "n_visible": torch.empty(shape, dtype=torch.int32, device=dev),
-                   "valid": torch.empty(shape, dtype=torch.uint8, device=dev)}
-        P = self.view_params(n_points=shape[1] if points is not None else 0, radius=radius, range=range)
+        points, world_mask, shape, n_points = self._viewpoints(points, world_mask)
+        out = self._out(out, {"gain": (shape, torch.float64), "n_visible": (shape, torch.int32), "valid": (shape, torch.uint8)})
+        P = self.view_params(n_points=n_points, radius=radius, range=range)
         _lib.call(self.L, self.b.h, "cagym_ig_view_gain", C.byref(P), _lib.ptr(world_mask), _lib.ptr(points), out["gain"].data_ptr(),
                   out["n_visible"].data_ptr(), out["valid"].data_ptr(), self.b._stream())
         return out
@@ -185,28 +185,19 @@ class InfoGain(object):
         its outputs.  Returns the dict of device tensors it wrote: cells [N,R,k,2] i32 (i, j), xy [N,R,k,2] f64 their centres,
         utility, gain [N,R,k] f64, distance [N,R,k] f32, n_found [N,R] i32; rows past n_found hold cells -1, xy NaN, utility =
         gain = 0, distance +inf.  `out`: such a dict to write into again (default: new tensors)."""
-        N, dev = self.b.N, self.b.device
-        field = field if (torch.is_tensor(field) and field.is_cuda and field.dtype == torch.float32 and field.is_contiguous()) \
-            else self._t(field, torch.float32)
-        field = field.reshape(N, -1, 60, 60)
+        N = self.b.N
+        field = self._dev(field, torch.float32).reshape(N, -1, 60, 60)
         R, k = field.shape[1], int(k)
-        gain = gain if (torch.is_tensor(gain) and gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous()) \
-            else self._t(gain, torch.float64, (N, 60, 60))
-        valid = valid if (torch.is_tensor(valid) and valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous()) \
-            else self._t(valid, torch.uint8, (N, 60, 60))
+        gain = self._dev(gain, torch.float64, (N, 60, 60))
+        valid = self._dev(valid, torch.uint8, (N, 60, 60))
         if gain.numel() != N * 3600 or valid.numel() != N * 3600:
             raise ValueError("propose_goals: gain and valid must be [N, 60, 60] maps")
         if mask is not None:
             mask = self._t(mask, torch.uint8, (N, R))
         P = self.view_params(n_robots=R, k=k, min_sep=min_sep, d0=d0)
-        if out is None:
-            kk = max(k, 1)  # (a k the library refuses: nothing is written)
-            out = {"cells": torch.empty((N, R, kk, 2), dtype=torch.int32, device=dev),
-                   "xy": torch.empty((N, R, kk, 2), dtype=torch.float64, device=dev),
-                   "utility": torch.empty((N, R, kk), dtype=torch.float64, device=dev),
-                   "gain": torch.empty((N, R, kk), dtype=torch.float64, device=dev),
-                   "distance": torch.empty((N, R, kk), dtype=torch.float32, device=dev),
-                   "n_found": torch.empty((N, R), dtype=torch.int32, device=dev)}
+        kk = max(k, 1)  # (a k the library refuses: nothing is written)
+        out = self._out(out, {"cells": ((N, R, kk, 2), torch.int32), "xy": ((N, R, kk, 2), torch.float64), "utility": ((N, R, kk), torch.float64),
+                              "gain": ((N, R, kk), torch.float64), "distance": ((N, R, kk), torch.float32), "n_found": ((N, R), torch.int32)})
         _lib.call(self.L, self.b.h, "cagym_ig_propose_goals", C.byref(P), _lib.ptr(mask), gain.data_ptr(), valid.data_ptr(), field.data_ptr(),
                   *[out[n].data_ptr() for n in ("cells", "xy", "utility", "gain", "distance", "n_found")], self.b._stream())
         return out
@@ -234,32 +225,20 @@ class InfoGain(object):
         indexed [j, i] for the map - and "headings", the list used.  want_rows=False: the two [.., H] tensors are not written
         (NULL) and not returned.  `out`: a dict of such tensors to write into again (default: new tensors; with want_rows=True it
         must hold the two rows), which itself is left as it is: the result is a new dict of the same tensors."""
-        N, dev = self.b.N, self.b.device
         hs = self.heading_list(headings)
         H = len(hs)
-        if points is not None:
-            if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float64 and points.is_contiguous()):
-                points = self._t(points, torch.float64)
-            points = points.reshape(N, -1, 2)
-            shape = (N, points.shape[1])
-        else:
-            shape = (N, 60, 60)
-        if world_mask is not None:
-            world_mask = self._t(world_mask, torch.uint8, (N,))
-        if out is None:
-            out = {"best_heading": torch.empty(shape, dtype=torch.int32, device=dev),
-                   "best_gain": torch.empty(shape, dtype=torch.float64, device=dev),
-                   "valid": torch.empty(shape, dtype=torch.uint8, device=dev)}
-            if want_rows:
-                out["gain_h"] = torch.empty(shape + (H,), dtype=torch.float64, device=dev)
-                out["n_visible_h"] = torch.empty(shape + (H,), dtype=torch.int32, device=dev)
+        points, world_mask, shape, n_points = self._viewpoints(points, world_mask)
+        spec = {"best_heading": (shape, torch.int32), "best_gain": (shape, torch.float64), "valid": (shape, torch.uint8)}
+        if want_rows:
+            spec.update(gain_h=(shape + (H,), torch.float64), n_visible_h=(shape + (H,), torch.int32))
+        out = self._out(out, spec)
         rows = [out.get("gain_h"), out.get("n_visible_h")] if want_rows else [None, None]
         if want_rows and (rows[0] is None or rows[1] is None):
             raise ValueError("view_gain_headings: want_rows=True needs out['gain_h'] and out['n_visible_h']")
         for t in rows:
             if t is not None and t.shape[-1] != H:
                 raise ValueError("view_gain_headings: out's rows hold %d headings, asked for %d" % (t.shape[-1], H))
-        P = _lib.IgHeadingParams(shape[1] if points is not None else 0, H, 0, float(radius), float(self.range if range is None else range),
+        P = _lib.IgHeadingParams(n_points, H, 0, float(radius), float(self.range if range is None else range),
                                  self.fov, (C.c_double * 16)(*hs))
         _lib.call(self.L, self.b.h, "cagym_ig_view_gain_headings", C.byref(P), _lib.ptr(world_mask), _lib.ptr(points), _lib.ptr(rows[0]),
                   _lib.ptr(rows[1]), out["best_heading"].data_ptr(), out["best_gain"].data_ptr(), out["valid"].data_ptr(), self.b._stream())
@@ -327,16 +306,11 @@ class InfoGain(object):
         choose in slot order, each without the cells the earlier ones chose.  Returns the dict of device tensors it wrote:
         actions [N,R,2] f64, choice [N,R] u8 (255: no feasible candidate), mi [N,R,9] f64 (-1: infeasible), claimed [N,60] i64;
         `out`: such a dict to write into again (default: new tensors)."""
-        N, dev = self.b.N, self.b.device
-        if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous()):
-            poses = self._t(poses, torch.float64)
-        poses = poses.reshape(N, -1, 3)
+        N = self.b.N
+        poses = self._dev(poses, torch.float64).reshape(N, -1, 3)
         R = poses.shape[1]
-        if out is None:
-            out = {"actions": torch.empty((N, R, 2), dtype=torch.float64, device=dev),
-                  "choice": torch.empty((N, R), dtype=torch.uint8, device=dev),
-                  "mi": torch.empty((N, R, 9), dtype=torch.float64, device=dev),
-                  "claimed": torch.empty((N, 60), dtype=torch.int64, device=dev)}
+        out = self._out(out, {"actions": ((N, R, 2), torch.float64), "choice": ((N, R), torch.uint8), "mi": ((N, R, 9), torch.float64),
+                              "claimed": ((N, 60), torch.int64)})
         P = GreedyParams(R, int(bool(coordinate)), self.dt, float(radius), self.fov, self.range,
                          (C.c_double * 3)(*[float(x) for x in v]), (C.c_double * 3)(*[float(x) for x in w]))
         _lib.call(self.L, self.b.h, "cagym_ig_greedy_plan", C.byref(P), poses.data_ptr(),
