@@ -11,10 +11,14 @@ a look round, as every robot does at the start.  Everything stays on the device.
 cones there and hands the cone's heading back, ig_set_goals(..., headings=) makes the robot turn to it on arrival, and the robot
 gives its goal up once info["goal_facing"] says "there, and facing it" - there is no look round, at the start or anywhere else.
 
+--assign team (default apart: the pick above) leaves the choice to the env: ig_assign_goals prices every proposal by the mutual
+information of the cells no teammate - under way or just assigned - is already going to see, through the walls and inside the sensor's
+range (and cone, with --headings), and sends the robots that choose now to complementary viewpoints in one launch.
+
 The same seed, hence the same never-repeating sequence of worlds, is then run by the built-in ig_greedy; both keep the IG team's
 episode log, and stats.paired_by_key compares the two episode by episode on the worlds both finished.
 
-    python examples/exploration_viewpoints.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--k 8] [--spin 20] [--headings 0]
+    python examples/exploration_viewpoints.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--k 8] [--spin 20] [--headings 0] [--assign apart]
 """
 import argparse
 import importlib
@@ -78,6 +82,8 @@ def main():
     ap.add_argument("--d0", type=float, default=1.0, help="metres added to the distance in gain / (distance + d0)")
     ap.add_argument("--spin", type=int, default=20, help="steps a robot turns on the spot after it has arrived (20 x 0.1 s x pi rad/s: once round)")
     ap.add_argument("--headings", type=int, default=0, help="H > 0: proposals and goals carry the best of H headings; no look round")
+    ap.add_argument("--assign", choices=("apart", "team"), default="apart",
+                    help="apart: the best proposal min_sep from the teammates' targets; team: ig_assign_goals, marginal view gains")
     ap.add_argument("--turn", type=float, default=3.141592653589793, help="rad/s of that turn")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--capacity", type=int, default=65536, help="rows of each episode log")
@@ -108,12 +114,15 @@ def main():
         active = goals["active"] != 0
         need = ~active & (spin == 0)
         prop = env.ig_propose_goals(k=a.k, min_sep=a.min_sep, d0=a.d0, mask=need.to(torch.uint8), headings=a.headings if a.headings > 0 else None)
-        target = torch.where(active[:, :, None], goals["goal_xy"], nan)  # what the robots that keep their target aim at
-        target, rank = pick_apart(prop, target, need, a.min_sep)
-        if a.headings > 0:  # the chosen proposal's best cone: the robot turns to it once it is there
-            env.ig_set_goals(target, mask=need.to(torch.uint8), headings=prop["heading"].gather(2, rank[:, :, None])[:, :, 0])
+        if a.assign == "team":  # one launch: the team's marginal gains, the goals (and headings) set for the robots that choose now
+            rank = env.ig_assign_goals(mode="best", mask=need.to(torch.uint8))["choice"]  # (-1: nothing left to see, no goal)
         else:
-            env.ig_set_goals(target, mask=need.to(torch.uint8))
+            target = torch.where(active[:, :, None], goals["goal_xy"], nan)  # what the robots that keep their target aim at
+            target, rank = pick_apart(prop, target, need, a.min_sep)
+            if a.headings > 0:  # the chosen proposal's best cone: the robot turns to it once it is there
+                env.ig_set_goals(target, mask=need.to(torch.uint8), headings=prop["heading"].gather(2, rank[:, :, None])[:, :, 0])
+            else:
+                env.ig_set_goals(target, mask=need.to(torch.uint8))
         n_set += int(need.sum())  # (host reads per step: an example's bookkeeping, not a training loop's)
         n_shifted += int((need & (rank > 0)).sum())
         actions[:, :R, 1] = torch.where(spin > 0, a.turn, 0.0).to(torch.float32)  # (read only by robots without a target)

@@ -168,6 +168,15 @@ class IgHeadingParams(C.Structure):
                 ("range", C.c_double), ("fov", C.c_double), ("headings", C.c_double * 16)]
 
 
+class IgAssignParams(C.Structure):
+    """cagym_ig_assign_params (include/cagym_ig_assign.h; not in STRUCTS, as IgObserveParams)."""
+    _fields_ = [("n_robots", C.c_int32), ("k", C.c_int32), ("mode", C.c_int32), ("flags", C.c_uint32), ("radius", C.c_double),
+                ("range", C.c_double), ("d0", C.c_double), ("fov", C.c_double)]
+
+
+IG_ASSIGN_MODES = {"slot": 0, "best": 1}  # CAGYM_IG_ASSIGN_SLOT / CAGYM_IG_ASSIGN_BEST
+
+
 # cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
 IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
                 ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
@@ -273,6 +282,7 @@ _ARGTYPES = {
     "cagym_ig_view_gain": [_vp, _P(IgViewParams), _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_propose_goals": [_vp, _P(IgViewParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_view_gain_headings": [_vp, _P(IgHeadingParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cagym_ig_assign_goals": [_vp, _P(IgAssignParams)] + [_vp] * 15,
     "cagym_ig_goal_face_actions": [_vp, _P(IgGoalParams), _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_goal_face_status": [_vp, _P(IgGoalParams), C.c_double, _vp, _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],

@@ -39,7 +39,8 @@ class _IgGoals(object):
     """attach_ig_goals' state: the parameter block of the three launches and the tensors they keep."""
     __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice",
                  "view", "own", "proposals", "proposals_k",  # (second row: ig_view_gain's / ig_propose_goals' buffers, made on first use)
-                 "face_tol", "goal_heading", "goal_facing", "hview", "hprop")  # (third: goal headings, made by the first headings= call)
+                 "face_tol", "goal_heading", "goal_facing", "hview", "hprop",  # (third: goal headings, made by the first headings= call)
+                 "last_proposal", "assign")  # (fourth: ig_assign_goals' - what the last proposal call was, its buffers made on first use)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -337,7 +338,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         q.goal_distance = torch.full((N, R), float("inf"), dtype=torch.float32, device=dev)
         q.goal_reached = torch.zeros((N, R), dtype=torch.uint8, device=dev)
         q.choice = torch.full((N, R), 255, dtype=torch.uint8, device=dev)
-        q.view = q.own = q.proposals = q.proposals_k = None
+        q.view = q.own = q.proposals = q.proposals_k = q.last_proposal = q.assign = None
         q.face_tol, q.goal_heading, q.goal_facing, q.hview, q.hprop = float(face_tol), None, None, None, None
         self._goals = q
         self._alloc_act()
@@ -507,7 +508,61 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
                 q.hprop["heading_index"].copy_(torch.where(on, idx, q.hprop["heading_index"]))
                 q.hprop["heading"].copy_(torch.where(on, new, q.hprop["heading"]))
             res["heading_index"], res["heading"] = q.hprop["heading_index"], q.hprop["heading"]
+        q.last_proposal = (headings is not None, float(d0))  # what ig_assign_goals reads: whether this call's rows carry headings, its d0
         return res
+
+    def ig_assign_goals(self, mode="best", mask=None, claim_active=True, set_goals=True, d0=None):
+        """Send the masked robots (mask [N, R], default: every robot) to COMPLEMENTARY viewpoints: ONE launch on the current stream
+        (cagym_ig_assign_goals, InfoGain.assign_goals; ig.assign_goals_spec states the rule) on the buffers of the last
+        ig_propose_goals call - its xy and distance, its heading rows if that call had headings=, and by default its d0.  Every
+        proposal's visible cell set is a 60-word mask (the cone's with a heading, a robot turning on the spot without); the team
+        claims masks one robot at a time, and every proposal still open is priced by the mutual information of the cells nobody has
+        claimed yet, divided by distance + d0.  mode "best": every round assigns the best (robot, proposal) left; "slot": the
+        masked robots choose in slot order.  claim_active: the robots OUTSIDE the mask whose goal is active keep what they are going
+        to see from it - goal_xy, and goal_heading where one exists - before anybody chooses; a masked robot's own goal is no seed.
+        Returns the dict of device tensors choice, order [N, R] i32 (-1: nothing was left to see), marginal, utility [N, R] f64,
+        claimed [N, 60] i64, masks [N, R, k, 60] i64, round_gain [N, R, R, k] f64 indexed [round, robot, proposal] - what each of
+        a robot's k options is worth GIVEN what its teammates are already going to see, NaN where it was not priced - and the
+        gathered xy [N, R, 2] and heading [N, R] f64 of the chosen proposals, NaN where choice is -1 (and for robots outside the
+        mask, whose rows of the other tensors keep what they held).  set_goals: then ig_set_goals(xy, mask=mask, headings=heading
+        when the proposals carry headings): a masked robot for which nothing is left to see gets a NaN goal, that is, no active
+        goal - its row is the caller's.  The robots are the first R agent slots, as ig_propose_goals assumes.  The buffers are
+        allocated on the first call and written again by every later one with the same k; nothing synchronises."""
+        q = self._need_goals("ig_assign_goals")
+        if q.proposals is None or q.last_proposal is None:
+            raise RuntimeError("ig_assign_goals needs an earlier ig_propose_goals call: it assigns that call's proposals")
+        g, N, dev = self._igm, self.N, self.device
+        ig, R, k = g.ig, g.R, q.proposals_k
+        headed, d0_prop = q.last_proposal
+        d0 = d0_prop if d0 is None else float(d0)
+        if not (d0 > 0.0 and np.isfinite(d0)):
+            raise ValueError("ig_assign_goals: d0 must be finite and positive, got %r" % (d0,))
+        if mode not in _lib.IG_ASSIGN_MODES:
+            raise ValueError("ig_assign_goals: mode must be 'slot' or 'best', got %r" % (mode,))
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=dev).to(torch.uint8).reshape(N, R).contiguous()
+        a = q.assign
+        if a is None or a["masks"].shape[2] != k:
+            a = q.assign = {"choice": torch.full((N, R), -1, dtype=torch.int32, device=dev),
+                            "order": torch.full((N, R), -1, dtype=torch.int32, device=dev),
+                            "marginal": torch.zeros((N, R), dtype=torch.float64, device=dev),
+                            "utility": torch.zeros((N, R), dtype=torch.float64, device=dev),
+                            "claimed": torch.zeros((N, 60), dtype=torch.int64, device=dev),
+                            "masks": torch.zeros((N, R, k, 60), dtype=torch.int64, device=dev),
+                            "round_gain": torch.full((N, R, R, k), float("nan"), dtype=torch.float64, device=dev)}
+        seeds = {}
+        if claim_active and mask is not None:  # (with every robot choosing there is nobody under way)
+            seeds = dict(claim=q.out["active"], claim_xy=q.out["goal_xy"], claim_heading=q.goal_heading)
+        ig.assign_goals(q.proposals["xy"], q.proposals["distance"], cand_heading=q.hprop["heading"] if headed else None, mask=mask,
+                        mode=mode, radius=q.P.radius, d0=d0, out=a, **seeds)
+        on = a["choice"] >= 0 if mask is None else (a["choice"] >= 0) & (mask != 0)
+        idx = a["choice"].clamp(min=0).long()
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        xy = torch.where(on[:, :, None], torch.gather(q.proposals["xy"], 2, idx[:, :, None, None].expand(N, R, 1, 2))[:, :, 0], nan)
+        heading = torch.where(on, torch.gather(q.hprop["heading"], 2, idx[:, :, None])[:, :, 0], nan) if headed else torch.full_like(a["marginal"], float("nan"))
+        if set_goals:
+            self.ig_set_goals(xy, mask=mask, headings=heading if headed else None)
+        return dict(a, xy=xy, heading=heading)
 
     def _ig_goal_status(self, restart_mask):
         q = self._goals

@@ -15,6 +15,7 @@
 #include "../../include/cagym_ig_goals.h"
 #include "../../include/cagym_ig_viewpoints.h"
 #include "../../include/cagym_ig_headings.h"
+#include "../../include/cagym_ig_assign.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -37,6 +38,7 @@
 #include "cagym_ig_geodesic.h"
 #include "cagym_ig_viewpoints.h"
 #include "cagym_ig_headings.h"
+#include "cagym_ig_assign.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2310,6 +2312,34 @@ int cagym_ig_view_gain_headings(void* env, const cagym_ig_heading_params* params
     if (blocks == 0) return CAGYM_OK;
     hipLaunchKernelGGL(k_ig_view_gain_headings, dim3((unsigned)blocks), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
                        P, world_mask, points_xy, gain_h, n_visible_h, best_heading, best_gain, valid);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- team goal assignment (csrc/cagym_ig_assign.h) --------------------------------------------------------------------------------------
+int cagym_ig_assign_goals(void* env, const cagym_ig_assign_params* params, const uint8_t* mask, const double* cand_xy,
+                          const double* cand_heading, const float* cand_distance, const uint8_t* claim, const double* claim_xy,
+                          const double* claim_heading, int32_t* choice, int32_t* order, double* marginal, double* utility,
+                          uint64_t* claimed, uint64_t* masks, double* round_gain, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_assign_goals");
+    const char* name = "cagym_ig_assign_goals";
+    if (!params || !cand_xy || !cand_distance || !choice || !order || !marginal || !utility || !claimed || !masks)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_assign_goals: null argument");
+    const cagym_ig_assign_params& p = *params;
+    if (int rc = ig_team_check(e, name, p.n_robots)) return rc;
+    if (p.k < 1 || p.k > IGV_MAXK) return fail(e, CAGYM_E_INVALID, "cagym_ig_assign_goals: k must be 1..16");
+    if (p.mode != CAGYM_IG_ASSIGN_SLOT && p.mode != CAGYM_IG_ASSIGN_BEST)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_assign_goals: mode must be 0 (slot order) or 1 (best first)");
+    if (int rc = ig_flags_check(e, name, p.flags, 0)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.radius, p.range, p.d0, p.fov}, "radius, range, d0 and fov must be finite and positive")) return rc;
+    if (claim && !claim_xy) return fail(e, CAGYM_E_INVALID, "cagym_ig_assign_goals: claim needs claim_xy");
+    IgAssignParams P;
+    P.R = p.n_robots; P.k = p.k; P.mode = p.mode;
+    P.radius = p.radius; P.range = p.range; P.fov = p.fov; P.d0 = p.d0;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_assign_goals, dim3((unsigned)e->cfg.n_worlds), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
+                       P, mask, cand_xy, cand_heading, cand_distance, claim, claim_xy, claim_heading, choice, order, marginal, utility,
+                       reinterpret_cast<unsigned long long*>(claimed), reinterpret_cast<unsigned long long*>(masks), round_gain);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

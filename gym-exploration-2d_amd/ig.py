@@ -202,6 +202,53 @@ class InfoGain(object):
                   *[out[n].data_ptr() for n in ("cells", "xy", "utility", "gain", "distance", "n_found")], self.b._stream())
         return out
 
+    def assign_goals(self, cand_xy, cand_distance, cand_heading=None, mask=None, claim=None, claim_xy=None, claim_heading=None, mode="best",
+                     radius=0.5, range=None, d0=1.0, out=None, want_rounds=True):
+        """cagym_ig_assign_goals: ONE launch on the current stream, one workgroup per world - a TEAM's goals by the sequential-greedy
+        allocation of coverage (ig.assign_goals_spec states the rule).  cand_xy [N,R,k,2] f64 and cand_distance [N,R,k] f32: every
+        robot's k candidate goals and how far each is (propose_goals()' xy and distance); cand_heading [N,R,k] f64 or None: with a
+        finite heading a candidate's cell set is visible_cells() of the pose (this object's fov), without one (NaN, or None for
+        all) the cells view_gain() counts at the point.  mask [N,R] u8 or None (every robot): the robots that choose now; a robot
+        whose byte is 0 keeps every byte of its rows, and a world without a masked robot is not touched at all.  claim [N,R] u8
+        with claim_xy [N,R,2] f64 and claim_heading [N,R] f64 or None: robots OUTSIDE the mask whose claim byte is set keep the
+        cells of that pose - teammates under way.  Every candidate is priced by mi_reward() of its cells that nobody has claimed
+        yet (bit for bit), and ranked by that marginal gain / (distance + d0).  mode "slot": the masked robots choose in slot
+        order; "best": every round assigns the best (robot, candidate) left.  Returns the dict of device tensors it wrote: choice,
+        order [N,R] i32 (-1: nothing was left to see), marginal, utility [N,R] f64, claimed [N,60] i64 the final union, masks
+        [N,R,k,60] i64 every candidate's cell set before any claim and, with want_rounds, round_gain [N,R,R,k] f64 indexed [round,
+        robot, candidate] (NaN: not priced in that round).  `out`: such a dict to write into again (default: new tensors)."""
+        N = self.b.N
+        if mode not in _lib.IG_ASSIGN_MODES:
+            raise ValueError("assign_goals: mode must be 'slot' or 'best', got %r" % (mode,))
+        dist = self._dev(cand_distance, torch.float32)
+        if dist.dim() != 3 or dist.shape[0] != N:
+            raise ValueError("assign_goals: cand_distance must be [N, R, k]")
+        R, k = int(dist.shape[1]), int(dist.shape[2])
+        xy = self._dev(cand_xy, torch.float64).reshape(N, R, k, 2)
+        hd = None if cand_heading is None else self._dev(cand_heading, torch.float64).reshape(N, R, k)
+        if mask is not None:
+            mask = self._t(mask, torch.uint8, (N, R))
+        if claim is not None:
+            if claim_xy is None:
+                raise ValueError("assign_goals: claim needs claim_xy")
+            claim = self._t(claim, torch.uint8, (N, R))
+        cxy = None if claim_xy is None else self._dev(claim_xy, torch.float64).reshape(N, R, 2)
+        chd = None if claim_heading is None else self._dev(claim_heading, torch.float64).reshape(N, R)
+        spec = {"choice": ((N, R), torch.int32), "order": ((N, R), torch.int32), "marginal": ((N, R), torch.float64),
+                "utility": ((N, R), torch.float64), "claimed": ((N, 60), torch.int64), "masks": ((N, R, k, 60), torch.int64)}
+        if want_rounds:
+            spec["round_gain"] = ((N, R, R, k), torch.float64)
+        out = self._out(out, spec)
+        rounds = out.get("round_gain") if want_rounds else None
+        if want_rounds and rounds is None:
+            raise ValueError("assign_goals: want_rounds=True needs out['round_gain']")
+        P = _lib.IgAssignParams(R, k, _lib.IG_ASSIGN_MODES[mode], 0, float(radius), float(self.range if range is None else range), float(d0),
+                                self.fov)
+        _lib.call(self.L, self.b.h, "cagym_ig_assign_goals", C.byref(P), _lib.ptr(mask), xy.data_ptr(), _lib.ptr(hd), dist.data_ptr(),
+                  _lib.ptr(claim), _lib.ptr(cxy), _lib.ptr(chd), *[out[n].data_ptr() for n in ("choice", "order", "marginal", "utility", "claimed", "masks")],
+                  _lib.ptr(rounds), self.b._stream())
+        return out if want_rounds else {n: v for n, v in out.items() if n != "round_gain"}
+
     def heading_list(self, headings):
         """The headings a caller means: an int H is h * 2 pi / H for h = 0..H-1, computed in fp64 here; a sequence is taken as
         given (radians).  Returns a list of 1..16 floats."""
@@ -759,6 +806,77 @@ def goal_face_spec(pose, goal_xy, goal_heading, dt, w_max, goal_tol, face_tol):
     if not reached:
         return None, False, False
     return (0.0, min(max(err / dt, -w_max), w_max)), True, abs(err) <= face_tol
+
+
+def cells_to_words(cells):
+    """bool [.., 60, 60] indexed [j, i] -> the library's visibility words [.., 60] uint64 (bit i of word j <=> cell (i, j))"""
+    cells = np.asarray(cells, dtype=bool)
+    return (cells.astype(np.uint64) << np.arange(60, dtype=np.uint64)).sum(axis=-1, dtype=np.uint64)
+
+
+def words_to_cells(words):
+    """the library's visibility words [.., 60] (uint64, or the int64 a tensor holds) -> bool [.., 60, 60] indexed [j, i]"""
+    words = np.ascontiguousarray(words)
+    words = words.view(np.uint64) if words.dtype == np.int64 else words.astype(np.uint64)
+    return ((words[..., None] >> np.arange(60, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+
+
+def assign_goals_spec(masks, claimed0, distance, valid, reward, mode, d0, open_robots):
+    """The team assignment of cagym_ig_assign_goals for one world, in numpy - its specification, given the candidates' cell sets.
+    masks [R, k, 60, 60] bool indexed [j, i]: every candidate's cell set (view_gain_spec(...)[3] for a candidate without a heading,
+    view_gain_headings_spec(...)["masks"][h] for one with; empty for an invalid point); claimed0 [60, 60] bool: the seed, the union of
+    the cell sets of the teammates under way; distance [R, k] f32; valid [R, k]: the points that pass view_gain_spec's rule;
+    reward(cells [60, 60] bool) -> float: the mutual information of a cell set (InfoGain.mi_reward on the device, oracle.mi_reward
+    on a belief); mode "slot" / "best" (or 0 / 1); d0 > 0; open_robots: the robots that choose now, a sequence of slots or a bool [R].
+      marginal gain of a candidate = reward(cells & ~claimed); eligible <=> valid, distance finite, marginal > 0;
+      utility = marginal / ((double)distance + d0), one fp64 addition and one fp64 division.
+      "slot": round t is the turn of the t-th open robot in slot order; it takes its eligible candidate of largest utility, of equal
+        utilities the smaller index, and claimed |= cells; none eligible: choice -1, nothing claimed.
+      "best": up to len(open_robots) rounds; each takes the eligible (robot, candidate) of largest utility among the open robots not
+        yet assigned - ties to the smaller slot, then the smaller index - and claimed |= cells; the rounds stop when nothing is eligible.
+    Returns a dict: choice, order [R] int32 (-1: unassigned, and every robot that is not open), marginal, utility [R] f64 (0 likewise),
+    claimed [60, 60] bool the final union, round_gain [R, R, k] f64 indexed [round, robot, candidate]: the marginal gain of every
+    valid candidate with a finite distance priced in that round ("slot": the robot whose turn it is, "best": every robot still
+    open), NaN everywhere else."""
+    masks = np.asarray(masks, dtype=bool)
+    R, k = masks.shape[:2]
+    dist = np.asarray(distance, dtype=np.float32).reshape(R, k)
+    ok = np.asarray(valid).reshape(R, k).astype(bool) & np.isfinite(dist)
+    mode = {"slot": 0, "best": 1, 0: 0, 1: 1}[mode]
+    d0 = float(d0)
+    o = np.asarray(open_robots)
+    opened = [int(r) for r in (np.flatnonzero(o) if o.dtype == bool else o.ravel())]
+    if sorted(set(opened)) != opened or any(r < 0 or r >= R for r in opened):
+        raise ValueError("assign_goals_spec: open_robots must be distinct slots in ascending order")
+    claimed = np.array(claimed0, dtype=bool).reshape(60, 60).copy()
+    out = {"choice": np.full(R, -1, dtype=np.int32), "order": np.full(R, -1, dtype=np.int32), "marginal": np.zeros(R), "utility": np.zeros(R),
+           "round_gain": np.full((R, R, k), np.nan)}
+    left = list(opened)
+    for t in range(len(opened)):
+        pricing = [opened[t]] if mode == 0 else list(left)
+        best = None  # (utility, robot, candidate, marginal)
+        for r in pricing:
+            for c in range(k):
+                if not ok[r, c]:
+                    continue
+                m = float(reward(masks[r, c] & ~claimed))
+                out["round_gain"][t, r, c] = m
+                if not m > 0:
+                    continue
+                with np.errstate(divide="ignore", over="ignore"):
+                    u = float(np.float64(m) / (np.float64(dist[r, c]) + np.float64(d0)))
+                if best is None or u > best[0]:  # (in ascending (slot, index): the strict test keeps the first of equal utilities)
+                    best = (u, r, c, m)
+        if best is None:
+            if mode == 1:
+                break
+            continue
+        u, r, c, m = best
+        out["choice"][r], out["order"][r], out["marginal"][r], out["utility"][r] = c, t, m, u
+        claimed |= masks[r, c]
+        left.remove(r)
+    out["claimed"] = claimed
+    return out
 
 
 def propose_goals_spec(gain, valid, field, k, min_sep, d0):

@@ -655,6 +655,42 @@ int cagym_ig_goal_face_actions(void* env, const cagym_ig_goal_params* params, co
 int cagym_ig_goal_face_status(void* env, const cagym_ig_goal_params* params, double face_tol, const double* goal_xy,
                               const uint8_t* active, const double* goal_heading, uint8_t* goal_facing, void* stream);
 
+/* ---- Team goal assignment: marginal view gains -------------------------------------------------------------------------------------
+ * cagym_ig_assign_goals: ONE launch on `stream`, on demand (no step runs it), one workgroup per world, no host synchronisation, no
+ * global atomics; two launches give the same bytes.  The sequential-greedy allocation of coverage over the robots' candidate goals:
+ * every candidate's visible cell set is a 60 x u64 mask, the team claims masks one robot at a time, and every candidate still open is
+ * priced by the mutual information of the cells nobody has claimed yet.  params: cagym_ig_assign_params, defined in
+ * include/cagym_ig_assign.h (n_robots = R 1..8, k 1..16, mode, flags = 0, radius, range, d0, fov).
+ * Inputs, DEVICE: mask [N,R] u8 or NULL (= every robot) the robots that choose now; cand_xy [N,R,k,2] f64; cand_heading [N,R,k] f64
+ * or NULL, an entry that is not finite (NaN) = omnidirectional; cand_distance [N,R,k] f32; claim [N,R] u8 or NULL, with it claim_xy
+ * [N,R,2] f64 and claim_heading [N,R] f64 or NULL.
+ *   cell set of a pose: with a finite heading exactly the mask cagym_ig_visible_cells returns for (x, y, heading) with this fov and
+ *     range; without one exactly the cells cagym_ig_view_gain counts at the point with this range.  A point that fails
+ *     cagym_ig_view_gain's `valid` rule at this radius has the empty set.
+ *   claimed starts as the union of the cell sets of (claim_xy, claim_heading) of every robot with claim != 0 and mask == 0; a masked
+ *     robot's claim byte is ignored.
+ *   marginal gain of a candidate = the double cagym_ig_mi_reward returns for cells & ~claimed, bit for bit.
+ *   eligible <=> the point is valid, cand_distance is finite and the marginal gain is > 0; utility = marginal / ((double)distance + d0).
+ *   mode CAGYM_IG_ASSIGN_SLOT: the masked robots take turns in slot order, each taking its eligible candidate of largest utility (of
+ *     equal ones the smaller index), then claimed |= cells; none eligible: choice -1, nothing claimed.
+ *   mode CAGYM_IG_ASSIGN_BEST: up to R rounds, each assigning the eligible (robot, candidate) of largest utility among the masked
+ *     robots still open (ties: the smaller slot, then the smaller index); the rounds stop when nothing is eligible.
+ * Outputs, DEVICE: choice [N,R] i32 the candidate or -1; order [N,R] i32 the round (0-based; SLOT: the robot's turn) in which it was
+ * assigned or -1; marginal, utility [N,R] f64 the chosen candidate's at that round, 0 when unassigned; claimed [N,60] u64 the final
+ * union, seeds included; masks [N,R,k,60] u64 every candidate's cell set before any claim (required: the kernel's workspace);
+ * round_gain [N,R,R,k] f64 or NULL, indexed [round, robot, candidate]: the marginal gain of every candidate priced in that round
+ * (SLOT: the robot whose turn it is; BEST: every robot still open), NaN for everything else - robots assigned or outside the mask,
+ * invalid points, non-finite distances, rounds that were not played.  Rows of robots outside the mask keep every byte (masks
+ * included); a world without a masked robot is neither read nor written, claimed included.
+ * Errors, before anything is touched: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params, cand_xy, cand_distance
+ * or required output, n_robots outside 1..8, k outside 1..16, a mode outside {0, 1}, flags != 0, a radius, range, d0 or fov that is
+ * not finite or not positive, claim without claim_xy; CAGYM_E_DEVICE as every launching entry. */
+typedef struct cagym_ig_assign_params cagym_ig_assign_params;
+int cagym_ig_assign_goals(void* env, const cagym_ig_assign_params* params, const uint8_t* mask, const double* cand_xy,
+                          const double* cand_heading, const float* cand_distance, const uint8_t* claim, const double* claim_xy,
+                          const double* claim_heading, int32_t* choice, int32_t* order, double* marginal, double* utility,
+                          uint64_t* claimed, uint64_t* masks, double* round_gain, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
