@@ -15,10 +15,16 @@ gives its goal up once info["goal_facing"] says "there, and facing it" - there i
 information of the cells no teammate - under way or just assigned - is already going to see, through the walls and inside the sensor's
 range (and cone, with --headings), and sends the robots that choose now to complementary viewpoints in one launch.
 
+--rank route (default utility: one of the picks above) prices the WAY as well: ig_route_gains walks every proposal's shortest path on
+the robot's own geodesic field, takes the sensor cone every --stride cells along it - what the robot will see while it drives - and
+sends each robot that chooses now to the proposal whose route and view together are worth most per metre, in one launch; --assign is
+not consulted then.
+
 The same seed, hence the same never-repeating sequence of worlds, is then run by the built-in ig_greedy; both keep the IG team's
 episode log, and stats.paired_by_key compares the two episode by episode on the worlds both finished.
 
     python examples/exploration_viewpoints.py [--worlds 64] [--depth 2] [--steps 128] [--robots 2] [--targets 3] [--k 8] [--spin 20] [--headings 0] [--assign apart]
+                                             [--rank utility] [--stride 4]
 """
 import argparse
 import importlib
@@ -84,6 +90,9 @@ def main():
     ap.add_argument("--headings", type=int, default=0, help="H > 0: proposals and goals carry the best of H headings; no look round")
     ap.add_argument("--assign", choices=("apart", "team"), default="apart",
                     help="apart: the best proposal min_sep from the teammates' targets; team: ig_assign_goals, marginal view gains")
+    ap.add_argument("--rank", choices=("utility", "route"), default="utility",
+                    help="utility: the pick of --assign on the proposals' own view gains; route: ig_route_gains' best, the way there priced too")
+    ap.add_argument("--stride", type=int, default=4, help="--rank route: path cells between two way-points")
     ap.add_argument("--turn", type=float, default=3.141592653589793, help="rad/s of that turn")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--capacity", type=int, default=65536, help="rows of each episode log")
@@ -114,7 +123,9 @@ def main():
         active = goals["active"] != 0
         need = ~active & (spin == 0)
         prop = env.ig_propose_goals(k=a.k, min_sep=a.min_sep, d0=a.d0, mask=need.to(torch.uint8), headings=a.headings if a.headings > 0 else None)
-        if a.assign == "team":  # one launch: the team's marginal gains, the goals (and headings) set for the robots that choose now
+        if a.rank == "route":  # one launch: every proposal's route and view priced, the goals (and headings) set for the robots that choose now
+            rank = env.ig_route_gains(mask=need.to(torch.uint8), stride=a.stride, set_goals=True)["best"]  # (-1: no route or nothing to see, no goal)
+        elif a.assign == "team":  # one launch: the team's marginal gains, the goals (and headings) set for the robots that choose now
             rank = env.ig_assign_goals(mode="best", mask=need.to(torch.uint8))["choice"]  # (-1: nothing left to see, no goal)
         else:
             target = torch.where(active[:, :, None], goals["goal_xy"], nan)  # what the robots that keep their target aim at

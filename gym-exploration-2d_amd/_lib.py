@@ -177,6 +177,15 @@ class IgAssignParams(C.Structure):
 IG_ASSIGN_MODES = {"slot": 0, "best": 1}  # CAGYM_IG_ASSIGN_SLOT / CAGYM_IG_ASSIGN_BEST
 
 
+class IgRouteParams(C.Structure):
+    """cagym_ig_route_params (include/cagym_ig_route.h; not in STRUCTS, as IgObserveParams)."""
+    _fields_ = [("n_robots", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("flags", C.c_uint32), ("radius", C.c_double),
+                ("range", C.c_double), ("fov", C.c_double), ("d0", C.c_double)]
+
+
+IG_ROUTE_MAX_WAYPOINTS = 16  # CAGYM_IG_ROUTE_MAX_WAYPOINTS
+
+
 # cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
 IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
                 ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
@@ -283,6 +292,7 @@ _ARGTYPES = {
     "cagym_ig_propose_goals": [_vp, _P(IgViewParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_view_gain_headings": [_vp, _P(IgHeadingParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_assign_goals": [_vp, _P(IgAssignParams)] + [_vp] * 15,
+    "cagym_ig_route_gains": [_vp, _P(IgRouteParams)] + [_vp] * 17,
     "cagym_ig_goal_face_actions": [_vp, _P(IgGoalParams), _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_goal_face_status": [_vp, _P(IgGoalParams), C.c_double, _vp, _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],

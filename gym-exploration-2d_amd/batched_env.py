@@ -40,7 +40,8 @@ class _IgGoals(object):
     __slots__ = ("P", "out", "goal_distance", "goal_reached", "choice",
                  "view", "own", "proposals", "proposals_k",  # (second row: ig_view_gain's / ig_propose_goals' buffers, made on first use)
                  "face_tol", "goal_heading", "goal_facing", "hview", "hprop",  # (third: goal headings, made by the first headings= call)
-                 "last_proposal", "assign")  # (fourth: ig_assign_goals' - what the last proposal call was, its buffers made on first use)
+                 "last_proposal", "assign",  # (fourth: ig_assign_goals' - what the last proposal call was, its buffers made on first use)
+                 "route")  # (fifth: ig_route_gains' buffers, made on first use)
 
 
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
@@ -338,7 +339,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         q.goal_distance = torch.full((N, R), float("inf"), dtype=torch.float32, device=dev)
         q.goal_reached = torch.zeros((N, R), dtype=torch.uint8, device=dev)
         q.choice = torch.full((N, R), 255, dtype=torch.uint8, device=dev)
-        q.view = q.own = q.proposals = q.proposals_k = q.last_proposal = q.assign = None
+        q.view = q.own = q.proposals = q.proposals_k = q.last_proposal = q.assign = q.route = None
         q.face_tol, q.goal_heading, q.goal_facing, q.hview, q.hprop = float(face_tol), None, None, None, None
         self._goals = q
         self._alloc_act()
@@ -560,6 +561,56 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
         xy = torch.where(on[:, :, None], torch.gather(q.proposals["xy"], 2, idx[:, :, None, None].expand(N, R, 1, 2))[:, :, 0], nan)
         heading = torch.where(on, torch.gather(q.hprop["heading"], 2, idx[:, :, None])[:, :, 0], nan) if headed else torch.full_like(a["marginal"], float("nan"))
+        if set_goals:
+            self.ig_set_goals(xy, mask=mask, headings=heading if headed else None)
+        return dict(a, xy=xy, heading=heading)
+
+    def ig_route_gains(self, mask=None, stride=4, d0=None, exclude=None, set_goals=False):
+        """Price what the masked robots (mask [N, R], default: every robot) see ON THE WAY to each of their proposals: ONE launch on
+        the current stream (cagym_ig_route_gains, InfoGain.route_gains; ig.route_spec and ig.route_gains_spec state the rule) on the
+        buffers of the last ig_propose_goals call - its cells, its field from every robot's own position, its heading rows if that
+        call had headings=, and by default its d0.  Every proposal's shortest path is walked back on that field by the goal
+        controller's neighbour rule; every `stride` cells along it, at most 16 times, the sensor cone is taken looking the way the
+        robot drives; the union, and the union with the proposal's own view, are priced by the mutual information of their cells
+        outside `exclude` [N, 60] i64 (e.g. ig_assign_goals(...)["claimed"]; default: nothing).  Returns the dict of device tensors
+        route_masks, total_masks [N, R, k, 60] i64, route_gain, total_gain, utility [N, R, k] f64 (utility = total_gain / (distance
+        + d0)), n_path, n_way [N, R, k] i32 (n_path -1: no route), truncated [N, R, k] u8, best [N, R] i32 (the proposal of largest
+        utility that has a route and total_gain > 0; -1: none), and the gathered xy [N, R, 2] and heading [N, R] f64 of `best`, NaN
+        where it is -1 (and for robots outside the mask, whose rows of the other tensors keep what they held).  set_goals: then
+        ig_set_goals(xy, mask=mask, headings=heading when the proposals carry headings), exactly as ig_assign_goals does.  The
+        buffers are allocated on the first call and written again by every later one with the same k; nothing synchronises, and
+        step() gains no launch."""
+        q = self._need_goals("ig_route_gains")
+        if q.proposals is None or q.last_proposal is None:
+            raise RuntimeError("ig_route_gains needs an earlier ig_propose_goals call: it prices that call's proposals")
+        g, N, dev = self._igm, self.N, self.device
+        ig, R, k = g.ig, g.R, q.proposals_k
+        headed, d0_prop = q.last_proposal
+        d0 = d0_prop if d0 is None else float(d0)
+        if not (d0 > 0.0 and np.isfinite(d0)):
+            raise ValueError("ig_route_gains: d0 must be finite and positive, got %r" % (d0,))
+        if int(stride) < 1:
+            raise ValueError("ig_route_gains: stride must be at least 1, got %r" % (stride,))
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=dev).to(torch.uint8).reshape(N, R).contiguous()
+        a = q.route
+        if a is None or a["route_masks"].shape[2] != k:
+            a = q.route = {"route_masks": torch.zeros((N, R, k, 60), dtype=torch.int64, device=dev),
+                           "total_masks": torch.zeros((N, R, k, 60), dtype=torch.int64, device=dev),
+                           "route_gain": torch.zeros((N, R, k), dtype=torch.float64, device=dev),
+                           "total_gain": torch.zeros((N, R, k), dtype=torch.float64, device=dev),
+                           "utility": torch.zeros((N, R, k), dtype=torch.float64, device=dev),
+                           "n_path": torch.full((N, R, k), -1, dtype=torch.int32, device=dev),
+                           "n_way": torch.zeros((N, R, k), dtype=torch.int32, device=dev),
+                           "truncated": torch.zeros((N, R, k), dtype=torch.uint8, device=dev),
+                           "best": torch.full((N, R), -1, dtype=torch.int32, device=dev)}
+        ig.route_gains(q.own["field"], q.proposals["cells"], cand_heading=q.hprop["heading"] if headed else None, mask=mask,
+                       exclude=exclude, stride=int(stride), radius=q.P.radius, d0=d0, out=a)
+        on = a["best"] >= 0 if mask is None else (a["best"] >= 0) & (mask != 0)
+        idx = a["best"].clamp(min=0).long()
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        xy = torch.where(on[:, :, None], torch.gather(q.proposals["xy"], 2, idx[:, :, None, None].expand(N, R, 1, 2))[:, :, 0], nan)
+        heading = torch.where(on, torch.gather(q.hprop["heading"], 2, idx[:, :, None])[:, :, 0], nan) if headed else torch.full_like(xy[:, :, 0], float("nan"))
         if set_goals:
             self.ig_set_goals(xy, mask=mask, headings=heading if headed else None)
         return dict(a, xy=xy, heading=heading)

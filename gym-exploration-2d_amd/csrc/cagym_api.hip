@@ -16,6 +16,7 @@
 #include "../../include/cagym_ig_viewpoints.h"
 #include "../../include/cagym_ig_headings.h"
 #include "../../include/cagym_ig_assign.h"
+#include "../../include/cagym_ig_route.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -39,6 +40,7 @@
 #include "cagym_ig_viewpoints.h"
 #include "cagym_ig_headings.h"
 #include "cagym_ig_assign.h"
+#include "cagym_ig_route.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2340,6 +2342,39 @@ int cagym_ig_assign_goals(void* env, const cagym_ig_assign_params* params, const
     hipLaunchKernelGGL(k_ig_assign_goals, dim3((unsigned)e->cfg.n_worlds), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
                        P, mask, cand_xy, cand_heading, cand_distance, claim, claim_xy, claim_heading, choice, order, marginal, utility,
                        reinterpret_cast<unsigned long long*>(claimed), reinterpret_cast<unsigned long long*>(masks), round_gain);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+// ---- route gains (csrc/cagym_ig_route.h) ------------------------------------------------------------------------------------------------
+int cagym_ig_route_gains(void* env, const cagym_ig_route_params* params, const uint8_t* mask, const float* field,
+                         const int32_t* cand_cells, const double* cand_heading, const uint64_t* exclude, uint64_t* route_masks,
+                         uint64_t* total_masks, double* route_gain, double* total_gain, double* utility, int32_t* n_path,
+                         int32_t* n_way, uint8_t* truncated, int32_t* best, int32_t* way_cells, int8_t* way_dir, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_route_gains");
+    const char* name = "cagym_ig_route_gains";
+    if (!params || !field || !cand_cells || !route_masks || !total_masks || !route_gain || !total_gain || !utility || !n_path || !n_way ||
+        !truncated || !best)
+        return fail(e, CAGYM_E_INVALID, "cagym_ig_route_gains: null argument");
+    const cagym_ig_route_params& p = *params;
+    if (int rc = ig_team_check(e, name, p.n_robots)) return rc;
+    if (p.k < 1 || p.k > IGV_MAXK) return fail(e, CAGYM_E_INVALID, "cagym_ig_route_gains: k must be 1..16");
+    if (p.stride < 1) return fail(e, CAGYM_E_INVALID, "cagym_ig_route_gains: stride must be at least 1");
+    if (int rc = ig_flags_check(e, name, p.flags, 0)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.radius, p.range, p.fov, p.d0}, "radius, range, fov and d0 must be finite and positive")) return rc;
+    IgRouteParams P;
+    P.R = p.n_robots; P.k = p.k;
+    P.stride = std::min(p.stride, IGR_WALK_CAP + 1);  // (no path has more moves: the same way-points, and no product near INT_MAX)
+    P.radius = p.radius; P.range = p.range; P.fov = p.fov; P.d0 = p.d0;
+    IgRouteOut O;
+    O.route_masks = reinterpret_cast<unsigned long long*>(route_masks);
+    O.total_masks = reinterpret_cast<unsigned long long*>(total_masks);
+    O.route_gain = route_gain; O.total_gain = total_gain; O.utility = utility;
+    O.n_path = n_path; O.n_way = n_way; O.truncated = truncated; O.best = best;
+    O.way_cells = way_cells; O.way_dir = way_dir;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(k_ig_route_gains, dim3((unsigned)e->cfg.n_worlds), dim3(IGV_THREADS), 0, reinterpret_cast<hipStream_t>(stream), e->G,
+                       P, mask, field, cand_cells, cand_heading, reinterpret_cast<const unsigned long long*>(exclude), O);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

@@ -249,6 +249,53 @@ class InfoGain(object):
                   _lib.ptr(rounds), self.b._stream())
         return out if want_rounds else {n: v for n, v in out.items() if n != "round_gain"}
 
+    def route_gains(self, field, cand_cells, cand_heading=None, mask=None, exclude=None, stride=4, radius=0.5, range=None, d0=1.0, out=None,
+                    want_waypoints=False):
+        """cagym_ig_route_gains: ONE launch on the current stream, one workgroup per world - what a robot sees ON THE WAY to each of
+        its candidate goals (ig.route_spec and ig.route_gains_spec state the rule).  field [N,R,60,60] f32: every robot's geodesic
+        field with its own position as the source (geodesic(points=robot positions)["field"]); cand_cells [N,R,k,2] i32 (i, j):
+        the candidates (propose_goals()' cells; a cell outside 0..59 has no route); cand_heading [N,R,k] f64 or None: with a finite
+        heading the candidate's own set is the cone's, without one a robot turning on the spot, as assign_goals() has it.  mask
+        [N,R] u8 or None (every robot): a robot whose byte is 0 keeps every byte of its rows, a world without a masked robot is not
+        touched.  exclude [N,60] i64 or None: cells already spoken for (assign_goals()["claimed"]).  Every candidate's shortest
+        path is walked back on the field by the controller's neighbour rule; every `stride` cells along it - at most 16 times - the
+        cone of this object's fov is taken at the cell's centre, looking the way the robot drives; route = their union, total =
+        route | the candidate's own set, each priced by mi_reward() of its cells outside `exclude` (bit for bit), utility =
+        total_gain / (field[cell] + d0).  Returns the dict of device tensors it wrote: route_masks, total_masks [N,R,k,60] i64,
+        route_gain, total_gain, utility [N,R,k] f64, n_path [N,R,k] i32 (the path's moves; -1: no route - gains 0, empty masks),
+        n_way [N,R,k] i32, truncated [N,R,k] u8 (way-points beyond the 16th were dropped), best [N,R] i32 (the candidate with a
+        route and total_gain > 0 of largest utility, ties to the smaller index; -1: none) and, with want_waypoints, way_cells
+        [N,R,k,16,2] i32 and way_dir [N,R,k,16] i8 (the way-points in travel order and the move into each, an index into
+        GEO_NEIGHBOURS; rows past n_way -1).  `out`: such a dict to write into again (default: new tensors)."""
+        N = self.b.N
+        cells = self._dev(cand_cells, torch.int32)
+        if cells.dim() != 4 or cells.shape[0] != N or cells.shape[3] != 2:
+            raise ValueError("route_gains: cand_cells must be [N, R, k, 2]")
+        R, k = int(cells.shape[1]), int(cells.shape[2])
+        field = self._dev(field, torch.float32)
+        if field.numel() != N * R * 3600:
+            raise ValueError("route_gains: field must be [N, R, 60, 60]")
+        hd = None if cand_heading is None else self._dev(cand_heading, torch.float64).reshape(N, R, k)
+        if mask is not None:
+            mask = self._t(mask, torch.uint8, (N, R))
+        ex = None if exclude is None else self._dev(exclude, torch.int64).reshape(N, 60)
+        W = _lib.IG_ROUTE_MAX_WAYPOINTS
+        spec = {"route_masks": ((N, R, k, 60), torch.int64), "total_masks": ((N, R, k, 60), torch.int64),
+                "route_gain": ((N, R, k), torch.float64), "total_gain": ((N, R, k), torch.float64), "utility": ((N, R, k), torch.float64),
+                "n_path": ((N, R, k), torch.int32), "n_way": ((N, R, k), torch.int32), "truncated": ((N, R, k), torch.uint8),
+                "best": ((N, R), torch.int32)}
+        if want_waypoints:
+            spec.update(way_cells=((N, R, k, W, 2), torch.int32), way_dir=((N, R, k, W), torch.int8))
+        out = self._out(out, spec)
+        ways = [out.get("way_cells"), out.get("way_dir")] if want_waypoints else [None, None]
+        if want_waypoints and (ways[0] is None or ways[1] is None):
+            raise ValueError("route_gains: want_waypoints=True needs out['way_cells'] and out['way_dir']")
+        P = _lib.IgRouteParams(R, k, int(stride), 0, float(radius), float(self.range if range is None else range), self.fov, float(d0))
+        _lib.call(self.L, self.b.h, "cagym_ig_route_gains", C.byref(P), _lib.ptr(mask), field.data_ptr(), cells.data_ptr(), _lib.ptr(hd),
+                  _lib.ptr(ex), *[out[n].data_ptr() for n in ("route_masks", "total_masks", "route_gain", "total_gain", "utility", "n_path",
+                                                               "n_way", "truncated", "best")], _lib.ptr(ways[0]), _lib.ptr(ways[1]), self.b._stream())
+        return out if want_waypoints else {n: v for n, v in out.items() if n not in ("way_cells", "way_dir")}
+
     def heading_list(self, headings):
         """The headings a caller means: an int H is h * 2 pi / H for h = 0..H-1, computed in fp64 here; a sequence is taken as
         given (radians).  Returns a list of 1..16 floats."""
@@ -876,6 +923,118 @@ def assign_goals_spec(masks, claimed0, distance, valid, reward, mode, d0, open_r
         claimed |= masks[r, c]
         left.remove(r)
     out["claimed"] = claimed
+    return out
+
+
+ROUTE_MAX_WAYPOINTS = _lib.IG_ROUTE_MAX_WAYPOINTS
+ROUTE_WALK_CAP = 3600  # moves per walk
+ROUTE_HEADING_M = (0, 2, 4, -2, 1, 3, -3, -1)  # a move in GEO_NEIGHBOURS order heads ROUTE_HEADING_M[d] * (pi / 4)
+
+
+def route_heading(d):
+    """The heading of a move in direction d of GEO_NEIGHBOURS: the double m * (pi / 4), one fp64 product."""
+    return ROUTE_HEADING_M[int(d)] * (math.pi / 4)
+
+
+def route_path_spec(field, cell):
+    """The walk of cagym_ig_route_gains from `cell` (i, j) down `field` [60, 60] f32 indexed [j, i] - a robot's geodesic field with
+    its own cell as the source - in plain numpy: the list of (i, j, move) in WALK order, the candidate's cell first, move the index in
+    GEO_NEIGHBOURS of the step taken out of the cell (None in the last cell, whose field is 0), or None when there is no route.
+      No route: the cell outside 0..59, or its field not finite.  From a cell whose value is not 0 the next cell is the neighbour
+      goal_action_spec chooses: GEO_NEIGHBOURS in order, finite values only, a diagonal only with both orthogonal neighbours finite,
+      key np.float32(field[n] + cost), the first of equal smallest keys.  No such neighbour, a neighbour whose value is not below the
+      cell's own, or more than 3600 moves: no route."""
+    field = np.asarray(field, dtype=np.float32).reshape(60, 60)
+    ci, cj = int(cell[0]), int(cell[1])
+    if not (0 <= ci < 60 and 0 <= cj < 60) or not np.isfinite(field[cj, ci]):
+        return None
+    at = lambda i, j: field[j, i] if (0 <= i < 60 and 0 <= j < 60) else np.float32(np.inf)
+    path = []
+    for s in range(ROUTE_WALK_CAP + 1):
+        cur = field[cj, ci]
+        if cur == 0:
+            path.append((ci, cj, None))
+            return path
+        if s == ROUTE_WALK_CAP:
+            break
+        best, pick = np.float32(np.inf), None
+        for k, (di, dj) in enumerate(GEO_NEIGHBOURS):
+            val = at(ci + di, cj + dj)
+            if not np.isfinite(val):
+                continue
+            if k >= 4 and not (np.isfinite(at(ci + di, cj)) and np.isfinite(at(ci, cj + dj))):
+                continue
+            key = np.float32(val + (GEO_ORTHO if k < 4 else GEO_DIAG))
+            if key < best:
+                best, pick = key, k
+        if pick is None or not at(ci + GEO_NEIGHBOURS[pick][0], cj + GEO_NEIGHBOURS[pick][1]) < cur:
+            return None
+        path.append((ci, cj, pick))
+        ci, cj = ci + GEO_NEIGHBOURS[pick][0], cj + GEO_NEIGHBOURS[pick][1]
+    return None
+
+
+def route_spec(field, cell, stride):
+    """The route of cagym_ig_route_gains for one candidate cell (i, j) of one robot, in numpy - its specification.  field [60, 60]
+    f32 indexed [j, i]: the robot's geodesic field with its own cell as the source (geodesic_spec's); stride >= 1.  Returns (n_path,
+    way_cells [n_way, 2] i32 (i, j), way_dir [n_way] i8, truncated).
+      route_path_spec walks q_0 = cell .. q_n, the cell whose field is 0; no route: (-1, no way-points, False).
+      Travel order: p_t = q_{n-t}.  The move INTO p_t, p_{t-1} -> p_t, is the opposite of the walk's move out of it: way_dir is its
+      index in GEO_NEIGHBOURS (the walk's index ^ 2), its heading route_heading(way_dir).
+      Way-points: t = stride, 2 stride, .. with t < n and t <= 16 stride, in travel order; truncated <=> a t < n beyond 16 stride
+      was dropped, that is, ceil(n / stride) - 1 > 16."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("route_spec: stride must be at least 1")
+    none = (-1, np.zeros((0, 2), dtype=np.int32), np.zeros(0, dtype=np.int8), False)
+    path = route_path_spec(field, cell)
+    if path is None:
+        return none
+    n = len(path) - 1
+    cells, dirs, truncated = [], [], False
+    for t in range(stride, n, stride):
+        if t > ROUTE_MAX_WAYPOINTS * stride:
+            truncated = True
+            break
+        i, j, move = path[n - t]
+        cells.append((i, j))
+        dirs.append(move ^ 2)
+    return n, np.array(cells, dtype=np.int32).reshape(-1, 2), np.array(dirs, dtype=np.int8), truncated
+
+
+def route_gains_spec(route_masks, terminal_masks, distance, has_route, reward, d0, exclude=None):
+    """The prices and the choice of cagym_ig_route_gains for ONE robot, in numpy - their specification, given the cell sets.
+    route_masks [k, 60, 60] bool indexed [j, i]: the union of every candidate's way-point sets (visible_cells of the poses
+    route_spec names); terminal_masks [k, 60, 60] bool: every candidate's own set by assign_goals_spec's rule (empty for an invalid
+    point); distance [k] f32: the robot's field at the candidate's cell; has_route [k]; reward(cells [60, 60] bool) -> float, as
+    assign_goals_spec takes it; d0 > 0; exclude [60, 60] bool or None: cells already spoken for.
+      A candidate without a route has empty masks, gains 0 and utility 0.  Else total = route | terminal, route_gain = reward(route
+      & ~exclude), total_gain = reward(total & ~exclude), utility = total_gain / ((double)distance + d0): one fp64 addition, one fp64
+      division.  best: the candidate with a route and total_gain > 0 of largest utility, of equal utilities the smaller index; -1
+      when there is none.
+    Returns a dict: route_masks, total_masks [k, 60, 60] bool (emptied where there is no route), route_gain, total_gain, utility
+    [k] f64 and best."""
+    route = np.array(route_masks, dtype=bool).reshape(-1, 60, 60)
+    k = route.shape[0]
+    term = np.asarray(terminal_masks, dtype=bool).reshape(k, 60, 60)
+    dist = np.asarray(distance, dtype=np.float32).reshape(k)
+    ok = np.asarray(has_route).reshape(k).astype(bool)
+    ex = np.zeros((60, 60), dtype=bool) if exclude is None else np.asarray(exclude, dtype=bool).reshape(60, 60)
+    d0 = float(d0)
+    route[~ok] = False
+    total = route | term
+    total[~ok] = False
+    out = {"route_masks": route, "total_masks": total, "route_gain": np.zeros(k), "total_gain": np.zeros(k), "utility": np.zeros(k), "best": -1}
+    best = None
+    for c in range(k):
+        if not ok[c]:
+            continue
+        out["route_gain"][c] = float(reward(route[c] & ~ex))
+        out["total_gain"][c] = tg = float(reward(total[c] & ~ex))
+        with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+            out["utility"][c] = u = float(np.float64(tg) / (np.float64(dist[c]) + np.float64(d0)))
+        if tg > 0 and (best is None or u > best):  # (ascending: the strict test keeps the first of equal utilities)
+            best, out["best"] = u, c
     return out
 
 

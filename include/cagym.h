@@ -691,6 +691,43 @@ int cagym_ig_assign_goals(void* env, const cagym_ig_assign_params* params, const
                           const double* claim_heading, int32_t* choice, int32_t* order, double* marginal, double* utility,
                           uint64_t* claimed, uint64_t* masks, double* round_gain, void* stream);
 
+/* ---- Route gains: what a robot sees on the way to a candidate goal ------------------------------------------------------------------
+ * cagym_ig_route_gains: ONE launch on `stream`, on demand (no step runs it), one workgroup of 256 threads per world, no host
+ * synchronisation, no global atomics, no unbounded loop; two launches give the same bytes.  Every candidate cell's shortest path is
+ * walked back on the robot's own geodesic field, the sensor cone is taken at way-points along it, and the union is priced.  params:
+ * cagym_ig_route_params, defined in include/cagym_ig_route.h (n_robots = R 1..8, k 1..16, stride >= 1, flags = 0, radius, range,
+ * fov, d0).
+ * Inputs, DEVICE: mask [N,R] u8 or NULL (= every robot); field [N,R,60,60] f32, each robot's geodesic field with its own position
+ * as the source, as cagym_ig_geodesic writes it; cand_cells [N,R,k,2] i32 (i, j), a row with a cell outside 0..59 has no route;
+ * cand_heading [N,R,k] f64 or NULL; exclude [N,60] u64 or NULL, cells already spoken for (e.g. cagym_ig_assign_goals' claimed).
+ *   walk: from the candidate's cell q_0 (field finite, else no route) to the neighbour cagym_ig_goal_actions would drive to - E, N,
+ *     W, S, NE, NW, SW, SE in this order, key fl32(field[n] + cost) over finite values only, a diagonal only with both orthogonal
+ *     neighbours finite, the first of equal smallest keys - until the cell whose field is 0, q_n.  A cell without such a neighbour,
+ *     a move that does not lower the field value, or more than 3600 moves: no route.
+ *   travel order: p_t = q_{n-t}; the heading into p_t is that of the move p_{t-1} -> p_t, the double m * (M_PI / 4) with m = 0, 2, 4,
+ *     -2, 1, 3, -3, -1 for E .. SE.
+ *   way-points: t = stride, 2 stride, .. with t < n and t <= 16 stride; truncated = 1 when a t < n beyond 16 stride was dropped.
+ *     A way-point's cell set is exactly the mask cagym_ig_visible_cells returns for (centre of its cell, heading into it) with this
+ *     fov and range.
+ *   route = the union of the way-point sets; terminal = the candidate's own set at its cell's centre by cagym_ig_assign_goals' rule
+ *     (finite cand_heading: the cone; none: a robot turning on the spot; EDF(centre) <= radius + 0.1: empty); total = route | terminal.
+ *   route_gain / total_gain = the double cagym_ig_mi_reward returns for route & ~exclude / total & ~exclude, bit for bit;
+ *     utility = total_gain / ((double)field[q_0] + d0).
+ *   best = the candidate with a route and total_gain > 0 of largest utility, of equal utilities the smaller index; none: -1.
+ * Outputs, DEVICE: route_masks, total_masks [N,R,k,60] u64; route_gain, total_gain, utility [N,R,k] f64 (no route: 0, empty masks);
+ * n_path [N,R,k] i32 the moves n, -1 = no route; n_way [N,R,k] i32; truncated [N,R,k] u8; best [N,R] i32; way_cells [N,R,k,16,2]
+ * i32 or NULL and way_dir [N,R,k,16] i8 or NULL: the way-points in travel order as (i, j) and the direction of the move into them
+ * (0..7 in the order above), rows past n_way -1.  Rows of robots outside the mask keep every byte; a world without a masked robot
+ * is neither read nor written.
+ * Errors, before anything is touched: CAGYM_E_STATE before cagym_ig_init; CAGYM_E_INVALID for a NULL params, field, cand_cells or
+ * required output, n_robots outside 1..8, k outside 1..16, stride < 1, flags != 0, a radius, range, fov or d0 that is not finite or
+ * not positive; CAGYM_E_DEVICE as every launching entry. */
+typedef struct cagym_ig_route_params cagym_ig_route_params;
+int cagym_ig_route_gains(void* env, const cagym_ig_route_params* params, const uint8_t* mask, const float* field,
+                         const int32_t* cand_cells, const double* cand_heading, const uint64_t* exclude, uint64_t* route_masks,
+                         uint64_t* total_masks, double* route_gain, double* total_gain, double* utility, int32_t* n_path,
+                         int32_t* n_way, uint8_t* truncated, int32_t* best, int32_t* way_cells, int8_t* way_dir, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
