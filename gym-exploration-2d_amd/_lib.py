@@ -186,6 +186,11 @@ class IgRouteParams(C.Structure):
 IG_ROUTE_MAX_WAYPOINTS = 16  # CAGYM_IG_ROUTE_MAX_WAYPOINTS
 
 
+class IgCreditParams(C.Structure):
+    """cagym_ig_credit_params (include/cagym_ig_credit.h; not in STRUCTS, as IgObserveParams)."""
+    _fields_ = [("n_robots", C.c_int32), ("flags", C.c_uint32), ("detect_range", C.c_float), ("fov_rad", C.c_double), ("range", C.c_double)]
+
+
 # cagym_ig_episode_log_ptrs (include/cagym_ig_episode_log.h): (field, typestr, shape in terms of L / N / M); the int32 capacity closes it
 IGLOG_FIELDS = [("key", "u4", "L"), ("world", "i4", "L"), ("episode", "i4", "L"), ("slice", "i8", "L"), ("steps", "i4", "L"),
                 ("ret", "f8", "L"), ("n_targets", "i4", "L"), ("n_found", "i4", "L"), ("found_at", "i4", "LM"), ("entropy", "f8", "L"),
@@ -293,6 +298,7 @@ _ARGTYPES = {
     "cagym_ig_view_gain_headings": [_vp, _P(IgHeadingParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_assign_goals": [_vp, _P(IgAssignParams)] + [_vp] * 15,
     "cagym_ig_route_gains": [_vp, _P(IgRouteParams)] + [_vp] * 17,
+    "cagym_ig_credit": [_vp, _P(IgCreditParams)] + [_vp] * 12,
     "cagym_ig_goal_face_actions": [_vp, _P(IgGoalParams), _vp, _vp, _vp, _vp, _vp],
     "cagym_ig_goal_face_status": [_vp, _P(IgGoalParams), C.c_double, _vp, _vp, _vp, _vp, _vp],
     "cagym_dmcts_workspace_bytes": [_int, _P(DmctsParams)],

@@ -44,6 +44,11 @@ class _IgGoals(object):
                  "route")  # (fifth: ig_route_gains' buffers, made on first use)
 
 
+class _IgCredit(object):
+    """attach_ig_credit's state: the tensors the credit launch writes and the per-robot accumulators it keeps."""
+    __slots__ = ("out", "acc")
+
+
 _OUT_KEYS = ("other_agents_states", "ego", "laserscan", "reward", "flags", "game_over")  # a rollout's buffers in CagymOutputs order
 GAME_OVER_MODES = {"agent0": _lib.GO_AGENT0, "all": _lib.GO_ALL, "learning": _lib.GO_LEARNING}
 
@@ -86,6 +91,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         self._ga3c = None
         self._igm = None
         self._goals = None        # attach_ig_goals' state, with attach_ig_learner only
+        self._credit = None       # attach_ig_credit's state, with attach_ig_learner only
         self._act = None          # [N, M, 2] f32 action table of an internal step (the caller's buffer is only read)
         self.team_reward = None   # [N] f64: the team's MI reward of the last step with ig_mcts attached (policy.team_reward)
         self._init_pool()
@@ -167,6 +173,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             if m is None:  # a new episode everywhere: prior beliefs, no running return, then the first observation of every world
                 g.ig.reset_belief(None)
                 g.ig.episode_stats["running"].zero_()
+                if self._credit is not None:
+                    self._credit.acc["running"].zero_()
                 self._ig_observe(None, 0)
                 if self._goals is not None:  # new maps everywhere: no goal survives
                     self._goals.out["active"].zero_()
@@ -219,7 +227,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         self._refuse_keep("attach_%s" % kind, "an attached IG planner's per-world restart reads the game_over of the auto-resetting launch; "
                           "the three-launch step has not been taken through it")
         R = self._n_ig if self._n_ig is not None else 0
-        self._igm = self._goals = None
+        self._igm = self._goals = self._credit = None
         ig = InfoGain(self, fov_rad=detect_fov * np.pi / 180, sens_range=detect_range, xdt=xdt, dt=self.cfg.dt)
         N, K, dev = self.N, self.K, self.device
         g = _IgState()
@@ -302,6 +310,53 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         if g.context_window is not None:  # the second image, of the worlds the observe launch just wrote and of no other
             g.ig.context_window(g.R, g.context_window, g.window, g.rotate, g.clear_max, g.observed, restart_mask,
                                 CONTEXT_ONLY_MASKED if flags & OBSERVE_ONLY_RESTARTED else 0)
+        q = self._credit
+        if q is not None:  # whose cone earned it: the same mask and flags, on the belief the observe launch just left
+            g.ig.robot_credit(g.R, g.range, self.obs_oas, restart_mask, flags, q.out, q.acc)
+
+    def attach_ig_credit(self):
+        """Per-robot credit for the team reward (needs attach_ig_learner): from now on every observe launch - behind step() and
+        reset() - is followed by ONE cagym_ig_credit launch with the same restart mask and flags (behind the context launch where
+        there is one), and step()'s info gains
+          "credit" [N, R, 3] f64 - per robot: own, the MI sum over the cells of its own cone; exclusive, over the cells no
+              teammate saw as well; difference, the team's gain minus what the gain would have been had this robot not looked
+              (its odds factor divided out of the cells it shares, its other cells dropped) - raw, as "gain" is;
+          "robot_reward" [N, R, 3] f64 - credit, but 0 for a world the step just restarted, as team_reward is;
+          "robot_observed" [N, R, 60] i64 - each robot's visible cells (their union is "observed");
+          "loo" [N, R] f64 - the leave-one-out gain itself
+        (ig.robot_credit_spec states all of it).  ig_robot_episode_stats() hands out per-robot accumulators kept as
+        ig_episode_stats() keeps the team's.  reset(world_mask=m) leaves the other worlds' rows as they were.  Attaching another IG
+        policy, or detach_ig_mcts(), drops it.  Without this call nothing is allocated, no launch runs and info has no such key.
+        The built-in planners, the exploration episode log, rollout(), snapshot and checkpoint know nothing of it."""
+        g = self._igm
+        if g is None or g.kind != "ig_learner":
+            raise RuntimeError("attach_ig_credit needs attach_ig_learner first: the credit is for the learner's robots")
+        N, R, dev = self.N, g.R, self.device
+        q = _IgCredit()
+        q.out = {"gain": torch.zeros((N,), dtype=torch.float64, device=dev),
+                 "robot_observed": torch.zeros((N, R, 60), dtype=torch.int64, device=dev),
+                 "credit": torch.zeros((N, R, 3), dtype=torch.float64, device=dev),
+                 "loo": torch.zeros((N, R), dtype=torch.float64, device=dev),
+                 "reward": torch.zeros((N, R, 3), dtype=torch.float64, device=dev)}
+        q.acc = {k: torch.zeros((N, R, 3), dtype=torch.float64, device=dev) for k in ("running", "sum", "last")}
+        q.acc["episodes"] = torch.zeros((N,), dtype=torch.int32, device=dev)
+        self._credit = q
+
+    def ig_robot_credit(self):
+        """The device tensors the last credit launch wrote (attach_ig_credit), by the names of InfoGain.robot_credit: gain [N] f64 -
+        the team's gain as that launch recomputed it, observe's bit for bit -, robot_observed [N, R, 60] i64, credit [N, R, 3] f64,
+        loo [N, R] f64 and reward [N, R, 3] f64 (info["robot_reward"])."""
+        if self._credit is None:
+            raise RuntimeError("ig_robot_credit() needs attach_ig_credit")
+        return dict(self._credit.out)
+
+    def ig_robot_episode_stats(self):
+        """Device views of the per-robot accumulators attach_ig_credit keeps, [N, R, 3] f64 over (own, exclusive, difference):
+        running - the return of the episode in progress, sum - over the finished episodes, last - of the last finished one; and
+        episodes [N] i32, the finished episodes per world."""
+        if self._credit is None:
+            raise RuntimeError("ig_robot_episode_stats() needs attach_ig_credit")
+        return dict(self._credit.acc)
 
     def attach_ig_goals(self, radius=0.5, v_max=2.0, w_max=np.pi, align_tol=np.pi / 4, goal_tol=0.25, face_tol=np.pi / 18):
         """Goal actions for the learner's robots (needs attach_ig_learner): from now on a robot may be given a PLACE to go to
@@ -623,7 +678,7 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
                 self._igm.ig.goal_face_status(q.P, q.out, q.goal_heading, q.goal_facing, q.face_tol)
 
     def detach_ig_mcts(self):
-        self._igm = self._goals = None
+        self._igm = self._goals = self._credit = None
         self.team_reward = None
 
     def _alloc_act(self):
@@ -698,7 +753,8 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
         (VecEnv semantics: the returned observation is the first one of the new episode).  With a policy attached
         (attach_ga3c / attach_ig_mcts) its agents' rows of `actions` are ignored and the env computes them; `actions`
         itself is only read.  With attach_ig_learner the robots' rows are the learner's (v, omega), and info also carries
-        "belief_window", "gain" and "observed" of the state the step left, with context=True "context_window", and with
+        "belief_window", "gain" and "observed" of the state the step left, with context=True "context_window", with
+        attach_ig_credit "credit", "robot_reward", "robot_observed" and "loo", and with
         attach_ig_goals "goal_distance" and "goal_reached" (and "goal_facing" once a goal has carried a heading)."""
         if auto_reset and self._igm is not None and not self._igm.episodic:
             k = self._igm.kind
@@ -714,6 +770,9 @@ class BatchedCollisionAvoidanceEnv(_PoolMixin, _ConsumersMixin, _SnapshotMixin, 
             info.update(belief_window=g.belief_window, gain=g.gain, observed=g.observed)
             if g.context_window is not None:
                 info["context_window"] = g.context_window
+            if self._credit is not None:
+                o = self._credit.out
+                info.update(credit=o["credit"], robot_reward=o["reward"], robot_observed=o["robot_observed"], loo=o["loo"])
             if self._goals is not None:
                 info.update(goal_distance=self._goals.goal_distance, goal_reached=self._goals.goal_reached)
                 if self._goals.goal_heading is not None:

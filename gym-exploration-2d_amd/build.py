@@ -31,6 +31,7 @@ HEADERS = K3_HEADERS + ["cagym_gen1.h", "cagym_sensors.h", "cagym_ig.h", "cagym_
                         "cagym_ig_headings.h", "../../include/cagym_ig_headings.h",
                         "cagym_ig_assign.h", "../../include/cagym_ig_assign.h",
                         "cagym_ig_route.h", "../../include/cagym_ig_route.h",
+                        "cagym_ig_credit.h", "../../include/cagym_ig_credit.h",
                         "cagym_ig_episode_log.h", "../../include/cagym_ig_episode_log.h",
                         "cagym_episode_records.h", "cagym_episode_log.h", "cagym_snapshot.h", "cagym_stream.h",
                         "cagym_explore.h", "cagym_terminal.h", "cagym_replay.h", "cagym_checkpoint.h", "cagym_layout.h"]

@@ -17,6 +17,7 @@
 #include "../../include/cagym_ig_headings.h"
 #include "../../include/cagym_ig_assign.h"
 #include "../../include/cagym_ig_route.h"
+#include "../../include/cagym_ig_credit.h"
 #include "../../include/cagym_ig_episode_log.h"
 #include "cagym_gen1.h"
 #include "cagym_sensors.h"
@@ -41,6 +42,7 @@
 #include "cagym_ig_headings.h"
 #include "cagym_ig_assign.h"
 #include "cagym_ig_route.h"
+#include "cagym_ig_credit.h"
 #include "cagym_ig_episode_log.h"
 #include "cagym_episode_records.h"
 #include "cagym_episode_log.h"
@@ -2175,6 +2177,29 @@ int cagym_ig_context_window(void* env, const cagym_ig_context_params* params, co
     P.R = p.n_robots; P.G = p.window; P.rotate = p.rotate; P.flags = p.flags; P.clear_max = p.clear_max;
     hipLaunchKernelGGL(k_ig_context_window, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G,
                        P, reinterpret_cast<const unsigned long long*>(observed), world_mask, context_window);
+    HIPCHK(e, hipGetLastError());
+    return CAGYM_OK;
+}
+
+int cagym_ig_credit(void* env, const cagym_ig_credit_params* params, const float* obs_oas, const uint8_t* restart_mask, double* gain,
+                    uint64_t* robot_observed, double* credit, double* loo, double* reward, double* running, double* sum, double* last,
+                    int32_t* episodes, void* stream) {
+    ENTRY_IG(e, env, "cagym_ig_credit");
+    if (!params || !obs_oas) return fail(e, CAGYM_E_INVALID, "cagym_ig_credit: null argument");
+    const cagym_ig_credit_params& p = *params;
+    const char* name = "cagym_ig_credit";
+    if (int rc = ig_team_check(e, name, p.n_robots)) return rc;  // (R may exceed the pool's team: the rows past it are zero)
+    if (int rc = ig_flags_check(e, name, p.flags, CAGYM_IG_EPISODE_FOLD | CAGYM_IG_OBSERVE_ONLY_RESTARTED)) return rc;
+    if (int rc = ig_positive_check(e, name, {p.fov_rad, p.range, (double)p.detect_range}, "fov_rad, range and detect_range must be finite and positive"))
+        return rc;
+    ON_DEVICE(e);
+    IgCreditParams P;
+    P.R = p.n_robots; P.flags = p.flags; P.det_range = p.detect_range; P.fov = p.fov_rad; P.range = p.range;
+    IgCreditOut O;
+    O.gain = gain; O.robot_observed = reinterpret_cast<unsigned long long*>(robot_observed); O.credit = credit; O.loo = loo; O.reward = reward;
+    O.running = running; O.sum = sum; O.last = last; O.episodes = episodes;
+    hipLaunchKernelGGL(k_ig_credit, dim3((unsigned)e->cfg.n_worlds), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), e->D, e->G, P, obs_oas,
+                       restart_mask, O);
     HIPCHK(e, hipGetLastError());
     return CAGYM_OK;
 }

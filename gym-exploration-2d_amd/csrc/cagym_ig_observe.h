@@ -24,6 +24,67 @@ struct IgObserveParams {
     double fov, range;
 };
 
+// Phase 2 below, poses and detections of world w's R robots into LDS (k_ig_robot_inputs on wave 0, lane j = slot j): the ONE statement
+// of it, for this kernel and for k_ig_credit (cagym_ig_credit.h), which must see the robots exactly as this launch did.  A slot past the
+// world's team gets a zero pose and no rows.  each(r, slot, heading) runs on lane 0 per robot (slot < 0: no such robot).
+template <typename F>
+__device__ __forceinline__ void ig_robot_inputs_lds(const CagymDev& D, int w, int lane, int R, float det_range, const float* __restrict__ oas,
+                                                    double (*s_pose)[3], double (*s_det)[IG_MAXK][2], int* s_nd, F each) {
+    const int M = D.M, K = M - 1;
+    unsigned long long robots;
+    ig_robot_slot(D, w, lane, robots);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int r = 0; r < R; r++) {
+        const int slot = ig_next_robot(robots);
+        double px = 0.0, py = 0.0, th = 0.0;
+        int cnt = 0;
+        if (slot >= 0) {
+            const size_t a = (size_t)w * M + slot;
+            px = D.px[a]; py = D.py[a]; th = D.heading[a];
+            bool tgt = false;
+            float r0 = 0.f, r1 = 0.f;
+            if (lane < K) {
+                const float* row = oas + (a * K + lane) * 10;
+                r0 = row[0];
+                r1 = row[1];
+                tgt = row[9] == 1.0f && sqrtf(r0 * r0 + r1 * r1) <= det_range;
+            }
+            const unsigned long long tm = __ballot(tgt);
+            if (tgt) {
+                double* d = s_det[r][__popcll(tm & below)];
+                d[0] = (double)r0 + px;
+                d[1] = (double)r1 + py;
+            }
+            cnt = __popcll(tm);
+        }
+        if (lane < 3) s_pose[r][lane] = lane == 0 ? px : lane == 1 ? py : th;
+        if (lane == 0) {
+            s_nd[r] = cnt;
+            each(r, slot, th);
+        }
+    }
+}
+
+// The odds factor of belief cell (i, j) under a robot at (px, py) with (c, s) = (cos, sin) of its heading and nd detections det:
+// 1.5 when a detection lies within thr of the cell's centre (both points rotated by mat2vec, k_ig_update's expression), else 0.66.
+__device__ __forceinline__ double ig_odds_factor(int i, int j, double px, double py, double c, double s, const double (*det)[2], int nd,
+                                                 double thr) {
+    double rs = 0.66;
+    if (nd > 0) {
+        double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
+        double r0, r1;
+        mat2vec(c, s, cx - px, cy - py, r0, r1);
+        for (int d = 0; d < nd; d++) {
+            const double* tg = det[d];
+            double t0, t1;
+            mat2vec(c, s, tg[0] - px, tg[1] - py, t0, t1);
+            double e0 = t0 - r0, e1 = t1 - r1;
+            if (sqrt(e0 * e0 + e1 * e1) < thr) { rs = 1.5; break; }
+        }
+    }
+    return rs;
+}
+
 __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpisode A, IgObserveParams P, const float* __restrict__ oas,
                                                     const uint8_t* __restrict__ restart_mask, double* team_reward, double* gain,
                                                     unsigned long long* observed, float* window) {
@@ -34,7 +95,7 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
     __shared__ double s_sc[IG_MAXR][2];  // the window's (sin, cos) of each robot
     __shared__ double s_det[IG_MAXR][IG_MAXK][2];
     __shared__ int s_nd[IG_MAXR];
-    const int w = blockIdx.x, tid = threadIdx.x, M = D.M, K = M - 1, R = P.R;
+    const int w = blockIdx.x, tid = threadIdx.x, R = P.R;
     const bool restarted = restart_mask && restart_mask[w];  // uniform
     if ((P.flags & 4u) && !restarted) return;                // CAGYM_IG_OBSERVE_ONLY_RESTARTED: nothing of this world is read or written
 
@@ -54,44 +115,13 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
     if (restarted) ig_fill_world_prior(G, w, tid, blockDim.x);
 
     // 2. poses and detections (k_ig_robot_inputs on wave 0, lane j = slot j), into LDS
-    if (tid < 64) {
-        const int lane = tid;
-        unsigned long long robots;
-        ig_robot_slot(D, w, lane, robots);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        for (int r = 0; r < R; r++) {
-            const int slot = ig_next_robot(robots);
-            double px = 0.0, py = 0.0, th = 0.0;
-            int cnt = 0;
-            if (slot >= 0) {
-                const size_t a = (size_t)w * M + slot;
-                px = D.px[a]; py = D.py[a]; th = D.heading[a];
-                bool tgt = false;
-                float r0 = 0.f, r1 = 0.f;
-                if (lane < K) {
-                    const float* row = oas + (a * K + lane) * 10;
-                    r0 = row[0];
-                    r1 = row[1];
-                    tgt = row[9] == 1.0f && sqrtf(r0 * r0 + r1 * r1) <= P.det_range;
-                }
-                const unsigned long long tm = __ballot(tgt);
-                if (tgt) {
-                    double* d = s_det[r][__popcll(tm & below)];
-                    d[0] = (double)r0 + px;
-                    d[1] = (double)r1 + py;
-                }
-                cnt = __popcll(tm);
-            }
-            if (lane < 3) s_pose[r][lane] = lane == 0 ? px : lane == 1 ? py : th;
-            if (lane == 0) {
-                s_nd[r] = cnt;
-                double s, c;
-                ig_window_sincos(P.rotate, th, s, c);
-                s_sc[r][0] = s;
-                s_sc[r][1] = c;
-            }
-        }
-    }
+    if (tid < 64)
+        ig_robot_inputs_lds(D, w, tid, R, P.det_range, oas, s_pose, s_det, s_nd, [&](int r, int, double th) {
+            double s, c;
+            ig_window_sincos(P.rotate, th, s, c);
+            s_sc[r][0] = s;
+            s_sc[r][1] = c;
+        });
     for (int j = tid; j < IG_BEL; j += blockDim.x) uni[j] = 0ull;
     __syncthreads();  // (also: the prior of a restarted world is in place)
 
@@ -109,20 +139,7 @@ __global__ void __launch_bounds__(256) k_ig_observe(CagymDev D, IgDev G, IgEpiso
         for (int q = tid; q < IG_BEL * IG_BEL; q += blockDim.x) {
             int j = q / IG_BEL, i = q - j * IG_BEL;
             if (!((vis[j] >> i) & 1ull)) continue;
-            double rs = 0.66;
-            if (nd > 0) {
-                double cx = ig_cell_centre(i), cy = ig_cell_centre(j);
-                double r0, r1;
-                mat2vec(c, s, cx - px, cy - py, r0, r1);
-                for (int d = 0; d < nd; d++) {
-                    const double* tg = s_det[p][d];
-                    double t0, t1;
-                    mat2vec(c, s, tg[0] - px, tg[1] - py, t0, t1);
-                    double e0 = t0 - r0, e1 = t1 - r1;
-                    if (sqrt(e0 * e0 + e1 * e1) < thr) { rs = 1.5; break; }
-                }
-            }
-            bel[q] *= rs;
+            bel[q] *= ig_odds_factor(i, j, px, py, c, s, s_det[p], nd, thr);
         }
         for (int j = tid; j < IG_BEL; j += blockDim.x) uni[j] |= vis[j];
         __syncthreads();

@@ -296,6 +296,28 @@ class InfoGain(object):
                                                                "n_way", "truncated", "best")], _lib.ptr(ways[0]), _lib.ptr(ways[1]), self.b._stream())
         return out if want_waypoints else {n: v for n, v in out.items() if n not in ("way_cells", "way_dir")}
 
+    def robot_credit(self, n_robots, detect_range, obs_oas, restart_mask=None, flags=0, out=None, accumulators=None, range=None):
+        """cagym_ig_credit: ONE launch on the current stream, directly behind observe() (and context_window()) with the same obs_oas,
+        restart_mask and flags - whose cone earned the team's gain (ig.robot_credit_spec states the rule).  Returns the dict of device
+        tensors it wrote: gain [N] f64 (observe's gain, bit for bit), robot_observed [N,R,60] i64 (each robot's visible cells),
+        credit [N,R,3] f64 (own: the MI sum over the robot's cells; exclusive: over the cells it alone saw; difference: gain minus
+        what the gain would have been had it not looked), loo [N,R] f64 (that leave-one-out gain) and reward [N,R,3] f64 (credit, but
+        0 for a world restarted in this launch, as team_reward is).  `out`: such a dict to write into again (default: new tensors); a
+        key it lacks is not written.  accumulators: a dict of running, sum, last [N,R,3] f64 and episodes [N] i32 that the launch
+        keeps by observe's statements per robot and kind (EPISODE_FOLD folds a restarted world's running values), or None.  R may
+        exceed the worlds' teams: the rows past a team are zero (loo = gain).  OBSERVE_ONLY_RESTARTED skips every other world.  range:
+        the cones' sensing range in metres (default: this object's, which is what observe() uses)."""
+        N, R = self.b.N, int(n_robots)
+        if out is None:
+            out = self._out(None, {"gain": ((N,), torch.float64), "robot_observed": ((N, R, 60), torch.int64), "credit": ((N, R, 3), torch.float64),
+                                   "loo": ((N, R), torch.float64), "reward": ((N, R, 3), torch.float64)})
+        acc = accumulators or {}
+        P = _lib.IgCreditParams(R, int(flags), float(detect_range), self.fov, float(self.range if range is None else range))
+        _lib.call(self.L, self.b.h, "cagym_ig_credit", C.byref(P), obs_oas.data_ptr(), _lib.ptr(restart_mask),
+                  *[_lib.ptr(out.get(n)) for n in ("gain", "robot_observed", "credit", "loo", "reward")],
+                  *[_lib.ptr(acc.get(n)) for n in ("running", "sum", "last", "episodes")], self.b._stream())
+        return out
+
     def heading_list(self, headings):
         """The headings a caller means: an int H is h * 2 pi / H for h = 0..H-1, computed in fp64 here; a sequence is taken as
         given (radians).  Returns a list of 1..16 floats."""
@@ -1070,6 +1092,70 @@ def propose_goals_spec(gain, valid, field, k, min_sep, d0):
         out["utility"][n], out["gain"][n], out["distance"][n] = util[j, i], gain[j, i], field[j, i]
         out["n_found"] = n + 1
         util[((ii - i) ** 2 + (jj - j) ** 2).astype(np.float64) * 0.25 < sep2] = -1.0
+    return out
+
+
+def block_sum_spec(values, member):
+    """The MI sums of the library in their own order (ig_reward_block of csrc/cagym_ig.h): values, member [60, 60] indexed [j, i];
+    thread q % 256 adds the values of its member cells q = 60 j + i in ascending order, then the 256 partial sums go through the
+    halving tree.  Sequential fp64 additions: the library's bits, given its values.  An empty set sums to +0.0."""
+    v = np.where(np.asarray(member, dtype=bool).ravel(), np.asarray(values, dtype=np.float64).ravel(), 0.0)  # (x + 0.0 is x for x >= +0.0)
+    v = np.concatenate([v, np.zeros(15 * 256 - 3600)]).reshape(15, 256)
+    acc = np.zeros(256)
+    for row in v:
+        acc = acc + row
+    h = 128
+    while h > 0:
+        acc[:h] = acc[:h] + acc[h:2 * h]
+        h //= 2
+    return float(acc[0])
+
+
+def robot_credit_spec(belief, mi, masks, poses, oas_rows, det_range=5.0):
+    """The per-robot credit of cagym_ig_credit for ONE world, in numpy - its specification, given the robots' cell sets.  belief, mi
+    [60, 60] f64 indexed [j, i]: the world's odds ratios and MI cache as the observe launch left them; masks [R, 60] u64 (or i64),
+    robot r's visible cells V_r (bit i of word j <=> cell (i, j); an absent robot: zeros); poses [R, 3] f64 (x, y, heading);
+    oas_rows [R, K, 10] f32, the robots' OtherAgentsStates rows (an absent robot: zeros).  Returns a dict:
+      "detections": a list of R arrays [n_r, 2] f64 - row + pose for the rows with row[9] == 1 and sqrt(r0^2 + r1^2) <= det_range,
+          the test in fp32 as the table is, in row order;
+      "factor" [R, 60, 60] f64: f_r = 1.5 where a detection of robot r lies within sqrt(0.5) * 0.5 + 0.01 of the cell's centre,
+          both rotated into the robot's frame (the belief update's test), else 0.66 - over the whole grid, not only V_r;
+      "gain": the sum of mi over U, the union of the V_r;
+      "own" [R]: over V_r; "exclusive" [R]: over V_r & ~U_-r, U_-r the union of V_s over s != r;
+      "loo" [R]: over q in U_-r of (q in V_r ? cell_mi(belief[q] / f_r(q)) : mi[q]) - the gain had robot r not looked;
+      "difference" [R] = gain - loo.
+    Every sum runs in block_sum_spec's order.  own, exclusive and gain are the library's bits given its mi; loo agrees up to the last
+    bits of the logarithms and of numpy's sine and cosine (the library's rotation also fuses one product into its sum)."""
+    belief, mi = np.asarray(belief, dtype=np.float64).reshape(60, 60), np.asarray(mi, dtype=np.float64).reshape(60, 60)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    R = poses.shape[0]
+    words = np.asarray(masks).reshape(R, 60).astype(np.uint64)
+    V = ((words[:, :, None] >> np.arange(60, dtype=np.uint64)[None, None, :]) & np.uint64(1)).astype(bool)  # [R, j, i]
+    rows = np.asarray(oas_rows, dtype=np.float32).reshape(R, -1, 10)
+    centre = np.arange(60, dtype=np.float64) * 0.5 - 15.0 + 0.25
+    cx, cy = centre[None, :], centre[:, None]
+    thr = np.sqrt(0.5) * 0.5 + 0.01
+    dets, factor = [], np.full((R, 60, 60), 0.66)
+    for r in range(R):
+        px, py, th = poses[r]
+        r0, r1 = rows[r, :, 0], rows[r, :, 1]
+        hit = (rows[r, :, 9] == np.float32(1.0)) & (np.sqrt(r0 * r0 + r1 * r1) <= np.float32(det_range))  # fp32 throughout
+        d = np.stack([r0[hit].astype(np.float64) + px, r1[hit].astype(np.float64) + py], axis=1)
+        dets.append(d)
+        c, s = np.cos(th), np.sin(th)
+        q0, q1 = c * (cx - px) + s * (cy - py), -s * (cx - px) + c * (cy - py)
+        for tx, ty in d:
+            t0, t1 = c * (tx - px) + s * (ty - py), -s * (tx - px) + c * (ty - py)
+            factor[r][np.sqrt((t0 - q0) ** 2 + (t1 - q1) ** 2) < thr] = 1.5
+    U = V.any(axis=0)
+    out = {"detections": dets, "factor": factor, "gain": block_sum_spec(mi, U), "own": np.zeros(R), "exclusive": np.zeros(R),
+           "loo": np.zeros(R), "difference": np.zeros(R)}
+    for r in range(R):
+        others = np.delete(V, r, axis=0).any(axis=0) if R > 1 else np.zeros((60, 60), dtype=bool)
+        out["own"][r] = block_sum_spec(mi, V[r])
+        out["exclusive"][r] = block_sum_spec(mi, V[r] & ~others)
+        out["loo"][r] = block_sum_spec(np.where(V[r], cell_mi(belief / factor[r]), mi), others)
+        out["difference"][r] = out["gain"] - out["loo"][r]
     return out
 
 

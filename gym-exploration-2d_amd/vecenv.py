@@ -116,9 +116,78 @@ class CagymVecEnv(object):
                     infos["context_window"] = info["context_window"]
                 if "goal_distance" in info:  # attach_ig_goals: metres to go along the grid, and goal reached
                     infos["goal_distance"], infos["goal_reached"] = info["goal_distance"], info["goal_reached"]
+                if "robot_reward" in info:  # attach_ig_credit: the team reward told apart per robot, [N, R, 3] f64
+                    infos["robot_reward"] = info["robot_reward"]
         if self.terminal_observation:
             infos["terminal_observation"] = self.flat(info["terminal"])
         return self.flat(), rews, go.bool(), infos
+
+    def step(self, actions):
+        self.step_async(actions)
+        return self.step_wait()
+
+    def close(self):
+        self.b.close()
+
+
+ROBOT_REWARDS = {"own": 0, "exclusive": 1, "difference": 2}  # the columns of info["robot_reward"] (attach_ig_credit)
+
+
+class CagymRobotVecEnv(object):
+    """The learner's robots as the N * R environments a standard training loop wants: env index w * R + r is robot r (slot order)
+    of world w.  Needs attach_ig_learner; attach_ig_credit is switched on here when a per-robot reward is asked for and the env does
+    not have it yet.
+      obs  [N*R, 3, G, G] f32: each robot's belief window; [N*R, 6, G, G] with attach_ig_learner(context=True), the context window's
+           three channels behind the belief's.
+      step(actions [N*R, 2]): the robots' (v, omega).  They go into the robots' rows of a table [N, M, 2] this object owns, whose
+           other rows stay zero (cagym_ig_robot_actions, on the device), and benv.step(table, auto_reset=True) runs; a robot that
+           holds a goal (attach_ig_goals) still follows the controller.
+      rews [N*R] f64: reward="difference" | "own" | "exclusive" - that column of info["robot_reward"]; "team" - team_reward, the
+           same number for every robot of a world.
+      dones [N*R] bool: the world's game_over, repeated per robot.
+      infos: "team_reward" [N] and, with the credit attached, "credit" [N, R, 3]; the goal keys where present.
+    Everything stays on the GPU; nothing synchronises."""
+
+    def __init__(self, benv, reward="difference"):
+        g = getattr(benv, "_igm", None)
+        if g is None or g.kind != "ig_learner":
+            raise RuntimeError("CagymRobotVecEnv needs attach_ig_learner: its environments are the learner's robots")
+        if reward != "team" and reward not in ROBOT_REWARDS:
+            raise ValueError("CagymRobotVecEnv: reward must be one of 'difference', 'own', 'exclusive', 'team', got %r" % (reward,))
+        if reward != "team" and benv._credit is None:
+            benv.attach_ig_credit()
+        self.b, self.reward, self.R = benv, reward, g.R
+        self.num_envs = benv.N * g.R
+        self._table = torch.zeros((benv.N, benv.M, 2), dtype=torch.float32, device=benv.device)
+        self._actions = None
+
+    def _obs(self):
+        g = self.b._igm
+        w = g.belief_window if g.context_window is None else torch.cat([g.belief_window, g.context_window], dim=2)
+        return w.reshape(self.num_envs, w.shape[2], g.window, g.window)
+
+    def reset(self):
+        self.b.reset()
+        return self._obs()
+
+    def step_async(self, actions):
+        self._actions = actions
+
+    def step_wait(self):
+        b, R = self.b, self.R
+        planned = torch.as_tensor(self._actions, device=b.device).to(torch.float64).reshape(b.N, R, 2).contiguous()
+        self._table.zero_()  # (a streamed world may come back with its robots in other slots)
+        b._igm.ig.robot_actions(R, planned, self._table)
+        _, _, go, info = b.step(self._table, auto_reset=True)
+        if self.reward == "team":
+            rews = b.team_reward.repeat_interleave(R)
+        else:
+            rews = info["robot_reward"][:, :, ROBOT_REWARDS[self.reward]].reshape(self.num_envs)
+        infos = {"team_reward": b.team_reward}
+        for k in ("credit", "goal_distance", "goal_reached", "goal_facing"):
+            if k in info:
+                infos[k] = info[k]
+        return self._obs(), rews, go.bool().repeat_interleave(R), infos
 
     def step(self, actions):
         self.step_async(actions)

@@ -728,6 +728,39 @@ int cagym_ig_route_gains(void* env, const cagym_ig_route_params* params, const u
                          uint64_t* total_masks, double* route_gain, double* total_gain, double* utility, int32_t* n_path,
                          int32_t* n_way, uint8_t* truncated, int32_t* best, int32_t* way_cells, int8_t* way_dir, void* stream);
 
+/* ---- Per-robot credit for the team reward: own, exclusive and difference rewards ----------------------------------------------------
+ * cagym_ig_observe gives a team ONE number per world; this call says whose cone earned it.  ONE launch on `stream` (one workgroup of
+ * 256 threads per world), to be enqueued directly behind cagym_ig_observe (and behind cagym_ig_context_window where there is one) with
+ * the same obs_oas, restart_mask and flags; no host synchronisation, no global atomics, barriers only; two launches give the same
+ * bytes; it writes nothing of the handle.  params: cagym_ig_credit_params, defined in include/cagym_ig_credit.h (n_robots = R 1..8,
+ * flags, detect_range fp32, fov_rad, range).  belief and mi below are the world's belief and MI cache as the observe launch left them.
+ * For world w (skipped - nothing read or written - with CAGYM_IG_OBSERVE_ONLY_RESTARTED when it is not restarted) and its robots
+ * r = 0..R-1, the active CAGYM_POL_IGMCTS slots in slot order (a row past the world's team: no pose, no detections, V_r empty):
+ *   pose and detections of robot r as cagym_ig_robot_inputs computes them;
+ *   V_r = the mask cagym_ig_visible_cells returns for (pose, fov_rad, range) on the world's current scenario slot; U = the union of
+ *     all V_r; U_-r = the union of V_s over s != r;
+ *   f_r(q) = 1.5 when cell q passes cagym_ig_update_belief's detection test for robot r (a detection within sqrt(0.5) 0.5 + 0.01 of
+ *     the cell's centre, both rotated into the robot's frame), else 0.66;
+ *   gain = the MI sum over U - cagym_ig_observe's gain[w], bit for bit;
+ *   own[r] = the MI sum over V_r, exclusive[r] = the MI sum over V_r & ~U_-r - both bit for bit what cagym_ig_mi_reward returns for
+ *     that mask;
+ *   loo[r] = the sum over q in U_-r of (q in V_r ? cell_mi(belief[q] / f_r(q)) : mi[q]), in cagym_ig_mi_reward's order (thread
+ *     q % 256 accumulates its cells strided, then the halving tree); an empty U_-r sums to +0.0: what the gain would have been had
+ *     robot r not looked;
+ *   difference[r] = gain - loo[r], the difference reward.  A row past the team: own = exclusive = difference = 0, loo = gain.
+ * Outputs, DEVICE, caller-owned, each may be NULL: gain [N] f64; robot_observed [N,R,60] u64 = V_r; credit [N,R,3] f64 = (own,
+ * exclusive, difference), raw as gain is; loo [N,R] f64; reward [N,R,3] f64 = credit, but 0 for a world restarted in this launch, as
+ * team_reward is; the accumulators running, sum, last [N,R,3] f64 and episodes [N] i32, by cagym_ig_observe's statements per robot
+ * and kind: if restarted: with CAGYM_IG_EPISODE_FOLD sum += running, last = running, episodes[w] += 1; running = 0; then
+ * running += credit.  running NULL: no accumulator but episodes is touched.
+ * Errors: CAGYM_E_INVALID for a NULL env, params or obs_oas, n_robots outside 1..8, unknown flags, a non-finite or non-positive
+ * fov_rad, range or detect_range; CAGYM_E_STATE before cagym_ig_init; CAGYM_E_DEVICE as every launching entry.  A refused call
+ * writes nothing. */
+typedef struct cagym_ig_credit_params cagym_ig_credit_params;
+int cagym_ig_credit(void* env, const cagym_ig_credit_params* params, const float* obs_oas, const uint8_t* restart_mask, double* gain,
+                    uint64_t* robot_observed, double* credit, double* loo, double* reward, double* running, double* sum, double* last,
+                    int32_t* episodes, void* stream);
+
 /* ---- Per-scenario episode records under auto-reset (experiments/src/env_utils.py:41-62 reads them from prev_episode_agents;
  * process_full_test_suite_pickles.py:90-116 turns them into the published table) ---------------------------------------------------
  * An auto-resetting step re-initialises a finished world inside the launch that finished it; the recorder rebuilds what the reference
